@@ -16,11 +16,21 @@ that N devices are visible and starts `python -m torch.distributed.run --nproc-p
 an exec), relays rank 0's JSON as its own last line and propagates the exit code (train_gen.py:295,324-329 -- the reference's
 DataParallel wrapping -- is what the N ranks replace).
 
-Rank 0 prints ONE JSON line (contract in the task statement) with two extra objects:
+Rank 0 prints ONE JSON line (contract in the task statement).  A plain run sets up, warms up, times the K steps and prints
+it: nothing else.  `--full` adds every side measurement (each still switched off by its own --no-* option), among them two
+extra objects of the line:
   roofline      the dominant kernel (bf16 MFMA GEMM family): algorithmic FLOPs per launch / average launch
                 duration measured with HIP events on the launch stream, vs the 2.5 PFLOP/s dense bf16 peak
   cpu_baseline  the CPU oracle (a parity-checked restatement of the reference, oracle/vd_oracle.py) timed on the
                 host cores on a bounded sample of the same workload
+and the per-kernel breakdown, the PCIe-inclusive rate, the fp32 parity-mode step, decode / candidate scoring, the 32 / 64
+rows-per-GPU runs and (N > 1) the extra legs.  Without `--full` those fields are null.
+
+`--dump-outputs DIR` writes what the last timed step computed, as float32 .npy files (same arguments -> same inputs):
+  loss.npy           the step's loss (scalar)
+  logits.npy         the logits the step returned [rows, answer length, vocab]
+  params_sample.npy  the parameters after the step's update: a fixed, seeded sample of up to 2048 elements of every
+                     parameter, in named_parameters() order
 """
 import argparse
 import json
@@ -317,6 +327,31 @@ def demangle(sym):
     return None
 
 
+def dump_outputs(out_dir, loss, logits, model, per_param=2048, max_logits=13_000_000, seed=20240601):
+    """`--dump-outputs`: what the last timed step handed its caller (loss, logits) and what it left behind (the updated
+    parameters), float32 .npy, ~56 MB at the default shape (64 MB at most).  The parameter sample is a fixed draw of up to
+    `per_param` flat indices per parameter (same seed, same named_parameters() order), so it does not depend on the engine's
+    flat layout.  Logits larger than `max_logits` elements (more rows than the default) are kept as a seeded, sorted sample
+    of flat indices, 1-D."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    g = torch.Generator().manual_seed(seed)
+    np.save(os.path.join(out_dir, "loss.npy"), loss.detach().float().cpu().numpy())
+    lg = logits.detach().float().cpu()
+    if lg.numel() > max_logits:
+        lg = lg.reshape(-1)[torch.randperm(lg.numel(), generator=g)[:max_logits].sort().values]
+    np.save(os.path.join(out_dir, "logits.npy"), lg.numpy())
+    parts = []
+    with torch.no_grad():
+        for _, p in model.named_parameters():
+            flat = p.detach().reshape(-1)
+            n = flat.numel()
+            idx = torch.randint(0, n, (per_param,), generator=g) if n > per_param else torch.arange(n)
+            parts.append(flat[idx.to(flat.device)].float().cpu())
+    np.save(os.path.join(out_dir, "params_sample.npy"), torch.cat(parts).numpy())
+
+
 def _flush_c_stdio():
     """RCCL (NCCL_DEBUG=VERSION) prints through C stdio; flush it so that bench.py's JSON is the last stdout line."""
     try:
@@ -359,6 +394,11 @@ def main():
     ap.add_argument("--no-rows-sensitivity", action="store_true",
                     help="skip the 32 / 64 rows-per-GPU side runs (fresh child processes; never `value`) that separate 'the kernels cannot' "
                          "from '16 rows per GPU is too small' for north_star's co-attention target")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement (per-kernel breakdown + roofline, PCIe-inclusive rate, fp32 parity mode, "
+                         "decode / candidate scoring, CPU baseline, rows sensitivity, N>1 legs); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's loss, logits and a seeded sample of the updated parameters to DIR/*.npy")
     ap.add_argument("--leg", default=None, help=argparse.SUPPRESS)          # set by run_leg(): this process IS a leg's rank
     args = ap.parse_args()
     argv = sys.argv[1:]
@@ -368,6 +408,11 @@ def main():
         args.no_breakdown = args.no_breakdown or not keep_breakdown
         args.no_cpu_baseline = args.no_h2d = args.no_fp32 = args.no_eval_decode = args.no_rows_sensitivity = True
         args.legs = "off"
+    if not args.full:                    # a plain run: the headline only (--breakdown-json / --legs on still ask for theirs)
+        args.no_breakdown = args.no_breakdown or not args.breakdown_json
+        args.no_cpu_baseline = args.no_h2d = args.no_fp32 = args.no_eval_decode = args.no_rows_sensitivity = True
+        if args.legs == "auto":
+            args.legs = "off"
 
     # ---- launcher: `--gpus N` with N > 1 and no rank environment -> start the N ranks ourselves (child process, no GPU call here)
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
@@ -476,9 +521,11 @@ def main():
                                                           shard_update=(args.shard_update == "on" and (world > 1 or force_dist)),
                                                           direct_bf16=os.environ.get("GSTVD_BENCH_DIRECT_BF16", "1") != "0")
 
+    last_logits = [None]
+
     def device_step():
         """Everything of a train step that is device work -- the part that is captured into the hipGraph."""
-        loss, _ = model(**batch)
+        loss, last_logits[0] = model(**batch)      # (a view of the engine's arena: a replay rewrites it in place)
         loss.backward()          # includes the pipelined all-reduce + AdamW
         opt.step()               # no-op marker: the update was applied during backward
         opt.zero_grad()
@@ -617,6 +664,8 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     final_loss = float(loss.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, loss, last_logits[0], model)        # before anything else runs a step
     if world > 1:
         import torch.distributed as dist
         tmax = torch.tensor([dt], device=device)
@@ -640,11 +689,13 @@ def main():
                      "one_gpu_validation_mode": bool(one_gpu)}
 
     # host issue time of one step (no sync inside): if this approaches ms_per_step the run is launch bound
-    torch.cuda.synchronize()
-    th = time.perf_counter()
-    eager_step()
-    host_ms = (time.perf_counter() - th) * 1e3
-    torch.cuda.synchronize()
+    host_ms = None
+    if args.full or not args.no_breakdown:
+        torch.cuda.synchronize()
+        th = time.perf_counter()
+        eager_step()
+        host_ms = (time.perf_counter() - th) * 1e3
+        torch.cuda.synchronize()
 
     roofline, breakdown = None, None
     if rank == 0 and not args.no_breakdown:
@@ -867,7 +918,7 @@ def main():
                             "coattn_frac": roofline.get("coattn_frac"), "all_gemm_tflops": roofline.get("all_gemm_tflops")}}
         import subprocess              # (288 GB of HBM: the children fit beside this process's model)
         for rr in (32, 64):
-            cmd = [sys.executable, os.path.abspath(__file__), "--rows-per-gpu", str(rr), "--steps", "5", "--warmup", "2", "--no-cpu-baseline",
+            cmd = [sys.executable, os.path.abspath(__file__), "--rows-per-gpu", str(rr), "--steps", "5", "--warmup", "2", "--full", "--no-cpu-baseline",
                    "--no-eval-decode", "--no-fp32", "--no-h2d", "--no-rows-sensitivity", "--leg", "rows_sens%d" % rr]
             try:
                 r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, timeout=300)
@@ -891,7 +942,7 @@ def main():
                                       % (B, T, "BASELINE configs[1] per-GPU shape" if B == 16 else
                                          "BASELINE configs[2] per-rank shape (global 80 at 8 GPUs)" if B == 10 else "custom rows/GPU"),
                           "global_batch": B * world, "rows_per_gpu": B, "seq_len": T, "parallelism": "dp%d" % world, "leg": args.leg,
-                          "gpu_ms_per_step_events": round(e0.elapsed_time(e1) / args.steps, 3), "eager_host_issue_ms_per_step": round(host_ms, 3), "hip_graph": (use_graph if use_graph == "segmented" else bool(use_graph)), "graphs_per_step": (getattr(replay, "n_graphs", 1) if use_graph else 0), "capture_error": capture_error_msg,
+                          "gpu_ms_per_step_events": round(e0.elapsed_time(e1) / args.steps, 3), "eager_host_issue_ms_per_step": round(host_ms, 3) if host_ms is not None else None, "hip_graph": (use_graph if use_graph == "segmented" else bool(use_graph)), "graphs_per_step": (getattr(replay, "n_graphs", 1) if use_graph else 0), "capture_error": capture_error_msg,
                           "final_loss": round(final_loss, 4)},
                "roofline": roofline, "cpu_baseline": cpu}
         if breakdown is not None:
@@ -917,6 +968,7 @@ def main():
                                            "scaling_vs_n1": "value(N) / value(1) at equal rows_per_gpu; bench.py never reports efficiency itself"}
         from gst_visdial_amd import graph as _g
         out["config"]["capture_quiesce"] = _g.LAST_QUIESCE[0] if use_graph else None
+        out["config"]["full"] = bool(args.full)          # side measurements on (null fields below are off, not failed)
         out["config"]["rows_sensitivity"] = rows_sens
         out["config"]["fp32_parity_mode_ms_per_step"] = fp32_ms
         out["config"]["pcie_inclusive"] = pcie

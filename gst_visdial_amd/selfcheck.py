@@ -9,11 +9,57 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
+PART_BYTES = 960 << 10      # a committed file stays under 1 MiB: a larger fixture is stored as NAME.part0.npz, NAME.part1.npz, ...
+
+
+def npz_files(path):
+    """The file(s) holding fixture `path` (.../NAME.npz): the file itself, or its numbered parts in order."""
+    if os.path.exists(path):
+        return [path]
+    stem, parts = path[:-len(".npz")], []
+    while os.path.exists("%s.part%d.npz" % (stem, len(parts))):
+        parts.append("%s.part%d.npz" % (stem, len(parts)))
+    if not parts:
+        raise FileNotFoundError(path)
+    return parts
+
+
+def read_npz(path):
+    """numpy arrays of fixture `path`, whole or in parts, in the order they were written."""
+    out = {}
+    for f in npz_files(path):
+        with np.load(f) as z:
+            out.update((k, z[k]) for k in z.files)
+    return out
+
+
+def write_npz(path, arrays):
+    """Write fixture `path` (compressed) as one file, or as numbered parts of at most PART_BYTES of raw array data each
+    (keys in order, never split inside an array); whatever form an earlier version of it had is removed first."""
+    for f in npz_files(path) if (os.path.exists(path) or os.path.exists(path[:-len(".npz")] + ".part0.npz")) else []:
+        os.remove(f)
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    if sum(v.nbytes for v in arrays.values()) <= PART_BYTES:
+        np.savez_compressed(path, **arrays)
+        return [path]
+    parts, cur, size = [], {}, 0
+    for k, v in arrays.items():
+        if v.nbytes > PART_BYTES:
+            raise ValueError("fixture array %s: %d bytes, more than one part holds -- store it in pieces" % (k, v.nbytes))
+        if cur and size + v.nbytes > PART_BYTES:
+            parts.append(cur)
+            cur, size = {}, 0
+        cur[k] = v
+        size += v.nbytes
+    parts.append(cur)
+    files = ["%s.part%d.npz" % (path[:-len(".npz")], i) for i in range(len(parts))]
+    for f, p in zip(files, parts):
+        np.savez_compressed(f, **p)
+    return files
 
 
 def load_npz(name):
-    with np.load(os.path.join(GOLDEN, name)) as z:
-        return {k: torch.from_numpy(z[k]) for k in z.files}
+    return {k: torch.from_numpy(v) for k, v in read_npz(os.path.join(GOLDEN, name)).items()}
 
 
 def build_tiny_model(precision="fp32", device="cuda:0", mode="vd_train", seed=0, cfg_file="tiny_cfg.json", state_file="tiny_state.npz",

@@ -36,13 +36,13 @@ sys.path.insert(0, ROOT)
 from oracle import ref_harness as rh            # noqa: E402
 from oracle import ref_adamw                    # noqa: E402
 from oracle.make_golden import make_inputs, call_model, npy   # noqa: E402
+from gst_visdial_amd.selfcheck import read_npz, write_npz      # noqa: E402
 
 OUT = os.path.join(ROOT, "tests", "golden")
 
 
 def load_state():
-    with np.load(os.path.join(OUT, "tiny_state.npz")) as z:
-        return {k: torch.from_numpy(z[k]) for k in z.files}
+    return {k: torch.from_numpy(v) for k, v in read_npz(os.path.join(OUT, "tiny_state.npz")).items()}
 
 
 def eval_batch(seed=21, B=2, NR=3, G=5, T=24, R=7, U=9, V=320, Fdim=40):
@@ -228,7 +228,7 @@ def main_trainer(e_path, d_path):
     out.update({"state3::" + k: v for k, v in states[3].items()})
     out.update({"state5::" + k: v for k, v in states[5].items()})
     out.update(opt3)
-    np.savez(os.path.join(OUT, "tiny_trainer.npz"), **npy(out))
+    write_npz(os.path.join(OUT, "tiny_trainer.npz"), npy(out))      # in parts: a committed file stays under 1 MiB
     meta = dict(param_names=names, shapes=[list(g["params"][0].shape) for g in groups], groups_iter3=groups3,
                 scheduler_iter3={k: v for k, v in sched3.items() if isinstance(v, (int, float, list))},
                 lr=lr, image_lr=image_lr, warmup_steps=warm, t_total=total, language_weights=language,

@@ -33,6 +33,7 @@ ROOT = os.path.dirname(HERE)
 sys.path.insert(0, ROOT)
 from oracle import ref_harness as rh      # noqa: E402
 from oracle import make_golden as mg      # noqa: E402
+from gst_visdial_amd.selfcheck import read_npz  # noqa: E402
 
 OUT = os.path.join(ROOT, "tests", "golden")
 
@@ -89,8 +90,7 @@ def main():
     with open(d_path, "w") as f:
         json.dump(dec_cfg, f)
     model, params = rh.build_reference_model(e_path, d_path, mode="vd_train", seed=0)
-    with np.load(os.path.join(OUT, "tiny_state.npz")) as z:
-        model.load_state_dict({k: torch.from_numpy(z[k]) for k in z.files}, strict=True)
+    model.load_state_dict({k: torch.from_numpy(v) for k, v in read_npz(os.path.join(OUT, "tiny_state.npz")).items()}, strict=True)
     with np.load(os.path.join(OUT, "tiny_train.npz")) as z:
         inp = {k[4:]: torch.from_numpy(z[k]) for k in z.files if k.startswith("in::")}
     model.train()                                         # train_gen.py:300

@@ -2,9 +2,9 @@
 
 TEST INFRASTRUCTURE ONLY.  This file runs only in the build container (the
 reference tree does not exist on the GPU box) and is used by
-`oracle/make_golden.py` to emit the golden vectors under `tests/golden/` and
-by `tests/test_oracle_vs_reference.py` (skipped when /root/reference is
-absent) to pin `oracle/vd_oracle.py` against the reference itself.
+`oracle/make_golden*.py` to emit the golden vectors under `tests/golden/`
+(`make_golden_full.py`'s pin `oracle/vd_oracle.py` against the reference at
+the full configuration: `tests/test_oracle_vs_reference.py`).
 
 Nothing here is copied from the reference: it only *imports* it, after
 installing the shims listed in SURVEY.md Appendix A:

@@ -22,8 +22,8 @@ What it restates (reference = gicheonkang/gst-visdial, paths relative to
 Pinning: every function here is checked (tests/test_oracle_golden.py) against
 golden vectors under tests/golden/ that `oracle/make_golden.py` produced by
 importing and running the reference itself in the build container, and
-(tests/test_oracle_vs_reference.py, container only) against the live reference
-at the full bert-base configuration.
+(tests/test_oracle_vs_reference.py) against the reference's outputs at the full
+bert-base configuration, recorded by `oracle/make_golden_full.py`.
 
 The oracle is written functionally over the reference's own `state_dict()`
 (key names are the checkpoint layout of train_gen.py:346-351) so a reference

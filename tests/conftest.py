@@ -2,7 +2,6 @@ import json
 import os
 import sys
 
-import numpy as np
 import pytest
 import torch
 
@@ -49,8 +48,9 @@ def pytest_pyfunc_call(pyfuncitem):
 
 
 def load_npz(name):
-    with np.load(os.path.join(GOLDEN, name)) as z:
-        return {k: torch.from_numpy(z[k]) for k in z.files}
+    """A fixture of tests/golden/, whole or in numbered parts (gst_visdial_amd.selfcheck.write_npz)."""
+    from gst_visdial_amd.selfcheck import read_npz
+    return {k: torch.from_numpy(v) for k, v in read_npz(os.path.join(GOLDEN, name)).items()}
 
 
 @pytest.fixture(scope="session")

@@ -27,7 +27,7 @@ def _eval_batch(ev, tag=""):
 
 
 # ------------------------------------------------------------------------------------------------ f-1: evaluate_gen
-@pytest.mark.parametrize("tag", ["", "attacked::"])
+@pytest.mark.parametrize("tag", ["", "attacked::"], ids=["", "attacked"])      # (an id holding "::" would not be a valid node id)
 def test_eval_set_scores_ranks_metrics_match_the_reference_run(tag):
     """evaluate_gen.py:45-118 end to end: gst_visdial_amd.evaluate.score_batch -> [B, rounds, options] scores equal the
     reference's expanded run; ranks bit-exact; evaluate() returns the reference's R@k / mean / MRR / NDCG.  The clean set

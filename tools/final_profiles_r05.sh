@@ -4,14 +4,14 @@
 # (The A/B records behind the round's decisions -- group order, attention, ring depths, tile widths, sc1 stores, keep bits -- were
 # written by tools/r05_s1.sh .. r05_s8.sh while the decisions were made; section 9 below repeats the switches that stayed.)
 export TMPDIR=/tmp; out=gpurun_out/final; rm -rf $out; mkdir -p $out
-LEAN="--no-cpu-baseline --no-eval-decode --no-breakdown --no-fp32 --no-h2d"
+LEAN="--full --no-cpu-baseline --no-eval-decode --no-breakdown --no-fp32 --no-h2d"
 # 1. the full GPU test-suite, whole log kept (the driver's command)
 python3 -X faulthandler -m pytest tests/ -x -q -m gpu -p no:cacheprovider --durations=12 > $out/gpu_tests_full.log 2>&1; echo "gpu tests rc=$?" >> $out/gpu_tests_full.log
 tail -3 $out/gpu_tests_full.log
 # 2. the contract line with the driver's flags + per-kernel event breakdown (all side measurements on); wall time of the whole command
 t0=$(date +%s.%N)
-python3 bench.py --steps 20 --warmup 5 --breakdown-json $out/breakdown_events.json > $out/bench_stdout.log 2> $out/bench_stderr.log
-echo "python3 bench.py --steps 20 --warmup 5 (the driver's flags, all side measurements on): $(python3 -c "import time,sys; print(round(time.time()-float(sys.argv[1]),1))" $t0) s wall" > $out/bench_wall.txt
+python3 bench.py --steps 20 --warmup 5 --full --breakdown-json $out/breakdown_events.json > $out/bench_stdout.log 2> $out/bench_stderr.log
+echo "python3 bench.py --steps 20 --warmup 5 --full (all side measurements on): $(python3 -c "import time,sys; print(round(time.time()-float(sys.argv[1]),1))" $t0) s wall" > $out/bench_wall.txt
 tail -1 $out/bench_stdout.log > $out/bench_n1.json; cat $out/bench_wall.txt; cut -c1-260 $out/bench_n1.json
 # 3. rocprofv3 --stats of the same command (kernel averages must agree with roofline.avg_launch_us)
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 bench.py --steps 10 --warmup 3 $LEAN > $out/prof_bench.log 2>&1
@@ -34,7 +34,7 @@ python3 tools/overlap_stats.py $out/kernel_trace_steps.csv.gz > $out/overlap_sta
   GSTVD_BENCH_ONE_GPU=1 python3 bench.py --gpus 2 --steps 3 --warmup 1 $LEAN 2>/dev/null | tail -1; echo "exit code $?" ) > $out/bench_launch_paths.txt 2>&1
 for rows in 16 10; do GSTVD_FORCE_DIST=1 python3 bench.py --steps 10 --warmup 2 --rows-per-gpu $rows --grad-compress bf16 --legs off $LEAN 2>/dev/null | tail -1 > $out/bench_force_dist_rows$rows.json; done
 GSTVD_FORCE_DIST=1 python3 bench.py --steps 10 --warmup 3 --legs on $LEAN 2>/dev/null | tail -1 > $out/bench_force_dist_legs.json
-python3 bench.py --steps 10 --warmup 2 --rows-per-gpu 10 --no-cpu-baseline --no-eval-decode --no-fp32 --no-h2d 2>/dev/null | tail -1 > $out/bench_n1_rows10.json
+python3 bench.py --steps 10 --warmup 2 --rows-per-gpu 10 --full --no-cpu-baseline --no-eval-decode --no-fp32 --no-h2d 2>/dev/null | tail -1 > $out/bench_n1_rows10.json
 tail -4 $out/bench_launch_paths.txt | cut -c1-300; cut -c1-200 $out/bench_force_dist_legs.json
 # 9. whole-step A/B records of the switches that stayed (two interleaved rounds each)
 ( bash tools/r04_step_ab.sh GSTVD_GROUP_ORDER 0 1 3; bash tools/r04_step_ab.sh GSTVD_ATTN_ONEPASS 0 1; bash tools/r04_step_ab.sh GSTVD_GEMM64_NS 8 3

@@ -3,14 +3,14 @@
 # under gpurun_out/final, copied to profiles/ by tools/collect_profiles.py r06).   bash tools/final_profiles_r06.sh
 # (The records behind the round's decisions were written by tools/r06_s1.sh .. r06_s5.sh while the decisions were made.)
 export TMPDIR=/tmp; out=gpurun_out/final; rm -rf $out; mkdir -p $out
-LEAN="--no-cpu-baseline --no-eval-decode --no-breakdown --no-fp32 --no-h2d --no-rows-sensitivity"
+LEAN="--full --no-cpu-baseline --no-eval-decode --no-breakdown --no-fp32 --no-h2d --no-rows-sensitivity"
 # 1. the full GPU test-suite, whole log kept (the driver's command)
 python3 -X faulthandler -m pytest tests/ -x -q -m gpu -p no:cacheprovider --durations=12 > $out/gpu_tests_full.log 2>&1; echo "gpu tests rc=$?" >> $out/gpu_tests_full.log
 tail -3 $out/gpu_tests_full.log
 # 2. the contract line with the driver's flags + per-kernel event breakdown (all side measurements on); wall time of the whole command
 t0=$(date +%s.%N)
-python3 bench.py --steps 20 --warmup 5 --breakdown-json $out/breakdown_events.json > $out/bench_stdout.log 2> $out/bench_stderr.log
-echo "python3 bench.py --steps 20 --warmup 5 (the driver's flags, all side measurements on): $(python3 -c "import time,sys; print(round(time.time()-float(sys.argv[1]),1))" $t0) s wall" > $out/bench_wall.txt
+python3 bench.py --steps 20 --warmup 5 --full --breakdown-json $out/breakdown_events.json > $out/bench_stdout.log 2> $out/bench_stderr.log
+echo "python3 bench.py --steps 20 --warmup 5 --full (all side measurements on): $(python3 -c "import time,sys; print(round(time.time()-float(sys.argv[1]),1))" $t0) s wall" > $out/bench_wall.txt
 tail -1 $out/bench_stdout.log > $out/bench_n1.json; cat $out/bench_wall.txt; cut -c1-260 $out/bench_n1.json
 # 3. rocprofv3 --stats of the same command (kernel averages must agree with roofline.avg_launch_us)
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 bench.py --steps 10 --warmup 3 $LEAN > $out/prof_bench.log 2>&1
@@ -38,7 +38,7 @@ GSTVD_FORCE_DIST=1 bash tools/trace_step.sh --no-eval-decode --no-rows-sensitivi
   python3 bench.py --steps 10 --warmup 3 --graph off $LEAN 2>/dev/null | tail -1 | cut -c1-400 ) > $out/bench_launch_paths.txt 2>&1
 for rows in 16 10; do GSTVD_FORCE_DIST=1 python3 bench.py --steps 10 --warmup 2 --rows-per-gpu $rows --grad-compress bf16 --legs off $LEAN 2>/dev/null | tail -1 > $out/bench_force_dist_rows$rows.json; done
 GSTVD_FORCE_DIST=1 python3 bench.py --steps 10 --warmup 3 --legs on $LEAN 2>/dev/null | tail -1 > $out/bench_force_dist_legs.json
-python3 bench.py --steps 10 --warmup 2 --rows-per-gpu 10 --no-cpu-baseline --no-eval-decode --no-fp32 --no-h2d --no-rows-sensitivity 2>/dev/null | tail -1 > $out/bench_n1_rows10.json
+python3 bench.py --steps 10 --warmup 2 --rows-per-gpu 10 --full --no-cpu-baseline --no-eval-decode --no-fp32 --no-h2d --no-rows-sensitivity 2>/dev/null | tail -1 > $out/bench_n1_rows10.json
 tail -4 $out/bench_launch_paths.txt | cut -c1-300; cut -c1-200 $out/bench_force_dist_legs.json
 # 9. eval / decode side measurements (decode with and without the questioner's 4-gram ban)
 python3 tools/eval_decode_bench.py > $out/eval_decode.json 2> /dev/null; cat $out/eval_decode.json
@@ -47,4 +47,4 @@ python3 tools/eval_decode_bench.py > $out/eval_decode.json 2> /dev/null; cat $ou
     GSTVD_FORCE_DIST=1 python3 bench.py --steps 5 --warmup 2 --grad-compress bf16 --graph $1 --shard-update $2 --legs off $LEAN 2>/dev/null | tail -1 | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('run $i --graph $1 --shard-update $2: rc ok', d['ms_per_step'], 'ms, hip_graph', d['config']['hip_graph'], d['config']['capture_quiesce'], 'payload by wgrad launch', d['config'].get('payload_written_by_wgrad_launch'))" || echo "run $i --graph $1 --shard-update $2: FAILED"
   done; done ) > $out/rccl_soak.txt 2>&1; tail -4 $out/rccl_soak.txt
 # 11. the driver's bench command three more times on this box (repeatability)
-( for i in 1 2 3; do python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-eval-decode --no-fp32 --no-h2d --no-rows-sensitivity 2>/dev/null | tail -1 | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); r=d['roofline']; print('run $i:', d['value'], 'rounds/s', d['ms_per_step'], 'ms; roofline frac', r['frac'], 'avg_launch_us', r['avg_launch_us'], 'rocprof', r.get('avg_launch_us_rocprof'))"; done ) > $out/bench_repeat.txt 2>&1; cat $out/bench_repeat.txt
+( for i in 1 2 3; do python3 bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-eval-decode --no-fp32 --no-h2d --no-rows-sensitivity 2>/dev/null | tail -1 | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); r=d['roofline']; print('run $i:', d['value'], 'rounds/s', d['ms_per_step'], 'ms; roofline frac', r['frac'], 'avg_launch_us', r['avg_launch_us'], 'rocprof', r.get('avg_launch_us_rocprof'))"; done ) > $out/bench_repeat.txt 2>&1; cat $out/bench_repeat.txt

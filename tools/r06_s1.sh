@@ -6,7 +6,7 @@
 #  2. rows sensitivity: the same bench at 32 and 64 rows per GPU (never `value`): does coattn_frac move with the row count?
 #  3. the box's own 16-row reference line for the round's A/Bs.
 export TMPDIR=/tmp; out=gpurun_out/r06_s1; rm -rf $out; mkdir -p $out
-LEAN="--no-cpu-baseline --no-eval-decode --no-fp32 --no-h2d"
+LEAN="--full --no-cpu-baseline --no-eval-decode --no-fp32 --no-h2d"
 rocprofv3 --kernel-trace --output-format csv -d $out/trace -- python3 tools/gemm_bench.py main lib > $out/gemm_bench.txt 2> $out/gemm_bench.err
 python3 tools/vendor_kernel_config.py $(ls $out/trace/*/*kernel_trace.csv | head -1) > $out/vendor_kernel_config.txt 2>&1
 rm -rf $out/trace

@@ -16,8 +16,6 @@ run sysscope0 ROC_SYSTEM_SCOPE_SIGNAL=0
 run skip_release DEBUG_CLR_SKIP_RELEASE_SCOPE=1
 run pktcap0 DEBUG_CLR_GRAPH_PACKET_CAPTURE=0
 run pktcap1 DEBUG_CLR_GRAPH_PACKET_CAPTURE=1
-run graphq1 DEBUG_HIP_FORCE_GRAPH_QUEUES=1
-run graphq2 DEBUG_HIP_FORCE_GRAPH_QUEUES=2
 run cpwait1 GPU_STREAMOPS_CP_WAIT=1
 run cpwait0 GPU_STREAMOPS_CP_WAIT=0
 run dynq0 DEBUG_HIP_DYNAMIC_QUEUES=0

@@ -3,12 +3,12 @@
 # command with the new side records (rows sensitivity, rocprof figure beside the live one, 5-step CPU baseline), scratch sizes of
 # the step's kernels as the hardware reports them, and the vendor kernel of the cross-K/V shape (session 1's filter missed it).
 export TMPDIR=/tmp; out=gpurun_out/r06_s2; rm -rf $out; mkdir -p $out
-LEAN="--no-cpu-baseline --no-eval-decode --no-fp32 --no-h2d --no-rows-sensitivity"
+LEAN="--full --no-cpu-baseline --no-eval-decode --no-fp32 --no-h2d --no-rows-sensitivity"
 python3 -X faulthandler -m pytest tests/ -x -q -m gpu -p no:cacheprovider --durations=8 > $out/gpu_tests_full.log 2>&1; echo "gpu tests rc=$?" >> $out/gpu_tests_full.log
 tail -12 $out/gpu_tests_full.log
 t0=$(date +%s.%N)
-python3 bench.py --steps 20 --warmup 5 > $out/bench_stdout.log 2> $out/bench_stderr.log
-echo "python3 bench.py --steps 20 --warmup 5: $(python3 -c "import time,sys; print(round(time.time()-float(sys.argv[1]),1))" $t0) s wall" | tee $out/bench_wall.txt
+python3 bench.py --steps 20 --warmup 5 --full > $out/bench_stdout.log 2> $out/bench_stderr.log
+echo "python3 bench.py --steps 20 --warmup 5 --full: $(python3 -c "import time,sys; print(round(time.time()-float(sys.argv[1]),1))" $t0) s wall" | tee $out/bench_wall.txt
 tail -1 $out/bench_stdout.log > $out/bench_n1.json; cut -c1-300 $out/bench_n1.json; tail -3 $out/bench_stderr.log
 python3 - <<'PY'
 import json

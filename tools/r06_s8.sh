@@ -2,7 +2,7 @@
 # Round 6, GPU session 4 (re-run as session 8 with the XCD-local hand-off): the Linear with the LayerNorm in its epilogue (gstvd_gemm_ln_epi): op tests, engine A/B, whole-step A/B
 # (GSTVD_FUSE_LN_EPI 0 / 1, two interleaved rounds), stand-alone kernel times, eager issue after the raw-stream accessor.
 export TMPDIR=/tmp; out=gpurun_out/r06_s8; rm -rf $out; mkdir -p $out
-LEAN="--no-cpu-baseline --no-eval-decode --no-fp32 --no-h2d --no-rows-sensitivity"
+LEAN="--full --no-cpu-baseline --no-eval-decode --no-fp32 --no-h2d --no-rows-sensitivity"
 timeout 900 python3 -X faulthandler -m pytest tests/test_round6_gpu.py -x -q -m gpu -p no:cacheprovider > $out/new_tests.log 2>&1; echo "rc=$?" >> $out/new_tests.log
 grep -n "Error\|error\|passed\|failed\|rc=\|assert" $out/new_tests.log | head -30
 timeout 400 bash tools/step_ab.sh GSTVD_FUSE_LN_EPI 0 1 2>&1 | tee $out/ln_epi_step_ab.txt
