@@ -1,14 +1,14 @@
 // MFMA GEMM for gfx950: C[m,n] = epi(alpha * sum_k A(m,k) B(n,k)), every nn.Linear fwd/dgrad/wgrad
-// on the gst-visdial enc_dec_a path (see include/gstvd_hip.h).
+// on the gst-visdial enc_dec_a path (see include/gstvd_hip.h).  gstvd_gemm sends bf16 problems to gemv.hip (M <= 16),
+// gemm_dma256.hip (grids of at least 120 256x256 tiles) or gemm_dma.hip (everything else); this file holds the entry points and
+// the register-staged kernel of the fp32 problems:
 //
-//  * bf16 inputs  -> v_mfma_f32_16x16x32_bf16, fp32 accumulate   (throughput mode)
 //  * fp32 inputs  -> v_mfma_f32_16x16x4_f32, exact fp32 fma chain (parity mode, 1e-4 logits gate)
 //  * operands are staged global -> registers -> LDS in 16-byte vectors, double buffered, one barrier
 //    per K tile; the next tile's global loads are in flight while the current tile is multiplied;
 //  * an operand may be row-major ([x][k], k contiguous) or k-major ([k][x]); the LDS image keeps the
-//    memory layout (straight, coalesced copy) and the MFMA fragment is read either with ds_read_b128
-//    (row-major, XOR-swizzled 16-byte slots) or with ds_read_b64_tr_b16 (k-major, XOR-swizzled 32-byte
-//    blocks) -- no transposing pass anywhere;
+//    memory layout (straight, coalesced copy): row-major rows in XOR-swizzled 16-byte slots, k-major
+//    rows padded by 16 bytes -- no transposing pass anywhere;
 //  * the MFMA is issued "swapped" (n on the accumulator rows) so each lane owns 4 consecutive n of one
 //    output row and the epilogue stores 8/16 bytes per lane.
 #include "gemm_common.h"
@@ -21,6 +21,7 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_kernel(GemmP p) {
   constexpr int STAGE = A_BYTES + B_BYTES;
   constexpr int NVA = BM * BK / VE / NT, NVB = BN * BK / VE / NT;
   static_assert(NVA >= 1 && NVB >= 1, "tile too small for the thread count");
+  static_assert(sizeof(T) == 4, "fp32 operands only: bf16 problems take the LDS-DMA kernels");
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -52,32 +53,17 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_kernel(GemmP p) {
       load_tile<T, BM, AKM, NT, NVA>(ra, gA, p.lda, m0, p.M, (t + 1) * BK, p.K, tid);
       load_tile<T, BN, BKM, NT, NVB>(rb, gB, p.ldb, n0, p.N, (t + 1) * BK, p.K, tid);
     }
-    if constexpr (sizeof(T) == 2) {
 #pragma unroll
-      for (int kk = 0; kk < BK / 32; ++kk) {
-        bf16x8 fa[MI], fb[NI];
+    for (int ks = 0; ks < BK / 4; ++ks) {
+      float fa[MI], fb[NI];
 #pragma unroll
-        for (int i = 0; i < MI; ++i) fa[i] = frag_bf16<BM, AKM>(cA, wm * WTM + i * 16, kk, lane);
+      for (int i = 0; i < MI; ++i) fa[i] = frag_f32<BM, AKM>(cA, wm * WTM + i * 16, ks, lane);
 #pragma unroll
-        for (int j = 0; j < NI; ++j) fb[j] = frag_bf16<BN, BKM>(cB, wn * WTN + j * 16, kk, lane);
+      for (int j = 0; j < NI; ++j) fb[j] = frag_f32<BN, BKM>(cB, wn * WTN + j * 16, ks, lane);
 #pragma unroll
-        for (int i = 0; i < MI; ++i)
+      for (int i = 0; i < MI; ++i)
 #pragma unroll
-          for (int j = 0; j < NI; ++j) acc[i][j] = mfma_bf16_k32(fb[j], fa[i], acc[i][j]);
-      }
-    } else {
-#pragma unroll
-      for (int ks = 0; ks < BK / 4; ++ks) {
-        float fa[MI], fb[NI];
-#pragma unroll
-        for (int i = 0; i < MI; ++i) fa[i] = frag_f32<BM, AKM>(cA, wm * WTM + i * 16, ks, lane);
-#pragma unroll
-        for (int j = 0; j < NI; ++j) fb[j] = frag_f32<BN, BKM>(cB, wn * WTN + j * 16, ks, lane);
-#pragma unroll
-        for (int i = 0; i < MI; ++i)
-#pragma unroll
-          for (int j = 0; j < NI; ++j) acc[i][j] = mfma_f32_k4(fb[j], fa[i], acc[i][j]);
-      }
+        for (int j = 0; j < NI; ++j) acc[i][j] = mfma_f32_k4(fb[j], fa[i], acc[i][j]);
     }
     if (more) {
       char* nA = smem + ((t + 1) & 1) * STAGE;
@@ -97,11 +83,11 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_kernel(GemmP p) {
       gemm_epilogue_tile<T, OT>(p, dk, acc[i][j], z, m0 + wm * WTM + i * 16 + li, n0 + wn * WTN + j * 16 + 4 * g);
 }
 
-template <typename T, typename OT, int BM, int BN, bool AKM, bool BKM>
+template <int BM, int BN, bool AKM, bool BKM>
 static int launch_cfg(const GemmP& p, int64_t batch, hipStream_t s) {
   constexpr int WM = 2, WN = 2;
-  constexpr int lds = 2 * (image_bytes<T, BM, AKM>() + image_bytes<T, BN, BKM>());
-  auto k = gemm_kernel<T, OT, BM, BN, WM, WN, AKM, BKM>;
+  constexpr int lds = 2 * (image_bytes<float, BM, AKM>() + image_bytes<float, BN, BKM>());
+  auto k = gemm_kernel<float, float, BM, BN, WM, WN, AKM, BKM>;
   static int attr_rc = ensure_lds(k, lds);
   if (attr_rc) return attr_rc;
   dim3 grid((unsigned)((p.N + BN - 1) / BN), (unsigned)((p.M + BM - 1) / BM), (unsigned)batch);
@@ -110,23 +96,31 @@ static int launch_cfg(const GemmP& p, int64_t batch, hipStream_t s) {
   return 0;
 }
 
-template <typename T, typename OT, bool AKM, bool BKM>
+template <bool AKM, bool BKM>
 static int launch_layout(const GemmP& p, int64_t batch, hipStream_t s) {
   // big tile when it still fills the chip, else the small one (M=592/400 streams, tiny test shapes)
   int64_t big = ((p.M + 127) / 128) * ((p.N + 127) / 128) * batch;
-  if (p.M >= 256 && p.N >= 128 && big >= 96) return launch_cfg<T, OT, 128, 128, AKM, BKM>(p, batch, s);
-  return launch_cfg<T, OT, 64, 64, AKM, BKM>(p, batch, s);
+  if (p.M >= 256 && p.N >= 128 && big >= 96) return launch_cfg<128, 128, AKM, BKM>(p, batch, s);
+  return launch_cfg<64, 64, AKM, BKM>(p, batch, s);
 }
 
-template <typename T, typename OT>
-static int launch_dtype(const GemmP& p, int64_t batch, int akm, int bkm, hipStream_t s) {
-  if (!akm && !bkm) return launch_layout<T, OT, false, false>(p, batch, s);
-  if (!akm && bkm) return launch_layout<T, OT, false, true>(p, batch, s);
-  if (akm && bkm) return launch_layout<T, OT, true, true>(p, batch, s);
-  return launch_layout<T, OT, true, false>(p, batch, s);
+static int launch_f32(const GemmP& p, int64_t batch, int akm, int bkm, hipStream_t s) {
+  if (!akm && !bkm) return launch_layout<false, false>(p, batch, s);
+  if (!akm && bkm) return launch_layout<false, true>(p, batch, s);
+  if (akm && bkm) return launch_layout<true, true>(p, batch, s);
+  return launch_layout<true, false>(p, batch, s);
 }
 
 thread_local const void** gstvd_plan_capture = nullptr;
+
+int copy_kernel_name(const void* fn, char* buf, int32_t buf_len) {
+  const char* name = fn ? hipKernelNameRefByPtr(fn, nullptr) : nullptr;
+  if (!name) return GSTVD_E_UNSUPPORTED;
+  int i = 0;
+  for (; name[i] && i < buf_len - 1; ++i) buf[i] = name[i];
+  buf[i] = 0;
+  return 0;
+}
 
 static int gemm_params(const gstvd_gemm_t* g, GemmP& p) {
   if (!g || !g->A || !g->B || !g->C) return GSTVD_E_NULL;
@@ -186,13 +180,7 @@ extern "C" int gstvd_gemm_kernel_name(const gstvd_gemm_t* g, int32_t splits, cha
   const int rc = splits >= 2 ? gstvd_gemm_splitk(g, splits, dummy_ws, (int64_t)1 << 40, nullptr) : gstvd_gemm(g, nullptr);
   gstvd_plan_capture = nullptr;
   if (rc) return rc;
-  if (!fn) return GSTVD_E_UNSUPPORTED;
-  const char* name = hipKernelNameRefByPtr(fn, nullptr);
-  if (!name) return GSTVD_E_UNSUPPORTED;
-  int i = 0;
-  for (; name[i] && i < buf_len - 1; ++i) buf[i] = name[i];
-  buf[i] = 0;
-  return 0;
+  return copy_kernel_name(fn, buf, buf_len);
 }
 
 extern "C" int gstvd_gemm(const gstvd_gemm_t* g, gstvd_stream_t stream) {
@@ -201,15 +189,13 @@ extern "C" int gstvd_gemm(const gstvd_gemm_t* g, gstvd_stream_t stream) {
   if (prc) return prc;
   hipStream_t s = (hipStream_t)stream;
   if (g->dtype_in == GSTVD_BF16 && (g->dtype_out == GSTVD_BF16 || g->dtype_out == GSTVD_F32)) {
-    int rc = gemv16_dispatch(p, g->batch, g->a_kmajor, g->b_kmajor, g->dtype_out == GSTVD_F32, s);     // decode step: M <= 16
+    const int out_f32 = g->dtype_out == GSTVD_F32;
+    int rc = gemv16_dispatch(p, g->batch, g->a_kmajor, g->b_kmajor, out_f32, s);     // decode step: M <= 16
     if (rc != GSTVD_E_UNSUPPORTED) return rc;
-    rc = gemm_dma256_dispatch(p, g->batch, g->a_kmajor, g->b_kmajor, g->dtype_out == GSTVD_F32, s);
+    rc = gemm_dma256_dispatch(p, g->batch, g->a_kmajor, g->b_kmajor, out_f32, s);
     if (rc != GSTVD_E_UNSUPPORTED) return rc;
-    rc = gemm_dma_dispatch(p, g->batch, g->a_kmajor, g->b_kmajor, g->dtype_out == GSTVD_F32, s);
-    if (rc != GSTVD_E_UNSUPPORTED) return rc;
+    return gemm_dma_dispatch(p, g->batch, g->a_kmajor, g->b_kmajor, out_f32, s);
   }
-  if (g->dtype_in == GSTVD_BF16 && g->dtype_out == GSTVD_BF16) return launch_dtype<bf16, bf16>(p, g->batch, g->a_kmajor, g->b_kmajor, s);
-  if (g->dtype_in == GSTVD_BF16 && g->dtype_out == GSTVD_F32) return launch_dtype<bf16, float>(p, g->batch, g->a_kmajor, g->b_kmajor, s);
-  if (g->dtype_in == GSTVD_F32 && g->dtype_out == GSTVD_F32) return launch_dtype<float, float>(p, g->batch, g->a_kmajor, g->b_kmajor, s);
+  if (g->dtype_in == GSTVD_F32 && g->dtype_out == GSTVD_F32) return launch_f32(p, g->batch, g->a_kmajor, g->b_kmajor, s);
   return GSTVD_E_DTYPE;
 }

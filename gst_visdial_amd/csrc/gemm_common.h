@@ -1,4 +1,4 @@
-// Shared pieces of the two GEMM main loops (gemm.hip: register-staged, any dtype; gemm_dma.hip: LDS-DMA ring, bf16).
+// Shared pieces of the GEMM kernels (gemm.hip: register-staged, fp32; gemm_dma.hip, gemm_dma256.hip, gemm_rows.hip, gemv.hip: bf16).
 #pragma once
 #include "common.h"
 
@@ -244,6 +244,9 @@ DEVFN void gemm_epilogue_rows(const GemmP& p, const DropKey& dk, const f32x4 (&a
 // site records the host-side kernel handle it WOULD have launched instead of launching it.  bench.py reports the launched
 // symbol from this -- the dispatch itself is the single source of truth, not a host-side re-derivation of its rule.
 extern thread_local const void** gstvd_plan_capture;
+// Copies the (mangled) symbol of the host-side kernel handle `fn` into buf (truncated to buf_len - 1 characters); GSTVD_E_UNSUPPORTED
+// when there is none.
+int copy_kernel_name(const void* fn, char* buf, int32_t buf_len);
 #define GSTVD_LAUNCH(kern, grid, block, lds, stream, ...)                                              \
   do {                                                                                                 \
     auto k_ = (kern);                                                                                  \

@@ -11,7 +11,6 @@
 //                        ds_read_b128 for the 16x16x32 fragment pattern; found by exhaustive search over the b128 lane groups)
 //   k-major operand    : 32 k-rows x 512 B; 32-byte block b of k-row r lives at block b ^ ((r&3) | ((r>>3)&1)<<2)
 #include "gemm_common.h"
-#include <stdlib.h>
 
 static __device__ __attribute__((aligned(256))) char g_zero_page256[256];
 static constexpr int g_strip_w = 8;      // column-strip width of the tile order (measured 2 / 4 / 8: 31.3 / 30.7 / 30.5 us at 4096x3072x768)
@@ -21,19 +20,6 @@ static constexpr int g_strip_w = 8;      // column-strip width of the tile order
 // ~0.8 us off the fill in front of the first MFMA: 29.0 -> 27.8 us at 4096x3072x768, step +0.8 % (1190 vs 1181 rounds/s, three
 // A/B pairs).  The LDS allocation is the larger of the ring and the epilogue's parking space.
 constexpr int NS256 = 3;
-// Timing ablations and in-kernel clock stamps exist only in the DIAGNOSTIC build of this file (-DGSTVD_DIAG ->
-// lib/libgstvd_hip_diag.so, `make diag`; loaded by tools/ only, never by gst_visdial_amd/_lib.py): several of them compute
-// wrong results on purpose, and no environment variable may be able to make the product library do that.
-#ifdef GSTVD_DIAG
-constexpr bool kDiag = true;
-// shader-clock and 100 MHz wall-clock stamps around the K loop of the first 512 workgroups (ST = 3), written to a buffer of their
-// own -- in-kernel clock = d(s_memtime) / d(s_memrealtime) x 100 MHz (MI355X_MICROARCH.md, DVFS item 6);
-// gstvd_debug_gemm_clock() copies them out
-static __device__ unsigned long long g_clk256[512 * 4];
-#else
-constexpr bool kDiag = false;
-#endif
-
 
 DEVFN int opaque_lane(int lane) { asm volatile("" : "+v"(lane)); return lane; }
 DEVFN int rm32_off(int row, int slot) { return row * 64 + ((slot ^ (((row >> 3) & 1) << 1)) << 4); }
@@ -98,12 +84,10 @@ struct Dma32 {
 
 // NIU = 16-column accumulator tiles per wave actually used (4: the full 256-wide tile; 3: a 192-wide tile inside the same
 // 256-wide LDS image -- N = 3072 then gives 16 x 16 = 256 tiles, one per CU, instead of 192 tiles on 256 CUs).
-// ST = K-step schedule: 0 the compiler's own order (DMA issue, then fragment reads two A fragments at a time in front of the
-// MFMAs that use them); 4 all twelve fragment reads first, then the DMA issue under their latency (diagnostic build, GSTVD_DIAG_ST=4; correct
-// results, measured -4 % per step in isolation, nothing inside the step).  Staggered-issue schedules (round 2's ST = 1 / 2 / 5)
-// measured no gain and are gone (profiles/r02_gemm_kloop_study.txt).
-// PF < 0 (except -5, the ping-pong tile) and ST = 3 are timing-only ablations of the diagnostic build (kDiag).
-template <typename OT, bool AKM, bool BKM, int PF, int NIU = 4, int ST = 0>
+// K-step schedule: the DMA issue, then fragment reads two A fragments at a time in front of the MFMAs that use them (the
+// compiler's own order).  The schedule variants and timing ablations rounds 2-4 measured against it are in DESIGN_HISTORY.md
+// and profiles/.
+template <typename OT, bool AKM, bool BKM, int NIU = 4>
 DEVFN void dma_tile256(const GemmP& p, int64_t z, int wg, int ntn, int nwg, char* smem) {
   constexpr int BM = 256, BN = 256, WM = 2, WN = 4, NS = NS256, NT = 512;
   constexpr int WTM = BM / WM, WTN = NIU * 16, MI = WTM / 16, NI = NIU, BNU = WN * WTN;   // 8 x NIU accumulator tiles per wave
@@ -139,96 +123,30 @@ DEVFN void dma_tile256(const GemmP& p, int64_t z, int wg, int ntn, int nwg, char
     ub.issue(s, p.K, smem + s * STAGE + A_BYTES, wave);
   }
   int slot = 0, fill = NS - 1;
-  static_assert(kDiag || (PF == 0 && ST == 0), "schedule variants and timing ablations belong to the -DGSTVD_DIAG build");
-#ifdef GSTVD_DIAG
-  unsigned long long clk0 = 0, rt0 = 0;
-  if (ST == 3) { clk0 = __builtin_amdgcn_s_memtime(); rt0 = __builtin_amdgcn_s_memrealtime(); }
-#endif
   for (int64_t t = 0; t < nkt; ++t) {
-    if (PF != -7) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NS - 2) * LPS) : "memory");
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NS - 2) * LPS) : "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-    // diagnostic build only -- PF = -1 / -2 / -6 / -7 / -8 are timing-only ablations (wrong results): -1 = zero-page DMAs
-    // inside the loop, -7 = no DMA instruction at all, -2 = no LDS reads / MFMA, -8 = MFMAs on stale registers, -6 = no epilogue
-    if (ST == 4 && PF != -2) {
-      // fragment reads first, all twelve of them (48 VGPRs): the compiler's own schedule reads two A fragments at a time right
-      // before the eight MFMAs that use them, which leaves the matrix pipe waiting on LDS latency eight times per step
-      // (in-kernel stamps: 1617 cycles per step for 1024 cycles of MFMA work with the DMA switched off).  Then the DMA issue,
-      // under the reads' latency; then 32 MFMAs behind counted lgkmcnt waits.
-      const char* cA = smem + slot * STAGE;
-      const char* cB = cA + A_BYTES;
-      bf16x8 fb[NI], fa[MI];
-#pragma unroll
-      for (int j = 0; j < NI; ++j) fb[j] = frag32<BN, BKM>(cB, wn * WTN + j * 16, lane);
-#pragma unroll
-      for (int i = 0; i < MI; ++i) fa[i] = frag32<BM, AKM>(cA, wm * WTM + i * 16, lane);
-      __builtin_amdgcn_sched_barrier(0);
-      if (PF == -1) {
-        ua.issue(1 << 20, p.K, smem + fill * STAGE, wave);
-        ub.issue(1 << 20, p.K, smem + fill * STAGE + A_BYTES, wave);
-      } else {
-        ua.issue(t + NS - 1, p.K, smem + fill * STAGE, wave);
-        ub.issue(t + NS - 1, p.K, smem + fill * STAGE + A_BYTES, wave);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < NI; ++j) acc[i][j] = mfma_bf16_k32(fb[j], fa[i], acc[i][j]);
-      slot = (slot + 1 == NS) ? 0 : slot + 1;
-      fill = (fill + 1 == NS) ? 0 : fill + 1;
-      continue;
-    }
-    if (PF == -7) {
-    } else if (PF == -1) {
-      ua.issue(1 << 20, p.K, smem + fill * STAGE, wave);      // zero-page DMAs keep the vmcnt bookkeeping identical
-      ub.issue(1 << 20, p.K, smem + fill * STAGE + A_BYTES, wave);
-    } else {
-      ua.issue(t + NS - 1, p.K, smem + fill * STAGE, wave);
-      ub.issue(t + NS - 1, p.K, smem + fill * STAGE + A_BYTES, wave);
-    }
+    ua.issue(t + NS - 1, p.K, smem + fill * STAGE, wave);
+    ub.issue(t + NS - 1, p.K, smem + fill * STAGE + A_BYTES, wave);
     const char* cA = smem + slot * STAGE;
     const char* cB = cA + A_BYTES;
-    if (PF == -8) {       // timing-only: real DMA, 32 MFMAs per wave on registers that are never reloaded (no LDS fragment reads)
-      bf16x8 fx = __builtin_bit_cast(bf16x8, (u32x4){(unsigned)lane, 1u, 2u, (unsigned)t});
+    bf16x8 fb[NI];
 #pragma unroll
-      for (int i = 0; i < MI; ++i)
+    for (int j = 0; j < NI; ++j) fb[j] = frag32<BN, BKM>(cB, wn * WTN + j * 16, lane);
 #pragma unroll
-        for (int j = 0; j < NI; ++j) acc[i][j] = mfma_bf16_k32(fx, fx, acc[i][j]);
-    } else if (PF != -2) {
-      bf16x8 fb[NI];
+    for (int i = 0; i < MI; ++i) {
+      const bf16x8 fa = frag32<BM, AKM>(cA, wm * WTM + i * 16, lane);
 #pragma unroll
-      for (int j = 0; j < NI; ++j) fb[j] = frag32<BN, BKM>(cB, wn * WTN + j * 16, lane);
-#pragma unroll
-      for (int i = 0; i < MI; ++i) {
-        const bf16x8 fa = frag32<BM, AKM>(cA, wm * WTM + i * 16, lane);
-#pragma unroll
-        for (int j = 0; j < NI; ++j) acc[i][j] = mfma_bf16_k32(fb[j], fa, acc[i][j]);
-      }
+      for (int j = 0; j < NI; ++j) acc[i][j] = mfma_bf16_k32(fb[j], fa, acc[i][j]);
     }
     slot = (slot + 1 == NS) ? 0 : slot + 1;
     fill = (fill + 1 == NS) ? 0 : fill + 1;
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifdef GSTVD_DIAG
-  if (ST == 3 && tid == 0 && wg < 512) {
-    g_clk256[wg * 4 + 0] = __builtin_amdgcn_s_memtime() - clk0;
-    g_clk256[wg * 4 + 1] = __builtin_amdgcn_s_memrealtime() - rt0;
-    g_clk256[wg * 4 + 2] = (unsigned long long)nkt;
-  }
-#endif
 
   const int g = lane >> 4, li = lane & 15;
   const DropKey dk = make_drop((p.epi & GSTVD_EPI_DROPOUT) ? p.p : 0.f, p.site, p.rng);
-  if (PF == -6) {      // timing-only ablation: no epilogue (one dependent store keeps the accumulators alive)
-    f32x4 t = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-      for (int j = 0; j < NI; ++j) t += acc[i][j];
-    if (t[0] + t[1] + t[2] + t[3] == 12345.678f) ((float*)p.C)[0] = t[0];
-    return;
-  }
   if constexpr (sizeof(OT) == 2) {
     if (epilogue_rows_ok(p)) {
       __builtin_amdgcn_s_barrier();            // every wave is done reading the ring: its LDS is free for the row-wise epilogue
@@ -238,115 +156,6 @@ DEVFN void dma_tile256(const GemmP& p, int64_t z, int wg, int ntn, int nwg, char
   }
 #pragma unroll
   for (int i = 0; i < MI; ++i)
-#pragma unroll
-    for (int j = 0; j < NI; ++j)
-      gemm_epilogue_tile<bf16, OT>(p, dk, acc[i][j], z, m0 + wm * WTM + i * 16 + li, n0 + wn * WTN + j * 16 + 4 * g);
-}
-
-// Ping-pong schedule of the same tile: the two wave groups (wm = 0 / 1, one wave of each per SIMD) run one slot apart, so
-// in every slot one group issues 16 MFMAs from registers while the other reads its next fragments from LDS and issues its
-// share of the LDS-DMA.  Per 32-deep stage and group: L0 (A pieces, 4 B + 4 A fragments) | M0 (rows 0-3) | L1 (B pieces,
-// 4 A fragments, counted vmcnt for stage t+1) | M1 (rows 4-7); every slot ends in a workgroup barrier.
-// Ordering: a stage is read from the slot after the barrier that follows every wave's vmcnt wait for it; a ring slot is
-// refilled only after the barrier that follows the lgkmcnt(0) retiring its last fragment read.
-template <typename OT, bool AKM, bool BKM>
-DEVFN void pp_tile256(const GemmP& p, int64_t z, int wg, int ntn, int nwg, char* smem) {
-  constexpr int BM = 256, BN = 256, WN = 4, NS = NS256, NT = 512;
-  constexpr int WTM = 128, WTN = 64, NI = 4, HI = 4;
-  constexpr int A_BYTES = BM * 64, B_BYTES = BN * 64, STAGE = A_BYTES + B_BYTES;
-  constexpr int NPA = A_BYTES / (NT * 16), NPB = B_BYTES / (NT * 16), LPS = NPA + NPB;
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave / WN, wn = wave % WN;
-  const int ntm = nwg / ntn;
-  const int strip = wg / (2 * ntm), sw = (ntn - strip * 2) < 2 ? (ntn - strip * 2) : 2;
-  const int within = wg - strip * 2 * ntm;
-  const int64_t m0 = (int64_t)(within / sw) * BM, n0 = (int64_t)(strip * 2 + within % sw) * BN;
-
-  Dma32<BM, AKM, NPA, NT> ua;
-  Dma32<BN, BKM, NPB, NT> ub;
-  ua.init(p.A + z * p.sA * 2, p.lda, m0, p.M, tid);
-  ub.init(p.B + z * p.sB * 2, p.ldb, n0, p.N, tid);
-
-  f32x4 acc[2 * HI][NI];
-#pragma unroll
-  for (int i = 0; i < 2 * HI; ++i)
-#pragma unroll
-    for (int j = 0; j < NI; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-  const int64_t nkt = (p.K + 31) / 32;
-#pragma unroll
-  for (int s = 0; s < NS - 1; ++s) {
-    ua.issue(s, p.K, smem + s * STAGE, wave);
-    ub.issue(s, p.K, smem + s * STAGE + A_BYTES, wave);
-  }
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NS - 2) * LPS) : "memory");
-  __builtin_amdgcn_s_barrier();
-  if (wm == 1) __builtin_amdgcn_s_barrier();            // group 1 runs one slot behind group 0
-  __builtin_amdgcn_sched_barrier(0);
-
-  int slot = 0, fill = NS - 1;
-  for (int64_t t = 0; t < nkt; ++t) {
-    const char* cA = smem + slot * STAGE;
-    const char* cB = cA + A_BYTES;
-    bf16x8 fb[NI], fa0[HI], fa1[HI];
-    // ---- L0
-    ua.issue(t + NS - 1, p.K, smem + fill * STAGE, wave);
-#pragma unroll
-    for (int j = 0; j < NI; ++j) fb[j] = frag32<BN, BKM>(cB, wn * WTN + j * 16, lane);
-#pragma unroll
-    for (int i = 0; i < HI; ++i) fa0[i] = frag32<BM, AKM>(cA, wm * WTM + i * 16, lane);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    // ---- M0
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int i = 0; i < HI; ++i)
-#pragma unroll
-      for (int j = 0; j < NI; ++j) acc[i][j] = mfma_bf16_k32(fb[j], fa0[i], acc[i][j]);
-    __builtin_amdgcn_s_setprio(0);
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    // ---- L1
-    ub.issue(t + NS - 1, p.K, smem + fill * STAGE + A_BYTES, wave);
-#pragma unroll
-    for (int i = 0; i < HI; ++i) fa1[i] = frag32<BM, AKM>(cA, wm * WTM + (HI + i) * 16, lane);
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NS - 2) * LPS) : "memory");     // own pieces of stage t+1 have landed
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    // ---- M1
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int i = 0; i < HI; ++i)
-#pragma unroll
-      for (int j = 0; j < NI; ++j) acc[HI + i][j] = mfma_bf16_k32(fb[j], fa1[i], acc[HI + i][j]);
-    __builtin_amdgcn_s_setprio(0);
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    slot = (slot + 1 == NS) ? 0 : slot + 1;
-    fill = (fill + 1 == NS) ? 0 : fill + 1;
-  }
-  if (wm == 0) __builtin_amdgcn_s_barrier();            // pairs with group 1's extra barrier
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-
-  const int g = lane >> 4, li = lane & 15;
-  const DropKey dk = make_drop((p.epi & GSTVD_EPI_DROPOUT) ? p.p : 0.f, p.site, p.rng);
-  if constexpr (sizeof(OT) == 2) {
-    if (epilogue_rows_ok(p)) {
-      __builtin_amdgcn_s_barrier();
-      gemm_epilogue_rows<2 * HI, NI, 4>(p, dk, acc, z, m0 + wm * WTM, n0 + wn * WTN, smem + wave * epi_wave_bytes<NI, 4>(), lane);
-      return;
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 2 * HI; ++i)
 #pragma unroll
     for (int j = 0; j < NI; ++j)
       gemm_epilogue_tile<bf16, OT>(p, dk, acc[i][j], z, m0 + wm * WTM + i * 16 + li, n0 + wn * WTN + j * 16 + 4 * g);
@@ -408,7 +217,7 @@ DEVFN void adamw_rows_pass(const gstvd_adamw_fuse_t& af, float alpha, float lr, 
   }
 }
 
-// Producer / consumer form of the same tile (the default; GSTVD_GEMM_PC=0 switches it off): 12 waves.  Waves 0-7 are the MFMA consumers of dma_tile256 (128x64 each)
+// Producer / consumer form of the same tile (grids of up to two rounds of tiles, and every grouped launch): 12 waves.  Waves 0-7 are the MFMA consumers of dma_tile256 (128x64 each)
 // and never touch the memory pipeline; waves 8-11 are LDS-DMA producers (8 pieces of 1 KB per wave and stage) and never touch
 // the matrix pipe.  One s_barrier per K-step still orders everything: before barrier t every producer has waited for its pieces
 // of stage t (counted vmcnt) and every consumer has retired its fragment reads of slot t-1, so after it the consumers read slot t
@@ -762,11 +571,10 @@ DEVFN int xcd_remap256(int bid, int nwg) {
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
 }
 
-template <typename OT, bool AKM, bool BKM, int PF, int NIU = 4, int ST = 0>
+template <typename OT, bool AKM, bool BKM, int NIU = 4>
 __global__ __launch_bounds__(512) void gemm_dma256_kernel(GemmP p, int ntn, int nwg) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  if (PF == -5) pp_tile256<OT, AKM, BKM>(p, blockIdx.y, xcd_remap256(blockIdx.x, nwg), ntn, nwg, smem);
-  else dma_tile256<OT, AKM, BKM, PF, NIU, ST>(p, blockIdx.y, xcd_remap256(blockIdx.x, nwg), ntn, nwg, smem);
+  dma_tile256<OT, AKM, BKM, NIU>(p, blockIdx.y, xcd_remap256(blockIdx.x, nwg), ntn, nwg, smem);
 }
 
 template <typename OT, bool AKM, bool BKM, int NIU = 4>
@@ -791,6 +599,8 @@ __global__ __launch_bounds__(768) void gemm_pc256_nt64_kernel(GemmP p, int ntn, 
 // A map entry's tile id is its bits 0-20; the bits above are ignored (reserved).  (Round 5 tried a START BARRIER in them -- position of
 // the tile in its unit and the unit's size, the workgroups of a unit waiting for each other before their K loops: 7.5 % fewer operand
 // fetches, 2.3 % slower, and the call cost the fused kernel 256 B/lane of scratch; removed, profiles/r05_group_sync_ab.txt.)
+// A tile id >= total names no tile of the table: the host checks the map it builds, the kernels skip such an entry so that a bad
+// map cannot write.
 constexpr int GROUP_TILE_MASK = 0x1fffff;
 DEVFN int grouped_tile_id(const int* bmap, int total, int chs) {
   const int bid = blockIdx.x;
@@ -799,14 +609,9 @@ DEVFN int grouped_tile_id(const int* bmap, int total, int chs) {
   return bid < full ? (((bid >> 3) >> chs) * 8 + (bid & 7)) * (1 << chs) + ((bid >> 3) & ((1 << chs) - 1)) : bid;
 }
 
-template <typename OT, bool AKM, bool BKM, int PF, int ST = 0>
-__global__ __launch_bounds__(512) void gemm_dma256_grouped_kernel(const gstvd_gemm_t* tab, const int* tile_off, int nprob, int total, int chs,
-                                                                  const int* bmap) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int entry = grouped_tile_id(bmap, total, chs);
-  if (entry < 0) return;
-  const int gid = entry & GROUP_TILE_MASK;
-  if (gid >= total) return;                  // a map entry that names no tile of the table (the host checks the map it builds; this keeps a bad one from writing)
+// The grouped kernels' prologue, once the workgroup's tile id `gid` is known to name a tile of the table: the problem's GemmP, the
+// tile's index inside the problem and the problem's tile grid (ntn columns, nwg tiles).
+DEVFN GemmP grouped_problem(const gstvd_gemm_t* tab, const int* tile_off, int nprob, int gid, int& tile, int& ntn, int& nwg) {
   int lo = 0, hi = nprob - 1;
   while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (tile_off[mid] <= gid) lo = mid; else hi = mid - 1; }
   const gstvd_gemm_t& g = tab[lo];
@@ -817,87 +622,80 @@ __global__ __launch_bounds__(512) void gemm_dma256_grouped_kernel(const gstvd_ge
   p.lda = g.lda; p.ldb = g.ldb; p.ldc = g.ldc; p.ldadd = g.ldadd; p.ldaux = g.ldaux;
   p.sA = p.sB = p.sC = p.sAdd = p.sAux = 0;
   p.epi = g.epilogue; p.alpha = g.alpha; p.p = g.dropout_p; p.site = g.site; p.rng = g.rng;
-  const int ntn = (int)((g.N + 255) / 256), ntm = (int)((g.M + 255) / 256);
-  dma_tile256<OT, AKM, BKM, PF, 4, ST>(p, 0, gid - tile_off[lo], ntn, ntm * ntn, smem);
+  ntn = (int)((g.N + 255) / 256);
+  nwg = (int)((g.M + 255) / 256) * ntn;
+  tile = gid - tile_off[lo];
+  return p;
+}
+
+template <typename OT, bool AKM, bool BKM>
+__global__ __launch_bounds__(768) void gemm_pc256_grouped_kernel(const gstvd_gemm_t* tab, const int* tile_off, int nprob, int total, int chs,
+                                                                 const int* bmap) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int entry = grouped_tile_id(bmap, total, chs);
+  if (entry < 0 || (entry & GROUP_TILE_MASK) >= total) return;
+  int tile, ntn, nwg;
+  const GemmP p = grouped_problem(tab, tile_off, nprob, entry & GROUP_TILE_MASK, tile, ntn, nwg);
+  pc_tile256<OT, AKM, BKM, 4, true>(p, 0, tile, ntn, nwg, smem);
+}
+
+__global__ __launch_bounds__(768) void gemm_pc256_grouped_adamw_kernel(const gstvd_gemm_t* tab, const int* tile_off, int nprob, int total, int chs,
+                                                                       const int* bmap, gstvd_adamw_fuse_t af) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int entry = grouped_tile_id(bmap, total, chs);
+  if (entry < 0 || (entry & GROUP_TILE_MASK) >= total) return;
+  int tile, ntn, nwg;
+  const GemmP p = grouped_problem(tab, tile_off, nprob, entry & GROUP_TILE_MASK, tile, ntn, nwg);
+  pc_tile256<float, true, true, 4, true, true>(p, 0, tile, ntn, nwg, smem, af);
 }
 
 constexpr int RING256 = NS256 * (256 + 256) * 64;
 constexpr int PARK256 = 8 * epi_wave_bytes<4, 4>();        // eight waves park 4 x 4 accumulator tiles each (row-wise epilogue)
 constexpr int LDS256 = RING256 > PARK256 ? RING256 : PARK256;
+// Producer / consumer form up to this many tiles per launch: measured -7 % per launch on single-round grids (4096x3072x768 33.8
+// -> 31.3 us, per K-step 0.82 -> 0.76 us), +7 % on the 1368-tile cross-K/V projection (its extra ~1.5 us of fixed cost is paid
+// 5.3 times): up to 2 rounds of tiles.  Larger grids take the 8-wave dma_tile256.
+constexpr int64_t PC256_MAX_TILES = 512;
+// Single-problem policy: the big tile only pays when its (4x smaller) grid still covers most of the chip.
+constexpr int64_t GEMM256_MIN_TILES = 120;
+// Tiles per XCD chunk of a grouped launch without a block map = 2^GROUP_CHUNK_LOG2 (8: measured best of 1..128 inside the step).
+constexpr int GROUP_CHUNK_LOG2 = 3;
 
 template <typename OT, bool AKM, bool BKM>
 static int launch256(const GemmP& p, int64_t batch, int niu, hipStream_t s) {
-  auto k0 = gemm_dma256_kernel<OT, AKM, BKM, 0>;
-  auto k3 = gemm_dma256_kernel<OT, AKM, BKM, 0, 3>;
-  static int attr_rc = ensure_lds(k0, LDS256) | ensure_lds(k3, LDS256);
-  if (attr_rc) return attr_rc;
-  // The K-step schedule variants that rounds 2-4 measured and rejected (ST = 4: all fragment reads first; the ping-pong tile;
-  // the timing ablations) exist only in the diagnostic build: GSTVD_DIAG_ST, GSTVD_DIAG_PP, GSTVD_DIAG_ABLATE.
-  int abl = 0, st = 0;
-#ifdef GSTVD_DIAG
-  auto p0 = gemm_dma256_kernel<OT, AKM, BKM, 0, 4, 4>;
-  auto p3 = gemm_dma256_kernel<OT, AKM, BKM, 0, 3, 4>;
-  auto ke = gemm_dma256_kernel<OT, AKM, BKM, -5>;
-  auto c0 = gemm_dma256_kernel<OT, AKM, BKM, 0, 4, 3>;
-  auto c1 = gemm_dma256_kernel<OT, AKM, BKM, -1, 4, 3>;
-  auto c2 = gemm_dma256_kernel<OT, AKM, BKM, -2, 4, 3>;
-  auto c7 = gemm_dma256_kernel<OT, AKM, BKM, -7, 4, 3>;
-  auto c8 = gemm_dma256_kernel<OT, AKM, BKM, -8, 4, 3>;
-  auto p1 = gemm_dma256_kernel<OT, AKM, BKM, -1, 4, 4>;
-  auto ka = gemm_dma256_kernel<OT, AKM, BKM, -1>;
-  auto kb = gemm_dma256_kernel<OT, AKM, BKM, -2>;
-  auto kf = gemm_dma256_kernel<OT, AKM, BKM, -6>;
-  static int diag_rc = ensure_lds(c0, LDS256) | ensure_lds(c1, LDS256) | ensure_lds(c2, LDS256) | ensure_lds(c7, LDS256) |
-                       ensure_lds(c8, LDS256) | ensure_lds(p1, LDS256) | ensure_lds(ka, LDS256) | ensure_lds(kb, LDS256) |
-                       ensure_lds(kf, LDS256) | ensure_lds(ke, LDS256) | ensure_lds(p0, LDS256) | ensure_lds(p3, LDS256);
-  if (diag_rc) return diag_rc;
-  static const int st_env = [] { const char* e = getenv("GSTVD_DIAG_ST"); return e ? atoi(e) : 0; }();
-  static const int pp = [] { const char* e = getenv("GSTVD_DIAG_PP"); return e ? atoi(e) : 0; }();
-  static const int diag_abl = [] { const char* e = getenv("GSTVD_DIAG_ABLATE"); return e ? atoi(e) : 0; }();
-  abl = diag_abl ? diag_abl : (pp ? 5 : 0);
-  st = (st_env == 3 || st_env == 4) ? st_env : 0;
-#endif
-  const int bnu = (niu == 3 && abl == 0) ? 192 : 256;
+  const int bnu = niu == 3 ? 192 : 256;
   const int ntm = (int)((p.M + 255) / 256), ntn = (int)((p.N + bnu - 1) / bnu);
-  // producer / consumer form: measured -7 % per launch on single-round grids (4096x3072x768 33.8 -> 31.3 us, per K-step 0.82 ->
-  // 0.76 us), +7 % on the 1368-tile cross-K/V projection (its extra ~1.5 us of fixed cost is paid 5.3 times): up to 2 rounds of tiles
-  static const int pc = [] { const char* e = getenv("GSTVD_GEMM_PC"); return e ? atoi(e) : 1; }();
-  if (pc && abl == 0 && st == 0 && (pc == 2 || (int64_t)ntm * ntn * batch <= 512)) {
-    if constexpr (!AKM && !BKM) {
-      // full-line (64-deep, alternating) staging of two row-major operands; GSTVD_GEMM_NT64=0 keeps the 32-deep stages (A/B)
-      static const int nt64 = [] { const char* e = getenv("GSTVD_GEMM_NT64"); return e ? atoi(e) : 1; }();
-      if (nt64 && p.K % 64 == 0 && p.K >= 128) {
-        auto n4 = gemm_pc256_nt64_kernel<OT, 4>;
-        auto n3 = gemm_pc256_nt64_kernel<OT, 3>;
-        constexpr int L4 = 3 * 256 * 128 + 2 * 256 * 128, L3 = 3 * 256 * 128 + 2 * 192 * 128;
-        constexpr int P4 = 8 * epi_wave_bytes<4, 4>(), P3 = 8 * epi_wave_bytes<3, 4>();
-        constexpr int lds4 = L4 > P4 ? L4 : P4, lds3 = L3 > P3 ? L3 : P3;
-        static_assert(lds4 <= 160 * 1024 && lds3 <= 160 * 1024, "LDS budget");
-        static int nt_rc = ensure_lds(n4, lds4) | ensure_lds(n3, lds3);
-        if (nt_rc) return nt_rc;
-        GSTVD_LAUNCH(bnu == 192 ? n3 : n4, dim3((unsigned)(ntm * ntn), (unsigned)batch), dim3(768), bnu == 192 ? lds3 : lds4, s, p, ntn, ntm * ntn);
-        GSTVD_LAUNCH_CHECK();
-        return 0;
-      }
-    }
-    auto c4 = gemm_pc256_kernel<OT, AKM, BKM, 4>;
-    auto c3 = gemm_pc256_kernel<OT, AKM, BKM, 3>;
-    static int pc_rc = ensure_lds(c4, LDS256) | ensure_lds(c3, LDS256);
-    if (pc_rc) return pc_rc;
-    GSTVD_LAUNCH(bnu == 192 ? c3 : c4, dim3((unsigned)(ntm * ntn), (unsigned)batch), dim3(768), LDS256, s, p, ntn, ntm * ntn);
+  const dim3 grid((unsigned)(ntm * ntn), (unsigned)batch);
+  if ((int64_t)ntm * ntn * batch > PC256_MAX_TILES) {
+    auto k4 = gemm_dma256_kernel<OT, AKM, BKM, 4>;
+    auto k3 = gemm_dma256_kernel<OT, AKM, BKM, 3>;
+    static int attr_rc = ensure_lds(k4, LDS256) | ensure_lds(k3, LDS256);
+    if (attr_rc) return attr_rc;
+    GSTVD_LAUNCH(bnu == 192 ? k3 : k4, grid, dim3(512), LDS256, s, p, ntn, ntm * ntn);
     GSTVD_LAUNCH_CHECK();
     return 0;
   }
-  auto kern = bnu == 192 ? k3 : k0;
-#ifdef GSTVD_DIAG
-  if (st == 4) kern = abl == 1 ? p1 : (bnu == 192 ? p3 : p0);
-  else if (st == 3) kern = abl == 1 ? c1 : abl == 2 ? c2 : abl == 7 ? c7 : abl == 8 ? c8 : c0;
-  else if (abl == 5) kern = ke;
-  else if (abl == 1) kern = ka;
-  else if (abl == 2) kern = kb;
-  else if (abl == 6) kern = kf;
-#endif
-  GSTVD_LAUNCH(kern, dim3((unsigned)(ntm * ntn), (unsigned)batch), dim3(512), LDS256, s, p, ntn, ntm * ntn);
+  if constexpr (!AKM && !BKM) {
+    // full-line (64-deep, alternating) staging of two row-major operands
+    if (p.K % 64 == 0 && p.K >= 128) {
+      auto n4 = gemm_pc256_nt64_kernel<OT, 4>;
+      auto n3 = gemm_pc256_nt64_kernel<OT, 3>;
+      constexpr int L4 = 3 * 256 * 128 + 2 * 256 * 128, L3 = 3 * 256 * 128 + 2 * 192 * 128;
+      constexpr int P4 = 8 * epi_wave_bytes<4, 4>(), P3 = 8 * epi_wave_bytes<3, 4>();
+      constexpr int lds4 = L4 > P4 ? L4 : P4, lds3 = L3 > P3 ? L3 : P3;
+      static_assert(lds4 <= 160 * 1024 && lds3 <= 160 * 1024, "LDS budget");
+      static int nt_rc = ensure_lds(n4, lds4) | ensure_lds(n3, lds3);
+      if (nt_rc) return nt_rc;
+      GSTVD_LAUNCH(bnu == 192 ? n3 : n4, grid, dim3(768), bnu == 192 ? lds3 : lds4, s, p, ntn, ntm * ntn);
+      GSTVD_LAUNCH_CHECK();
+      return 0;
+    }
+  }
+  auto c4 = gemm_pc256_kernel<OT, AKM, BKM, 4>;
+  auto c3 = gemm_pc256_kernel<OT, AKM, BKM, 3>;
+  static int pc_rc = ensure_lds(c4, LDS256) | ensure_lds(c3, LDS256);
+  if (pc_rc) return pc_rc;
+  GSTVD_LAUNCH(bnu == 192 ? c3 : c4, grid, dim3(768), LDS256, s, p, ntn, ntm * ntn);
   GSTVD_LAUNCH_CHECK();
   return 0;
 }
@@ -919,87 +717,28 @@ static int pick_niu(const GemmP& p, int64_t batch) {
   return r3 * (14.0 + 0.84 * nkt) < r4 * (14.0 + 0.95 * nkt) ? 3 : 4;     // measured 0.73 vs 0.82 us per step at K = 768
 }
 
-// Single-problem policy: the big tile only pays when its (4x smaller) grid still covers most of the chip.
 int gemm_dma256_dispatch(const GemmP& p, int64_t batch, int akm, int bkm, int out_f32, hipStream_t s) {
-  static const int min_tiles = [] { const char* e = getenv("GSTVD_GEMM256_MIN_TILES"); return e ? atoi(e) : 120; }();
   const int64_t tiles = ((p.M + 255) / 256) * ((p.N + 255) / 256) * batch;
-  if (p.M < 256 || p.N < 256 || tiles < min_tiles) return GSTVD_E_UNSUPPORTED;
+  if (p.M < 256 || p.N < 256 || tiles < GEMM256_MIN_TILES) return GSTVD_E_UNSUPPORTED;
   const int niu = pick_niu(p, batch);
   return out_f32 ? launch256_layout<float>(p, batch, akm, bkm, niu, s) : launch256_layout<bf16>(p, batch, akm, bkm, niu, s);
 }
 
-template <typename OT, bool AKM, bool BKM>
-__global__ __launch_bounds__(768) void gemm_pc256_grouped_kernel(const gstvd_gemm_t* tab, const int* tile_off, int nprob, int total, int chs,
-                                                                 const int* bmap) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int entry = grouped_tile_id(bmap, total, chs);
-  if (entry < 0) return;
-  const int gid = entry & GROUP_TILE_MASK;
-  if (gid >= total) return;                  // a map entry that names no tile of the table (the host checks the map it builds; this keeps a bad one from writing)
-  int lo = 0, hi = nprob - 1;
-  while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (tile_off[mid] <= gid) lo = mid; else hi = mid - 1; }
-  const gstvd_gemm_t& g = tab[lo];
-  GemmP p;
-  p.A = (const char*)g.A; p.B = (const char*)g.B; p.C = (char*)g.C;
-  p.bias = g.bias; p.addend = (const char*)g.addend; p.aux = (char*)g.aux;
-  p.M = g.M; p.N = g.N; p.K = g.K;
-  p.lda = g.lda; p.ldb = g.ldb; p.ldc = g.ldc; p.ldadd = g.ldadd; p.ldaux = g.ldaux;
-  p.sA = p.sB = p.sC = p.sAdd = p.sAux = 0;
-  p.epi = g.epilogue; p.alpha = g.alpha; p.p = g.dropout_p; p.site = g.site; p.rng = g.rng;
-  const int ntn = (int)((g.N + 255) / 256), ntm = (int)((g.M + 255) / 256);
-  pc_tile256<OT, AKM, BKM, 4, true>(p, 0, gid - tile_off[lo], ntn, ntm * ntn, smem);
-}
-
-__global__ __launch_bounds__(768) void gemm_pc256_grouped_adamw_kernel(const gstvd_gemm_t* tab, const int* tile_off, int nprob, int total, int chs,
-                                                                       const int* bmap, gstvd_adamw_fuse_t af) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int entry = grouped_tile_id(bmap, total, chs);
-  if (entry < 0) return;
-  const int gid = entry & GROUP_TILE_MASK;
-  if (gid >= total) return;                  // a map entry that names no tile of the table (the host checks the map it builds; this keeps a bad one from writing)
-  int lo = 0, hi = nprob - 1;
-  while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (tile_off[mid] <= gid) lo = mid; else hi = mid - 1; }
-  const gstvd_gemm_t& g = tab[lo];
-  GemmP p;
-  p.A = (const char*)g.A; p.B = (const char*)g.B; p.C = (char*)g.C;
-  p.bias = g.bias; p.addend = (const char*)g.addend; p.aux = (char*)g.aux;
-  p.M = g.M; p.N = g.N; p.K = g.K;
-  p.lda = g.lda; p.ldb = g.ldb; p.ldc = g.ldc; p.ldadd = g.ldadd; p.ldaux = g.ldaux;
-  p.sA = p.sB = p.sC = p.sAdd = p.sAux = 0;
-  p.epi = g.epilogue; p.alpha = g.alpha; p.p = g.dropout_p; p.site = g.site; p.rng = g.rng;
-  const int ntn = (int)((g.N + 255) / 256), ntm = (int)((g.M + 255) / 256);
-  pc_tile256<float, true, true, 4, true, true>(p, 0, gid - tile_off[lo], ntn, ntm * ntn, smem, af);
-}
-
+// Weight gradients are long-K problems (K = rows of the batch): the producer / consumer tile gains ~0.08 us on every one of
+// their ~128 K-steps (18432x768x4688: 160 -> 143 us).
 template <typename OT, bool AKM, bool BKM>
 static int grouped256(const gstvd_gemm_t* tab, const int* off, int nprob, int total, const int* bmap, int nblocks, hipStream_t s) {
-  auto k0 = gemm_dma256_grouped_kernel<OT, AKM, BKM, 0>;
-  static int attr_rc = ensure_lds(k0, LDS256);
-  if (attr_rc) return attr_rc;
-  // tiles per XCD chunk = 2^chs (default 8: measured best of 1..128 inside the step); GSTVD_GROUP_CHUNK_LOG2 overrides for tuning runs
-  static const int chs = [] { const char* e = getenv("GSTVD_GROUP_CHUNK_LOG2"); const int v = e ? atoi(e) : 3; return v < 0 ? 0 : (v > 10 ? 10 : v); }();
-  // weight gradients are long-K problems (K = rows of the batch): the producer / consumer tile gains ~0.08 us on every one of
-  // their ~128 K-steps (18432x768x4688: 160 -> 143 us)
-  static const int pc = [] { const char* e = getenv("GSTVD_GEMM_PC"); return e ? atoi(e) : 1; }();
-  if (pc) {
-    auto kp = gemm_pc256_grouped_kernel<OT, AKM, BKM>;
-    static int pc_rc = ensure_lds(kp, LDS256);
-    if (pc_rc) return pc_rc;
-    GSTVD_LAUNCH(kp, dim3((unsigned)(bmap ? nblocks : total)), dim3(768), LDS256, s, tab, off, nprob, total, chs, bmap);
-    GSTVD_LAUNCH_CHECK();
-    return 0;
-  }
-  GSTVD_LAUNCH(k0, dim3((unsigned)(bmap ? nblocks : total)), dim3(512), LDS256, s, tab, off, nprob, total, chs, bmap);
+  auto kp = gemm_pc256_grouped_kernel<OT, AKM, BKM>;
+  static int pc_rc = ensure_lds(kp, LDS256);
+  if (pc_rc) return pc_rc;
+  GSTVD_LAUNCH(kp, dim3((unsigned)(bmap ? nblocks : total)), dim3(768), LDS256, s, tab, off, nprob, total, GROUP_CHUNK_LOG2, bmap);
   GSTVD_LAUNCH_CHECK();
   return 0;
 }
 
 extern "C" int gstvd_gemm_group_tile(void) { return 256; }
 
-extern "C" int32_t gstvd_gemm_group_caps(void) {
-  const char* e = getenv("GSTVD_GEMM_PC");
-  return (e ? atoi(e) : 1) != 0 ? 1 : 0;
-}
+extern "C" int32_t gstvd_gemm_group_caps(void) { return 1; }
 
 // symbol of the grouped kernel for a (dtype, layout) combination -- same plan-only mechanism as gstvd_gemm_kernel_name
 extern "C" int gstvd_gemm_grouped_kernel_name(int32_t dtype_in, int32_t dtype_out, int32_t a_kmajor, int32_t b_kmajor, char* buf,
@@ -1012,31 +751,13 @@ extern "C" int gstvd_gemm_grouped_kernel_name(int32_t dtype_in, int32_t dtype_ou
   const int rc = gstvd_gemm_grouped(&dummy_tab, &dummy_off, 1, 1, dtype_in, dtype_out, a_kmajor, b_kmajor, nullptr, 0, nullptr);
   gstvd_plan_capture = nullptr;
   if (rc) return rc;
-  const char* name = fn ? hipKernelNameRefByPtr(fn, nullptr) : nullptr;
-  if (!name) return GSTVD_E_UNSUPPORTED;
-  int i = 0;
-  for (; name[i] && i < buf_len - 1; ++i) buf[i] = name[i];
-  buf[i] = 0;
-  return 0;
+  return copy_kernel_name(fn, buf, buf_len);
 }
 
 extern "C" int gstvd_gemm_grouped_adamw_kernel_name(char* buf, int32_t buf_len) {
   if (!buf || buf_len <= 1) return GSTVD_E_NULL;
-  const char* name = hipKernelNameRefByPtr((const void*)gemm_pc256_grouped_adamw_kernel, nullptr);
-  if (!name) return GSTVD_E_UNSUPPORTED;
-  int i = 0;
-  for (; name[i] && i < buf_len - 1; ++i) buf[i] = name[i];
-  buf[i] = 0;
-  return 0;
+  return copy_kernel_name((const void*)gemm_pc256_grouped_adamw_kernel, buf, buf_len);
 }
-
-#ifdef GSTVD_DIAG
-extern "C" int gstvd_debug_gemm_clock(uint64_t* out_host, int32_t n_words) {
-  if (!out_host || n_words <= 0 || n_words > 512 * 4) return GSTVD_E_SHAPE;
-  hipError_t e = hipMemcpyFromSymbol(out_host, HIP_SYMBOL(g_clk256), (size_t)n_words * 8, 0, hipMemcpyDeviceToHost);
-  return e == hipSuccess ? 0 : (int)e;
-}
-#endif
 
 extern "C" int gstvd_gemm_grouped_adamw(const gstvd_gemm_t* table_dev, const int32_t* tile_off_dev, int64_t nprob, int64_t total_tiles,
                                         const gstvd_adamw_fuse_t* f, const int32_t* block_map_dev, int64_t nblocks, gstvd_stream_t stream) {
@@ -1045,13 +766,11 @@ extern "C" int gstvd_gemm_grouped_adamw(const gstvd_gemm_t* table_dev, const int
   if (nprob <= 0 || total_tiles <= 0) return GSTVD_E_SHAPE;
   if (block_map_dev && (nblocks < total_tiles || total_tiles > GROUP_TILE_MASK)) return GSTVD_E_SHAPE;     // a map that cannot name every tile
   if (((uintptr_t)f->grad_base | (uintptr_t)f->param | (uintptr_t)f->m | (uintptr_t)f->v | (uintptr_t)f->shadow_bf16) & 15) return GSTVD_E_ALIGN;
-  if (!(gstvd_gemm_group_caps() & 1)) return GSTVD_E_UNSUPPORTED;     // the producer / consumer tile is switched off (tuning runs)
   auto kp = gemm_pc256_grouped_adamw_kernel;
   static int rc = ensure_lds(kp, LDS256);
   if (rc) return rc;
-  static const int chs = [] { const char* e = getenv("GSTVD_GROUP_CHUNK_LOG2"); const int v = e ? atoi(e) : 3; return v < 0 ? 0 : (v > 10 ? 10 : v); }();
   GSTVD_LAUNCH(kp, dim3((unsigned)(block_map_dev ? nblocks : total_tiles)), dim3(768), LDS256, (hipStream_t)stream, table_dev, tile_off_dev,
-               (int)nprob, (int)total_tiles, chs, block_map_dev, *f);
+               (int)nprob, (int)total_tiles, GROUP_CHUNK_LOG2, block_map_dev, *f);
   GSTVD_LAUNCH_CHECK();
   return 0;
 }

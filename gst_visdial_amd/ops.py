@@ -4,7 +4,6 @@ torch is used only as the owner of device memory and of the HIP stream; every fu
 a hand-written gfx950 kernel on `torch.cuda.current_stream()` and raises if the library is missing,
 a tensor is not on the GPU, or the kernel returns a non-zero status.  No fallbacks.
 """
-import os
 import ctypes as C
 
 import torch
@@ -44,9 +43,6 @@ def _stream():
     if _RAW_STREAM is not None and _DEV_INDEX is not None:
         return _RAW_STREAM(_DEV_INDEX)
     return torch.cuda.current_stream().cuda_stream
-
-
-GEMM256_MIN_TILES = int(__import__("os").environ.get("GSTVD_GEMM256_MIN_TILES", "120"))
 
 
 class Profiler(object):
@@ -96,16 +92,6 @@ def _prof_end(e0, tag, flops=0.0, nbytes=0.0, detail=None):
     e1 = torch.cuda.Event(enable_timing=True)
     e1.record()
     Profiler.active.records.append((tag, flops, nbytes, e0, e1, detail, Profiler.scope))
-
-
-def gemm_tag(dtype_in, a_km, b_km, M, N, batch):
-    """Name of the kernel instantiation gstvd_gemm dispatches to (same rule as launch_layout in csrc/gemm.hip)."""
-    big = ((M + 127) // 128) * ((N + 127) // 128) * batch
-    tile = 128 if (M >= 256 and N >= 128 and big >= 96) else 64
-    if dtype_in == BF16 and M >= 256 and N >= 256 and ((M + 255) // 256) * ((N + 255) // 256) * batch >= GEMM256_MIN_TILES:
-        tile = 256
-    lay = {(0, 0): "nt", (0, 1): "nn", (1, 1): "tn", (1, 0): "tt"}[(int(a_km), int(b_km))]
-    return "gemm_%s_%s_%d" % ("bf16" if dtype_in == BF16 else "f32", lay, tile)
 
 
 _KNAME = {}
@@ -208,7 +194,7 @@ def gemv_ln(A, B, C_out, M, N, K, gamma, beta, eps, y_out=None, bias=None, adden
     return C_out
 
 
-SPLITK = int(os.environ.get("GSTVD_GEMM_SPLITK", "1"))
+SPLITK = 1                  # 0: never split (the reference path of the split-K test)
 _SPLITK_WS = {}
 
 

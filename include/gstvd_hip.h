@@ -347,22 +347,13 @@ int gstvd_gemm_grouped_adamw_kernel_name(char* buf, int32_t buf_len);
  * gstvd_gemm.  y_out (or NULL): bf16 [M, ldy >= K] receives LN(A), the residual input of the sub-layer's closing Linear.
  * GSTVD_E_UNSUPPORTED for any other shape (the caller then runs gstvd_ln_fwd + gstvd_gemm). */
 int gstvd_gemv_ln(const gstvd_gemm_t* g, const float* gamma, const float* beta, float eps, void* y_out, int64_t ldy, gstvd_stream_t s);
-/* bit 0: gstvd_gemm_grouped honours GSTVD_EPI_COLSUM (the producer / consumer kernel is the one it launches) */
+/* bit 0: gstvd_gemm_grouped honours GSTVD_EPI_COLSUM (always set: the producer / consumer kernel is the one it launches) */
 int32_t gstvd_gemm_group_caps(void);
 /* Measurement support: the (mangled) symbol of the device kernel that gstvd_gemm (splits <= 1) or gstvd_gemm_splitk
  * (splits >= 2) would launch for this descriptor -- the dispatch runs, the launch is replaced by recording its target.
  * bench.py's roofline.kernel comes from here.  Nothing is launched; pointers in the descriptor are not dereferenced. */
 int gstvd_gemm_kernel_name(const gstvd_gemm_t* g, int32_t splits, char* buf, int32_t buf_len);
 int gstvd_gemm_grouped_kernel_name(int32_t dtype_in, int32_t dtype_out, int32_t a_kmajor, int32_t b_kmajor, char* buf, int32_t buf_len);
-
-#ifdef GSTVD_DIAG
-/* DIAGNOSTIC BUILD ONLY (lib/libgstvd_hip_diag.so, `make -C gst_visdial_amd/csrc diag`; the product library neither exports this
- * symbol nor contains the timing ablations it serves): copies the in-kernel clock stamps that the GSTVD_GEMM_ST=3 variant of the
- * 256x256 GEMM tile leaves behind -- per workgroup {shader-clock ticks, 100 MHz wall ticks, K steps, 0} around its K loop -- to
- * host memory.  Evidence for DESIGN.md's "what clock does an MFMA-dense loop hold" (MI355X_MICROARCH.md, DVFS give-back item 6);
- * replaces nothing in the reference. */
-int gstvd_debug_gemm_clock(uint64_t* out_host, int32_t n_words);
-#endif
 
 #ifdef __cplusplus
 }

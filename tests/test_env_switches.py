@@ -1,13 +1,14 @@
 """the product carries only the environment switches DESIGN.md section 5 documents -- the settings
-rounds 2-5 measured and rejected are gone (or live in the -DGSTVD_DIAG build that only tools/ load).  The documented list
-must equal (a) the GSTVD_* strings in the shipped library and (b) the GSTVD_* names the package's os.environ reads use."""
+rounds 2-5 measured and rejected are gone, and so are the GEMM library's tuning switches.  The documented list must equal
+(a) the GSTVD_* strings in the shipped library and (b) the GSTVD_* names the package's os.environ reads use."""
 import glob
 import os
 import re
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REJECTED = {"GSTVD_GROUP_ORDER", "GSTVD_GEMM_ST", "GSTVD_GEMM_PP", "GSTVD_GEMM_VARIANT", "GSTVD_KV_SIDE", "GSTVD_GEMM128_N96",
-            "GSTVD_GEMM256_NIU"}
+            "GSTVD_GEMM256_NIU", "GSTVD_GEMM_PC", "GSTVD_GEMM_NT64", "GSTVD_GEMM256_MIN_TILES", "GSTVD_GROUP_CHUNK_LOG2",
+            "GSTVD_GEMM_SPLITK"}
 
 
 def _documented():

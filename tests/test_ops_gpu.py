@@ -38,7 +38,8 @@ def rnd(*shape, dtype=torch.float32, seed=0, s=1.0):
 # ------------------------------------------------------------------------------------------ GEMM
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("M,N,K", [(200, 96, 64), (300, 256, 128), (111, 64, 320), (592, 1024, 256), (1024, 768, 192),
-                                   (2816, 3072, 160), (3000, 2824, 104)])      # the last two take the 256x256x32 tile
+                                   (2816, 3072, 160), (3000, 2824, 104),       # the 256x256x32 producer / consumer tile
+                                   (8192, 4352, 64)])                           # > 512 256-tiles: the 8-wave 256x256x32 tile
 def test_gemm_forward_bias(dtype, M, N, K):
     o = ops()
     x, w = rnd(M, K, dtype=dtype, seed=1), rnd(N, K, dtype=dtype, seed=2, s=0.1)

@@ -1,12 +1,12 @@
 #!/usr/bin/env python3
 """Back-to-back timing + correctness of the step's main GEMM shapes through the C ABI (bf16 in/out; tn: fp32 out).
-usage: gemm_bench.py [set] [lib]   set in: main (default) | small | mscale | all.  Tuning env vars (GSTVD_GEMM_*) apply.
+usage: gemm_bench.py [set] [lib]   set in: main (default) | small | mscale | all.
 `lib`: also time torch.matmul (the vendor BLAS behind it) on the same operands -- a speed-of-light REFERENCE for the tile design,
 never a code path of the product (which has no BLAS call)."""
 import os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import torch
-from gst_visdial_amd import ops
+from gst_visdial_amd import ops, _lib as L
 dev = "cuda"
 MAIN = [("nt", 4096, 3072, 768), ("nn", 4096, 3072, 768), ("nt", 4096, 2304, 768), ("nt", 4096, 768, 3072), ("nn", 4096, 768, 3072),
         ("nn", 4096, 768, 2304), ("nt", 4096, 768, 768), ("nn", 4096, 768, 768), ("nt", 4688, 18432, 768), ("nn", 4688, 768, 18432),
@@ -14,6 +14,13 @@ MAIN = [("nt", 4096, 3072, 768), ("nn", 4096, 3072, 768), ("nt", 4096, 2304, 768
 SMALL = [("nt", 592, 1024, 1024), ("nn", 592, 1024, 1024), ("nt", 592, 3072, 1024), ("nn", 592, 1024, 3072), ("nt", 400, 768, 768),
          ("nn", 400, 768, 768), ("nt", 400, 2304, 768), ("nt", 400, 3072, 768), ("nn", 400, 768, 3072), ("nt", 400, 768, 3072),
          ("nt", 400, 30528, 768), ("nn", 400, 768, 30528)]
+def kernel_symbol(A, B, C, M, N, K, a_km, b_km):
+    """The device kernel the library launches for this problem (gstvd_gemm_kernel_name)."""
+    d = L.GemmDesc()
+    d.A, d.B, d.C, d.M, d.N, d.K, d.batch, d.alpha = A.data_ptr(), B.data_ptr(), C.data_ptr(), M, N, K, 1, 1.0
+    d.lda, d.ldb, d.ldc = A.stride(0), B.stride(0), C.stride(0)
+    d.dtype_in, d.dtype_out, d.a_kmajor, d.b_kmajor = ops.dt(A), ops.dt(C), int(a_km), int(b_km)
+    return ops.gemm_kernel_symbol(d, ops.splitk_plan(d.dtype_in, M, N, K, 1, a_km, b_km))
 def run(lay, M, N, K, reps=30):
     a_km, b_km = (lay == "tn"), (lay in ("nn", "tn"))
     g = torch.Generator(device=dev).manual_seed(M + N + K)
@@ -43,7 +50,7 @@ def run(lay, M, N, K, reps=30):
         e1.record(); torch.cuda.synchronize()
         ul = e0.elapsed_time(e1) * 1e3 / reps
         lib = "   | vendor BLAS (torch.matmul, bf16 out) %7.1f us %6.1f TFLOP/s" % (ul, 2.0 * M * N * K / ul / 1e6)
-    print("%s %5dx%5dx%5d %-22s %7.1f us  %6.1f TFLOP/s  relerr %.1e%s%s" % (lay, M, N, K, ops.gemm_tag(1, a_km, b_km, M, N, 1), us,
+    print("%s %5dx%5dx%5d %-56s %7.1f us  %6.1f TFLOP/s  relerr %.1e%s%s" % (lay, M, N, K, kernel_symbol(A, B, C, M, N, K, a_km, b_km), us,
           2.0 * M * N * K / us / 1e6, err, "  <-- WRONG" if err > 2e-2 else "", lib))
 # row scaling of the latency-bound decoder / vision problems: would running the decoder's rows as two half-size chains on two
 # streams shorten it?  Only if a launch gets faster with fewer rows.

@@ -1,6 +1,7 @@
 """Stand-alone: the plain grouped weight-gradient launch (no AdamW: its fabric reads are operand fetches only) on the STEP's table of
-problems -- or on its long-K / short-K part -- under GSTVD_GROUP_ORDER; for rocprofv3 --pmc FETCH_SIZE runs and event timing.
-    python tools/wgrad_table_probe.py [all|long|short|uniform]     (GSTVD_GROUP_ORDER in the environment)
+problems -- or on its long-K / short-K part -- under a tile placement (ops.GROUP_ORDER: 0 = the library's chunked order, else the
+host's per-XCD block map; default: the package's); for rocprofv3 --pmc FETCH_SIZE runs and event timing.
+    python tools/wgrad_table_probe.py [all|long|short|uniform] [GROUP_ORDER]
 Prints the operand bytes every problem needs once, so that FETCH_SIZE x 2 / that = how many times the launch fetched its operands."""
 import sys
 import os
@@ -26,6 +27,8 @@ def step_table():
 
 def main():
     which = sys.argv[1] if len(sys.argv) > 1 else "all"
+    if len(sys.argv) > 2:
+        ops.GROUP_ORDER = int(sys.argv[2])
     dev = torch.device("cuda:0")
     shapes = step_table()
     if which == "long":
@@ -56,8 +59,8 @@ def main():
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record(); launch(); e1.record(); torch.cuda.synchronize()
         best = min(best, e0.elapsed_time(e1))
-    print("table %s, GSTVD_GROUP_ORDER=%s: %d problems, %d tiles, operands once %.3f GB, C written %.3f GB; launch %.1f us"
-          % (which, os.environ.get("GSTVD_GROUP_ORDER", "default"), len(shapes), tiles, once / 1e9,
+    print("table %s, GROUP_ORDER=%d: %d problems, %d tiles, operands once %.3f GB, C written %.3f GB; launch %.1f us"
+          % (which, ops.GROUP_ORDER, len(shapes), tiles, once / 1e9,
              sum(4 * M * N for M, N, K in shapes) / 1e9, best * 1e3))
 
 
