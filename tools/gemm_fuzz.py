@@ -30,7 +30,8 @@ def run(n_cases=200, seed=0, verbose=True):
         A = mk(K, M) if a_km else mk(M, K)
         B = mk(K, N) if b_km else mk(N, K)
         out_f32 = rnd.random() < 0.15
-        C = torch.empty(M, N + pad, device=dev, dtype=torch.float32 if out_f32 else bf)[:, :N]
+        CANARY = 12288.0                                                   # exact in bf16 and fp32: the pad columns of C / aux must keep it
+        C = torch.full((M, N + pad), CANARY, device=dev, dtype=torch.float32 if out_f32 else bf)[:, :N]
         kw, ref = {}, (A.float().t() if a_km else A.float()) @ (B.float() if b_km else B.float().t())
         alpha = rnd.choice([1.0, 1.0, 0.125])
         ref = ref * alpha
@@ -41,7 +42,7 @@ def run(n_cases=200, seed=0, verbose=True):
         epi, aux = 0, None
         mode = rnd.choice(["none", "none", "gelu", "dgelu"]) if not out_f32 else "none"
         if mode == "gelu":
-            aux = torch.empty(M, N + pad, device=dev, dtype=bf)[:, :N]; epi = o.EPI_GELU
+            aux = torch.full((M, N + pad), CANARY, device=dev, dtype=bf)[:, :N]; epi = o.EPI_GELU
             u = ref.clone().requires_grad_(True); r2 = torch.nn.functional.gelu(u); r2.backward(torch.ones_like(r2)); aux_ref = u.grad; ref = r2.detach()
         elif mode == "dgelu":
             aux = mk(M, N); epi = o.EPI_DGELU; ref = ref * aux.float()
@@ -59,6 +60,10 @@ def run(n_cases=200, seed=0, verbose=True):
         if mode == "gelu":
             e2 = (aux.float() - aux_ref).abs().max().item()
             ok = ok and e2 <= 2e-2
+        for name, t in (("C", C), ("aux", aux if mode == "gelu" else None)):      # nothing may be written past column N
+            if t is not None and pad and not bool((torch.as_strided(t, (M, pad), (N + pad, 1), N) == CANARY).all()):
+                ok = False
+                print("case %d: pad columns of %s were written" % (case, name))
         if not ok:
             bad += 1
             print("FAIL case %d: %s M=%d N=%d K=%d pad=%d f32out=%s mode=%s drop=%s alpha=%g kw=%s err=%.3e" % (case, lay, M, N, K, pad, out_f32, mode, drop, alpha, sorted(kw), err))
