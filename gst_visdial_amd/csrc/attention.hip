@@ -24,6 +24,7 @@
 //   * fp32 parity mode runs the same skeleton on v_mfma_f32_16x16x4_f32.
 #include "common.h"
 #include <math.h>
+#include <stdio.h>
 #include <stdlib.h>
 #include <type_traits>
 
@@ -979,13 +980,51 @@ static int attn_check(const gstvd_attn_t* a, bool bwd) {
   return 0;
 }
 
-template <typename T, int D> static int attn_fwd_launch(const gstvd_attn_t& a, hipStream_t s) {
-  if (a.Lq == 1 && !a.causal && !(a.dropout_p > 0.f && a.rng) && a.Lk <= 8192) {      // the decode step's shape
+// The route of a launch: ONE decision, taken here, which the launchers below act on and gstvd_attn_kernel_name reports.
+enum AttnKind { ATTN_DECODE, ATTN_FWD_TILED, ATTN_BWD_TWOPART, ATTN_BWD_ONEPASS_BITS, ATTN_BWD_ONEPASS_E32, ATTN_BWD_ONEPASS_E64 };
+struct AttnRoute { int kind, nkb, nqb, dq_first; };
+// plan-only mode (gstvd_attn_kernel_name): the launch site records the kernel handle it WOULD have launched and launches nothing
+struct AttnPlan { const void* fn; int dq_first; };
+
+static AttnRoute attn_fwd_route(const gstvd_attn_t& a) {
+  AttnRoute r = {ATTN_FWD_TILED, 0, 0, -1};
+  if (a.Lq == 1 && !a.causal && !(a.dropout_p > 0.f && a.rng) && a.Lk <= 8192) r.kind = ATTN_DECODE;      // the decode step's shape
+  return r;
+}
+
+static bool attn_small_index_space_host(const gstvd_attn_t& a) {
+  return (uint64_t)a.B * (uint64_t)a.nh * (uint64_t)a.Lq * (uint64_t)((a.Lk + 3) & ~3) < (1ull << 33);
+}
+
+static AttnRoute attn_bwd_route(const gstvd_attn_t& a) {
+  AttnRoute r = {ATTN_BWD_TWOPART, (a.Lk + 63) / 64, (a.Lq + 63) / 64, 0};
+  if (a.dtype == GSTVD_BF16 && a.d == 64) {
+    // one pass per (row, head) when a head's keys fit its 16 waves and there are enough queries to be worth a whole CU
+    // (GSTVD_ATTN_ONEPASS=0: the two-part kernel everywhere, for A/B runs)
+    static const int onepass = [] { const char* e = getenv("GSTVD_ATTN_ONEPASS"); return e ? atoi(e) : 1; }();
+    if (onepass && !a.causal && a.Lk > 64 && a.Lk <= 256 && a.Lq >= 64 && a.Lq <= ONEPASS_MAX_LQ) {
+      const bool bits = a.drop_bits != nullptr && a.dropout_p > 0.f && a.rng != nullptr;     // forward left the keep bits of its draws
+      r.kind = bits ? ATTN_BWD_ONEPASS_BITS : attn_small_index_space_host(a) ? ATTN_BWD_ONEPASS_E32 : ATTN_BWD_ONEPASS_E64;
+      r.dq_first = -1;
+      return r;
+    }
+  }
+  // a dQ block walks nkb key chunks, a dK/dV block nqb query chunks (with two second products per tile: the longer one at a tie);
+  // the longer-running class goes first (round 5, profiles/r05_attn_block_order.txt; the forced orders of that A/B are gone)
+  r.dq_first = r.nkb > r.nqb ? 1 : 0;
+  return r;
+}
+
+template <typename T, int D> static int attn_fwd_launch(const gstvd_attn_t& a, hipStream_t s, AttnPlan* plan) {
+  const AttnRoute r = attn_fwd_route(a);
+  if (r.kind == ATTN_DECODE) {
+    if (plan) { plan->fn = (const void*)attn_decode_kernel<T, D>; return 0; }
     const int ldsd = (D + a.Lk) * 4;
     hipLaunchKernelGGL((attn_decode_kernel<T, D>), dim3((unsigned)a.nh, (unsigned)a.B), dim3(DEC_NT), ldsd, s, a);
     GSTVD_LAUNCH_CHECK();
     return 0;
   }
+  if (plan) { plan->fn = (const void*)attn_fwd_kernel<T, D>; return 0; }
   constexpr int lds = 2 * Img<T, D>::BYTES + 64 * 4;
   static int rc = attn_lds_attr(attn_fwd_kernel<T, D>, lds);
   if (rc) return rc;
@@ -1022,65 +1061,82 @@ __global__ __launch_bounds__(256, (D <= 64 ? 3 : 2)) void attn_bwd_kernel(gstvd_
   else attn_bwd_dq_body<T, D, false>(a, bx, h, b, smem);
 }
 
-static bool attn_small_index_space_host(const gstvd_attn_t& a) {
-  return (uint64_t)a.B * (uint64_t)a.nh * (uint64_t)a.Lq * (uint64_t)((a.Lk + 3) & ~3) < (1ull << 33);
-}
-
-template <typename T, int D> static int attn_bwd_launch(const gstvd_attn_t& a, hipStream_t s) {
+template <typename T, int D> static int attn_bwd_launch(const gstvd_attn_t& a, hipStream_t s, AttnPlan* plan) {
   constexpr bool BF = sizeof(T) == 2;
+  const AttnRoute r = attn_bwd_route(a);
+  if (plan) plan->dq_first = r.dq_first;
+  // attn_bwd_route names the one-pass kernel for (bf16, d = 64) only -- the same condition as this `if constexpr`, which exists so
+  // that the kernel is not instantiated for other types; should the two ever drift apart, the launch fails below instead of
+  // taking another kernel than the one gstvd_attn_kernel_name reports
   if constexpr (BF && D == 64) {
-    // one pass per (row, head) when a head's keys fit its 16 waves and there are enough queries to be worth a whole CU
-    // (GSTVD_ATTN_ONEPASS=0: the two-part kernel everywhere, for A/B runs)
-    static const int onepass = [] { const char* e = getenv("GSTVD_ATTN_ONEPASS"); return e ? atoi(e) : 1; }();
-    if (onepass && !a.causal && a.Lk > 64 && a.Lk <= 256 && a.Lq >= 64 && a.Lq <= ONEPASS_MAX_LQ) {
+    if (r.kind != ATTN_BWD_TWOPART) {
+      if (plan) {
+        plan->fn = r.kind == ATTN_BWD_ONEPASS_BITS ? (const void*)attn_bwd_onepass_kernel<true, true>
+                 : r.kind == ATTN_BWD_ONEPASS_E32 ? (const void*)attn_bwd_onepass_kernel<true, false>
+                                                  : (const void*)attn_bwd_onepass_kernel<false, false>;
+        return 0;
+      }
       constexpr int lds1p = 12 * Img<T, D>::BYTES + 2 * ONEPASS_MAX_LQ * 4 + 256 * 8;
       static int rc1 = attn_lds_attr(attn_bwd_onepass_kernel<true, false>, lds1p) | attn_lds_attr(attn_bwd_onepass_kernel<false, false>, lds1p) |
                        attn_lds_attr(attn_bwd_onepass_kernel<true, true>, lds1p);
       if (rc1) return rc1;
       dim3 grid((unsigned)a.nh, (unsigned)a.B);
-      const bool bits = a.drop_bits != nullptr && a.dropout_p > 0.f && a.rng != nullptr;     // forward left the keep bits of its draws
-      if (bits) hipLaunchKernelGGL((attn_bwd_onepass_kernel<true, true>), grid, dim3(1024), lds1p, s, a);
-      else if (attn_small_index_space_host(a)) hipLaunchKernelGGL((attn_bwd_onepass_kernel<true, false>), grid, dim3(1024), lds1p, s, a);
+      if (r.kind == ATTN_BWD_ONEPASS_BITS) hipLaunchKernelGGL((attn_bwd_onepass_kernel<true, true>), grid, dim3(1024), lds1p, s, a);
+      else if (r.kind == ATTN_BWD_ONEPASS_E32) hipLaunchKernelGGL((attn_bwd_onepass_kernel<true, false>), grid, dim3(1024), lds1p, s, a);
       else hipLaunchKernelGGL((attn_bwd_onepass_kernel<false, false>), grid, dim3(1024), lds1p, s, a);
       GSTVD_LAUNCH_CHECK();
       return 0;
     }
   }
+  if (r.kind != ATTN_BWD_TWOPART) return GSTVD_E_UNSUPPORTED;       // (the route names the one-pass kernel only for bf16, d = 64)
+  if (plan) { plan->fn = (const void*)attn_bwd_kernel<T, D>; return 0; }
   constexpr int lds1 = (BF ? 3 : 2) * Img<T, D>::BYTES + 64 * 4;
   constexpr int lds2 = (BF ? 4 : 2) * Img<T, D>::BYTES + 128 * 4;
   constexpr int lds = lds1 > lds2 ? lds1 : lds2;
   static int rc = attn_lds_attr(attn_bwd_kernel<T, D>, lds);
   if (rc) return rc;
-  const int nkb = (a.Lk + 63) / 64, nqb = (a.Lq + 63) / 64;
-  // a dQ block walks nkb key chunks, a dK/dV block nqb query chunks (with two second products per tile: the longer one at a tie);
-  // the longer-running class goes first (round 5, profiles/r05_attn_block_order.txt; the forced orders of that A/B are gone)
-  const int dq_first = nkb > nqb ? 1 : 0;
-  dim3 grid((unsigned)((nkb + nqb) * a.nh * a.B));
-  hipLaunchKernelGGL((attn_bwd_kernel<T, D>), grid, dim3(256), lds, s, a, nkb, nqb, dq_first);
+  dim3 grid((unsigned)((r.nkb + r.nqb) * a.nh * a.B));
+  hipLaunchKernelGGL((attn_bwd_kernel<T, D>), grid, dim3(256), lds, s, a, r.nkb, r.nqb, r.dq_first);
   GSTVD_LAUNCH_CHECK();
   return 0;
 }
 
-template <typename T> static int attn_fwd_d(const gstvd_attn_t& a, hipStream_t s) {
-  if (a.d == 32) return attn_fwd_launch<T, 32>(a, s);
-  if (a.d == 64) return attn_fwd_launch<T, 64>(a, s);
-  return attn_fwd_launch<T, 128>(a, s);
+template <typename T> static int attn_fwd_d(const gstvd_attn_t& a, hipStream_t s, AttnPlan* plan) {
+  if (a.d == 32) return attn_fwd_launch<T, 32>(a, s, plan);
+  if (a.d == 64) return attn_fwd_launch<T, 64>(a, s, plan);
+  return attn_fwd_launch<T, 128>(a, s, plan);
 }
-template <typename T> static int attn_bwd_d(const gstvd_attn_t& a, hipStream_t s) {
-  if (a.d == 32) return attn_bwd_launch<T, 32>(a, s);
-  if (a.d == 64) return attn_bwd_launch<T, 64>(a, s);
-  return attn_bwd_launch<T, 128>(a, s);
+template <typename T> static int attn_bwd_d(const gstvd_attn_t& a, hipStream_t s, AttnPlan* plan) {
+  if (a.d == 32) return attn_bwd_launch<T, 32>(a, s, plan);
+  if (a.d == 64) return attn_bwd_launch<T, 64>(a, s, plan);
+  return attn_bwd_launch<T, 128>(a, s, plan);
 }
 
-extern "C" int gstvd_attn_fwd(const gstvd_attn_t* a, gstvd_stream_t stream) {
+static int attn_fwd_entry(const gstvd_attn_t* a, hipStream_t s, AttnPlan* plan) {
   int rc = attn_check(a, false);
   if (rc) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  return a->dtype == GSTVD_BF16 ? attn_fwd_d<bf16>(*a, s) : attn_fwd_d<float>(*a, s);
+  return a->dtype == GSTVD_BF16 ? attn_fwd_d<bf16>(*a, s, plan) : attn_fwd_d<float>(*a, s, plan);
 }
-extern "C" int gstvd_attn_bwd(const gstvd_attn_t* a, gstvd_stream_t stream) {
+static int attn_bwd_entry(const gstvd_attn_t* a, hipStream_t s, AttnPlan* plan) {
   int rc = attn_check(a, true);
   if (rc) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  return a->dtype == GSTVD_BF16 ? attn_bwd_d<bf16>(*a, s) : attn_bwd_d<float>(*a, s);
+  return a->dtype == GSTVD_BF16 ? attn_bwd_d<bf16>(*a, s, plan) : attn_bwd_d<float>(*a, s, plan);
+}
+
+extern "C" int gstvd_attn_fwd(const gstvd_attn_t* a, gstvd_stream_t stream) { return attn_fwd_entry(a, (hipStream_t)stream, nullptr); }
+extern "C" int gstvd_attn_bwd(const gstvd_attn_t* a, gstvd_stream_t stream) { return attn_bwd_entry(a, (hipStream_t)stream, nullptr); }
+
+// Which kernel would gstvd_attn_fwd (bwd == 0) / gstvd_attn_bwd (bwd != 0) launch for this descriptor?  The entry point runs exactly
+// as for a launch -- same checks, same route -- in plan-only mode: nothing is launched, no memory is touched.  Writes the device
+// function's (mangled) symbol into buf; the two-part backward's answer carries its block order: "<symbol> dq_first=0|1".
+extern "C" int gstvd_attn_kernel_name(const gstvd_attn_t* a, int32_t bwd, char* buf, int32_t buf_len) {
+  if (!a || !buf || buf_len <= 1) return GSTVD_E_NULL;
+  AttnPlan plan = {nullptr, -1};
+  const int rc = bwd ? attn_bwd_entry(a, nullptr, &plan) : attn_fwd_entry(a, nullptr, &plan);
+  if (rc) return rc;
+  const char* name = plan.fn ? hipKernelNameRefByPtr(plan.fn, nullptr) : nullptr;
+  if (!name) return GSTVD_E_UNSUPPORTED;
+  const int n = plan.dq_first >= 0 ? snprintf(buf, (size_t)buf_len, "%s dq_first=%d", name, plan.dq_first)
+                                   : snprintf(buf, (size_t)buf_len, "%s", name);
+  return n >= 0 && n < buf_len ? 0 : GSTVD_E_SHAPE;      // (a buffer too small for the answer is an error, not a truncated name)
 }

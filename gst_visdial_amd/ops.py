@@ -705,6 +705,14 @@ def attn_desc(Q, K, V, O, LSE, key_mask, B, nh, Lq, Lk, d, *, causal=False, mask
     return a
 
 
+def attn_kernel_symbol(a, bwd=False):
+    """(Mangled) symbol of the device kernel gstvd_attn_fwd / gstvd_attn_bwd launch for descriptor `a` -- asked of the library's own
+    route decision (gstvd_attn_kernel_name).  The two-part backward's answer ends in " dq_first=0" or " dq_first=1"."""
+    buf = C.create_string_buffer(512)
+    L.check("gstvd_attn_kernel_name", L.load().gstvd_attn_kernel_name(C.byref(a), int(bool(bwd)), buf, 512))
+    return buf.value.decode()
+
+
 def attn_fwd(a):
     lib = L.load()
     e0 = _prof_begin()

@@ -232,6 +232,11 @@ typedef struct {
 } gstvd_attn_t;
 int gstvd_attn_fwd(const gstvd_attn_t* a, gstvd_stream_t s);
 int gstvd_attn_bwd(const gstvd_attn_t* a, gstvd_stream_t s);  /* dQ (+delta) then dK,dV */
+/* Measurement / test support: the (mangled) symbol of the device kernel gstvd_attn_fwd (bwd == 0) or gstvd_attn_bwd (bwd != 0)
+ * would launch for this descriptor, taken from the launchers' own route decision; same status codes as the launch.  Nothing is
+ * launched.  The two-part backward's answer carries its block order: "<symbol> dq_first=0|1".  GSTVD_E_SHAPE when buf_len is
+ * too small for the answer. */
+int gstvd_attn_kernel_name(const gstvd_attn_t* a, int32_t bwd, char* buf, int32_t buf_len);
 
 /* ---- LM head loss: CrossEntropyLoss(ignore_index) of visual_dialog_decoder.py:70-77 ----------
  * logits [M, ldl >= V]; row_loss [M] (0 for ignored rows); stats (fp32[3], written by the call):

@@ -18,9 +18,10 @@ import re
 import torch
 
 BF16, F32 = torch.bfloat16, torch.float32
-_INT = {torch.bfloat16: torch.int16, torch.float32: torch.int32}
+_INT = {torch.bfloat16: torch.int16, torch.float32: torch.int32, torch.int64: torch.int64}
 # canary bit patterns: finite, far from anything an integer GEMM produces, and not the image of one another's halves
-CANARY = {torch.bfloat16: 0x4B5A, torch.float32: 0x4B5A17C3}
+# (int64: the attention keep-bit buffer of tests/exact_attn.py)
+CANARY = {torch.bfloat16: 0x4B5A, torch.float32: 0x4B5A17C3, torch.int64: 0x4B5A17C32D693C87}
 A_RANGE, E_RANGE = 3, 8                 # operands uniform in [-3, 3]; bias / addend in [-8, 8]
 EXACT_LIMIT = 2 ** 24
 SPLITK_COUNTER_BYTES = 4096             # counter area at the head of the split-K scratch (csrc/gemm_dma.hip: SPLITK_MAX_TILES * 4)
@@ -426,11 +427,16 @@ class Problem(object):
 KERNEL_RE = re.compile(rb"_Z\d+(?:gemm_\w*kernel|gemv16\w*kernel)\w*")
 
 
-def library_gemm_kernels(lib_path):
-    """Mangled names of every GEMM kernel instantiation the built library carries."""
+def library_kernels(lib_path, pattern):
+    """Mangled names of every kernel instantiation of the built library that the (bytes) regular expression matches."""
     with open(lib_path, "rb") as f:
         blob = f.read()
-    return sorted(set(m.decode() for m in KERNEL_RE.findall(blob)))
+    return sorted(set(m.decode() for m in pattern.findall(blob)))
+
+
+def library_gemm_kernels(lib_path):
+    """Mangled names of every GEMM kernel instantiation the built library carries."""
+    return library_kernels(lib_path, KERNEL_RE)
 
 
 def lib_path():

@@ -346,6 +346,7 @@ def test_colsum(dtype):
 
 
 # ------------------------------------------------------------------------------------------ attention
+# (tolerance layer; the exact layer -- one-hot / uniform inputs, canary windows, route census -- is tests/test_attn_exact_gpu.py)
 def attn_ref(q, k, v, key_mask, causal, neg, scale, dmask):
     s = torch.einsum("bqhd,bkhd->bhqk", q, k) * scale
     Lq, Lk = q.shape[1], k.shape[1]
