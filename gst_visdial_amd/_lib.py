@@ -9,7 +9,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libgstvd_hip.so")
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 F32, BF16 = 0, 1
 EPI_BIAS, EPI_ADD, EPI_GELU, EPI_DGELU, EPI_DROPOUT = 1, 2, 4, 8, 16
@@ -70,6 +70,16 @@ class AdamFuse(C.Structure):
                 ("step", _vp), ("beta1", _f32), ("beta2", _f32), ("eps", _f32), ("grad_scale", _f32), ("write_grad", _i32)]
 
 
+class NspHeadDesc(C.Structure):
+    """gstvd_nsp_head_t: first-token gather, poolers, fusion, bi_seq_relationship and the 2-way softmax of one launch."""
+    _fields_ = [("xt", _vp), ("ldt", _i64), ("t_rows", _i64), ("xv", _vp), ("ldv", _i64), ("v_rows", _i64),
+                ("wt", _vp), ("ldwt", _i64), ("wv", _vp), ("ldwv", _i64),
+                ("bt", _vp), ("bv", _vp), ("wn", _vp), ("ldwn", _i64), ("bn", _vp),
+                ("z", _vp), ("ldz", _i64), ("prob0", _vp),
+                ("B", _i32), ("H", _i32), ("Hv", _i32), ("Hb", _i32), ("dtype", _i32), ("fusion", _i32),
+                ("kernel_name", _vp), ("kernel_name_len", _i32), ("reserved_", _i32)]
+
+
 class ColsumEntry(C.Structure):
     _fields_ = [("partial", _vp), ("out", _vp * 3), ("nblk", _i64), ("stride", _i64), ("H", _i64),
                 ("nvec", _i32), ("accumulate", _i32 * 3), ("blk0", _i32)]
@@ -123,6 +133,7 @@ SIGNATURES = {
     "gstvd_adamw_blocks": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _f32, _f32, _f32, _vp, _f32, _i64, _vp, _i64, _vp, _vp]),
     "gstvd_gemm_grouped_adamw": (_i32, [_vp, _vp, _i64, _i64, C.POINTER(AdamFuse), _vp, _i64, _vp]),
     "gstvd_gemm_grouped_adamw_kernel_name": (_i32, [C.c_char_p, _i32]),
+    "gstvd_nsp_head": (_i32, [C.POINTER(NspHeadDesc), _vp]),
 }
 
 _STATUS = {-1: "GSTVD_E_DTYPE", -2: "GSTVD_E_SHAPE", -3: "GSTVD_E_ALIGN", -4: "GSTVD_E_NULL", -5: "GSTVD_E_UNSUPPORTED"}

@@ -103,16 +103,24 @@ class FlatParams(object):
     nn.Parameters); every live nn.Parameter becomes a view of `P` and its `.grad` a view of `G`."""
 
     def __init__(self, model, precision):
-        enc_cfg, dec_cfg = model.encoder.config, model.decoder.config
-        bert = model.encoder.bert_pretrained.bert
-        gen = model.decoder.decoder
+        # `model`: an EncoderDecoderModel, or (encoder-only form) a VisualDialogEncoder of the discriminative enc_only arch
+        self.enc_only = not hasattr(model, "decoder")
+        encoder = model if self.enc_only else model.encoder
+        enc_cfg = encoder.config
+        bert = encoder.bert_pretrained.bert
         self.slots, self.items, self.pads = {}, [], []
         self.placed = {}
         self.off = 0
         H, Hv, Hb = enc_cfg.hidden_size, enc_cfg.v_hidden_size, enc_cfg.bi_hidden_size
-        V = dec_cfg.vocab_size
-        self.Vp = _round_up(V, 64)
-        lm_w = gen.lm_head.decoder.weight
+        if self.enc_only:
+            dec_cfg = gen = lm_w = None       # no decoder slots, no LM head: the word table keeps its own row count
+            self.Vp = 0
+        else:
+            dec_cfg = model.decoder.config
+            gen = model.decoder.decoder
+            V = dec_cfg.vocab_size
+            self.Vp = _round_up(V, 64)
+            lm_w = gen.lm_head.decoder.weight
 
         def place(name, params, shape=None, pad_rows_to=None):
             """Lay `params` out back to back under one fused slot `name`."""
@@ -164,7 +172,7 @@ class FlatParams(object):
             ffn(p, lay.intermediate, lay.output, ".fi", ".fo", ".ln2")
 
         self.enc_emb = bert.embeddings
-        self.dec_emb = gen.bert.embeddings
+        self.dec_emb = None if self.enc_only else gen.bert.embeddings
         emb("emb", self.enc_emb)
         ve = bert.v_embeddings
         place("vemb.img.w", [ve.image_embeddings.weight]); place("vemb.img.b", [ve.image_embeddings.bias])
@@ -189,6 +197,16 @@ class FlatParams(object):
                 place(p + ".ln2.w", [o.LayerNorm2.weight]); place(p + ".ln2.b", [o.LayerNorm2.bias])
                 ffn(p, c.v_intermediate, c.v_output, ".vfi", ".vfo", ".vln")
                 ffn(p, c.t_intermediate, c.t_output, ".tfi", ".tfo", ".tln")
+        if self.enc_only:
+            # the NSP head (models/vilbert_dialog.py:915-941,1038) is live here; cls.predictions.*, cls.imagePredictions.*,
+            # sep_embeddings and q_dense* stay in the dead buffer, as in the enc_dec form
+            cls = encoder.bert_pretrained.cls
+            self.marks["nsp"] = _round_up(self.off, 64)
+            place("pool.t.w", [bert.t_pooler.dense.weight]); place("pool.t.b", [bert.t_pooler.dense.bias])
+            place("pool.v.w", [bert.v_pooler.dense.weight]); place("pool.v.b", [bert.v_pooler.dense.bias])
+            place("nsp.w", [cls.bi_seq_relationship.weight]); place("nsp.b", [cls.bi_seq_relationship.bias])
+            self._finish(model, precision)
+            return
         self.marks["vlf"] = _round_up(self.off, 64)
         place("vlf.v.w", [model.vlfusion.fc_v.weight]); place("vlf.v.b", [model.vlfusion.fc_v.bias])
         place("vlf.l.w", [model.vlfusion.fc_l.weight]); place("vlf.l.b", [model.vlfusion.fc_l.bias])
@@ -222,6 +240,9 @@ class FlatParams(object):
         else:
             place("lm.w", [lm_w], shape=(self.Vp, lm_w.shape[1]), pad_rows_to=self.Vp)
         place("lm.b", [gen.lm_head.bias], shape=(self.Vp,), pad_rows_to=self.Vp)
+        self._finish(model, precision)
+
+    def _finish(self, model, precision):
         self.n_live = _round_up(self.off, 64)
         self.live = [p for p, _ in self.items]
         live_ids = set(id(p) for p in self.live)
@@ -245,9 +266,10 @@ class FlatParams(object):
         for p, off in self.items:
             p.data = P[off:off + p.numel()].view(p.shape)
         self.P, self.D = P, D
-        self.G = torch.zeros(self.n_live, dtype=torch.float32, device=device)
+        # (encoder-only form: inference only -- no gradient buffer, no gradient views)
+        self.G = None if self.enc_only else torch.zeros(self.n_live, dtype=torch.float32, device=device)
         self.S = torch.empty(self.n_live, dtype=torch.bfloat16, device=device) if self.precision == "bf16" else None
-        self.grad_views = [self.G[off:off + p.numel()].view(p.shape) for p, off in self.items]
+        self.grad_views = [] if self.enc_only else [self.G[off:off + p.numel()].view(p.shape) for p, off in self.items]
         self.ptrs = [(p, P[off:off + p.numel()].data_ptr()) for p, off in self.items]
         self.shadow_version = None
         self.device = device
@@ -289,7 +311,7 @@ class FlatParams(object):
             for d in shape:
                 n *= d
             return n
-        non_gemm = ("ln.w", "ln1.w", "ln2.w", "ln3.w", "vln.w", "tln.w", "vemb.loc.w")
+        non_gemm = ("ln.w", "ln1.w", "ln2.w", "ln3.w", "vln.w", "tln.w", "vemb.loc.w", "nsp.w")
         by_start = {}
         for name, (off, shape) in self.slots.items():
             gemm = name.endswith(".w") and not name.endswith(non_gemm)
@@ -331,10 +353,16 @@ class Engine(object):
     def __init__(self, model):
         # weak: the model owns the engine, not the other way round -- no reference cycle, so dropping the model frees the
         # flat buffers, the arena and any captured decode sessions by reference counting, not at some later GC pass
-        self._setup(weakref.ref(model), model.encoder.config, model.decoder.config, model.params)
+        if hasattr(model, "decoder"):
+            self._setup(weakref.ref(model), model.encoder.config, model.decoder.config, model.params)
+        else:
+            # encoder-only form: `model` is a VisualDialogEncoder of the enc_only arch (evaluate_disc.py); the encoder schedule
+            # is the same code, what follows it is `nsp_scores` instead of VLFusion + decoder
+            self._setup(weakref.ref(model), model.config, None, model.params)
 
     def _setup(self, model_ref, enc_cfg, dec_cfg, params):
         self._model_ref = model_ref
+        self.enc_only = dec_cfg is None
         self.enc_cfg, self.dec_cfg = enc_cfg, dec_cfg
         prec = params.get("amd_precision", "bf16")
         if prec not in ("bf16", "fp32"):
@@ -377,7 +405,7 @@ class Engine(object):
         # very objects the copied module tree gets)
         new = Engine.__new__(Engine)
         new._setup(weakref.ref(owner), copy.deepcopy(self.enc_cfg, memo), copy.deepcopy(self.dec_cfg, memo),
-                   copy.deepcopy(orig.params, memo))
+                   copy.deepcopy(orig.params, memo))      # (dec_cfg is None for the encoder-only form, and stays None)
         return new
 
     def close(self):
@@ -391,8 +419,11 @@ class Engine(object):
         if device.type != "cuda":
             raise GstvdError("gst_visdial_amd runs on MI355X only; tensors are on %s (no CPU path)" % device)
         ops.set_device(device)
-        gen = self.model.decoder.decoder
-        topo = (id(gen.bert.embeddings), id(self.model.encoder.bert_pretrained.bert.embeddings), id(gen.lm_head.decoder.weight))
+        if self.enc_only:
+            topo = (id(self.model.bert_pretrained.bert.embeddings),)
+        else:
+            gen = self.model.decoder.decoder
+            topo = (id(gen.bert.embeddings), id(self.model.encoder.bert_pretrained.bert.embeddings), id(gen.lm_head.decoder.weight))
         if self.flat is None or self.flat.topo != topo:
             self.flat = FlatParams(self.model, self.precision)
             self.flat.topo = topo
@@ -431,7 +462,8 @@ class Engine(object):
         self.W, self.Pv, self.Gv = {}, {}, {}
         for name in f.slots:
             self.Pv[name] = f.view(f.P, name)
-            self.Gv[name] = f.view(f.G, name)
+            if f.G is not None:
+                self.Gv[name] = f.view(f.G, name)
             self.W[name] = f.view(wbuf, name)
 
     # ------------------------------------------------------------------------------------------ helpers
@@ -1189,6 +1221,29 @@ class Engine(object):
         scores = torch.empty(rows, dtype=torch.float32, device=ids.device)
         ops.answer_scores(logits.t, lse, dec_ids.contiguous(), rows, U, scores)
         return scores
+
+    # ------------------------------------------------------------------------------------------ discriminative ranking
+    @torch.no_grad()
+    def nsp_scores(self, feats, loc, img_mask, ids, segs, att_mask):
+        """The eval branch of the enc_only arch (models/visual_dialog_encoder.py:68-74, vilbert_dialog.py:1400-1401,1482,1519):
+        the two-stream encoder, then ONE launch (gstvd_nsp_head) for first-token gather, both poolers, the fusion, cls.
+        bi_seq_relationship and the 2-way softmax.  -> (seq_relationship_score z [B, 2] fp32, prob0 [B] fp32 =
+        softmax(z, 1)[:, 0], what evaluate_disc.py:81-83 ranks by).  The MLM / image prediction heads over all B*T tokens,
+        whose outputs the reference's only caller discards (evaluate_disc.py:79), are not computed."""
+        if not self.enc_only:
+            raise GstvdError("nsp_scores belongs to the encoder-only engine of an enc_only VisualDialogEncoder")
+        self._begin(ids.device, False)
+        self.train = False
+        dummy = ids.new_zeros(ids.shape[0], 1)
+        I = self._inputs(feats, loc, img_mask, ids, segs, att_mask, dummy, None)
+        xt, xv = self.encoder(I)
+        Bn = I["B"]
+        z = torch.empty(Bn, 2, dtype=torch.float32, device=ids.device)
+        prob0 = torch.empty(Bn, dtype=torch.float32, device=ids.device)
+        ops.nsp_head(xt.t, I["T"], xv.t, I["R"], self.W["pool.t.w"], self.Pv["pool.t.b"], self.W["pool.v.w"], self.Pv["pool.v.b"],
+                     self.Pv["nsp.w"], self.Pv["nsp.b"], Bn, self.enc_cfg.fusion_method, z, prob0)
+        self.last = dict(enc_t=xt, enc_v=xv)
+        return z, prob0
 
     # ------------------------------------------------------------------------------------------ sampling decode
     def _decode_plan(self, ins, L0, max_seq_len):

@@ -1,0 +1,121 @@
+"""Discriminative evaluation: the build's counterpart of evaluate_disc.evaluate (evaluate_disc.py:27-118) and of the eval
+branch of train_disc.forward (train_disc.py:27-124) for a `VisualDialogEncoder` with model = 'enc_only_a'.
+
+Same batch contract (per-dialog tensors [B, rounds, options, L] from the disc eval dataloader; image tensors once per dialog)
+and the same metrics.  Two things differ, neither changes a result:
+  * the image tensors are expanded to one row per option by INDEXING the per-dialog tensors chunk by chunk, not by the
+    reference's 100x `.expand(...).contiguous()` copy of the whole batch (evaluate_disc.py:52-58);
+  * the ranking probability softmax(nsp_scores, 1)[:, 0] comes out of the head kernel itself (Engine.nsp_scores).
+Index work (sequence lengths, masks, chunk bounds, the row -> dialog map) is integer-exact torch code, restated bit for bit by
+tests/test_disc_cpu.py."""
+import torch
+
+from .metrics import SparseGTMetrics, NDCGBatchSum, scores_to_ranks
+
+
+def sequence_lengths(sep_indices, hist_len):
+    """train_disc.py:97-98: position of the [SEP] that closes the last utterance of the row, plus one."""
+    return torch.gather(sep_indices, 1, hist_len.view(-1, 1)).squeeze(1) + 1
+
+
+def sequence_mask(lengths, max_len):
+    """utils/data_utils.py:7-18, on the device `lengths` lives on: mask[b, t] = t < lengths[b] (bool)."""
+    return torch.arange(max_len, device=lengths.device).unsqueeze(0) < lengths.unsqueeze(1)
+
+
+def option_rows_to_dialog(num_dialogs, num_rounds, num_options):
+    """Row r of the flattened [dialog, round, option] batch belongs to dialog r // (rounds * options): the index that replaces
+    the reference's expand + contiguous of the image tensors (evaluate_disc.py:52-58)."""
+    return torch.arange(num_dialogs).repeat_interleave(num_rounds * num_options)
+
+
+def chunk_bounds(num_rows, rows_per_call):
+    """[(start, end)] of consecutive chunks of at most `rows_per_call` rows (the last one may be shorter; the reference asserts
+    divisibility, evaluate_disc.py:65)."""
+    if rows_per_call <= 0:
+        raise ValueError("rows_per_call must be positive")
+    return [(s, min(s + rows_per_call, num_rows)) for s in range(0, num_rows, rows_per_call)]
+
+
+def _module(encoder):
+    return getattr(encoder, "module", encoder)          # nn.DataParallel(encoder, [gpu]) of evaluate_disc.py:167
+
+
+def _prepare(item, params):
+    """The tensor work of train_disc.forward's eval branch (train_disc.py:32-67,87-99; sample_indices = arange): flatten,
+    move to the device, build the attention mask there."""
+    dev = params["device"]
+    tokens = item["tokens"]
+    tokens = tokens.view(-1, tokens.shape[-1]).to(dev)
+    segments = item["segments"].view(-1, item["segments"].shape[-1]).to(dev)
+    sep_indices = item["sep_indices"].view(-1, item["sep_indices"].shape[-1]).to(dev)
+    mask = item["mask"].view(-1, item["mask"].shape[-1]).to(dev)
+    hist_len = item["hist_len"].view(-1).to(dev)
+    f, l, m = item["image_feat"], item["image_loc"], item["image_mask"]
+    features = f.view(-1, f.shape[-2], f.shape[-1]).to(dev)
+    spatials = l.view(-1, l.shape[-2], l.shape[-1]).to(dev)
+    image_mask = m.view(-1, m.shape[-1]).to(dev)
+    att = sequence_mask(sequence_lengths(sep_indices, hist_len), tokens.shape[1])
+    return tokens, features, spatials, sep_indices, segments, mask, att, image_mask
+
+
+def forward_disc(encoder, item, params):
+    """Eval branch of train_disc.forward -> its 6-tuple (loss, lm_loss, nsp_loss, img_loss, nsp_scores, lm_scores): the losses
+    are None as there, and so is lm_scores (the MLM logits are not computed; modules.VisualDialogEncoder)."""
+    if "train" in params["mode"]:
+        raise NotImplementedError("forward_disc is the eval branch of train_disc.forward; train_disc.py is out of scope")
+    tokens, features, spatials, sep_indices, segments, mask, att, image_mask = _prepare(item, params)
+    _, _, _, nsp_scores, lm_scores, _, _ = encoder(tokens, features, spatials, sep_indices=sep_indices, token_type_ids=segments,
+                                                   masked_lm_labels=mask, attention_mask=att, image_attention_mask=image_mask)
+    return None, None, None, None, nsp_scores, lm_scores
+
+
+def chunk_item(batch, dialog_of_row, start, end):
+    """Rows [start, end) of a batch's flattened [dialog, round, option] rows as a train_disc.forward item; the image tensors of
+    a row are those of its dialog, picked by index."""
+    flat = lambda k: batch[k].reshape(-1, batch[k].shape[-1])
+    d = dialog_of_row[start:end]
+    return dict(tokens=flat("tokens")[start:end], segments=flat("segments")[start:end],
+                sep_indices=flat("sep_indices")[start:end], mask=flat("mask")[start:end],
+                hist_len=batch["hist_len"].reshape(-1)[start:end],
+                image_feat=batch["image_feat"][d], image_loc=batch["image_loc"][d], image_mask=batch["image_mask"][d])
+
+
+@torch.no_grad()
+def score_batch(encoder, batch, params, rows_per_call=200):
+    """-> softmax(nsp_scores, 1)[:, 0] of every answer option, [dialogs, rounds, options] fp32 on the device."""
+    B, rounds, options = batch["tokens"].shape[:3]
+    dialog_of_row = option_rows_to_dialog(B, rounds, options)
+    mod = _module(encoder)
+    out = []
+    for s, e in chunk_bounds(B * rounds * options, rows_per_call):
+        tokens, features, spatials, _, segments, _, att, image_mask = _prepare(chunk_item(batch, dialog_of_row, s, e), params)
+        out.append(mod.nsp_scores(tokens, features, spatials, segments, att, image_mask)[1])
+    return torch.cat(out, 0).view(B, rounds, options)
+
+
+@torch.no_grad()
+def evaluate_disc(encoder, dataloader, params, eval_batch_size=None, rows_per_call=200):
+    """evaluate_disc.py:27-118.  mode 'vd_eval_val': the metrics dict (r@1/5/10, mean, mrr, ndcg); any other eval mode
+    ('vd_eval_test'): the ranks_json list.  `eval_batch_size` is kept for the reference's signature: dialogs per batch are read
+    off each batch (the reference's expand needs every batch full)."""
+    mode = params["mode"]
+    sparse, ndcg, ranks_json = SparseGTMetrics(), NDCGBatchSum(), []
+    _module(encoder).eval()
+    for batch in dataloader:
+        output = score_batch(encoder, batch, params, rows_per_call).cpu()
+        if mode == "vd_eval_val":
+            sparse.observe(output, batch["gt_option_inds"])
+            rid = batch["round_id"].squeeze(1)
+            ndcg.observe(output[torch.arange(output.size(0)), rid - 1, :], batch["gt_relevance"])
+        else:
+            ranks = scores_to_ranks(output).squeeze(1)
+            for i in range(output.shape[0]):
+                ranks_json.append({"image_id": batch["image_id"][i].item(), "round_id": int(batch["round_id"][i].item()),
+                                   "ranks": [r.item() for r in ranks[i][:]]})
+    if mode == "vd_eval_val":
+        metrics = {}
+        metrics.update(sparse.retrieve(reset=True))
+        metrics.update(ndcg.retrieve(reset=True))
+        return metrics
+    return ranks_json

@@ -67,3 +67,25 @@ class NDCG(object):
 
     def reset(self):
         self._num, self._den = 0.0, 0.0
+
+
+class NDCGBatchSum(NDCG):
+    """NDCG whose accumulator follows visdial_metrics.py:160-174 to the bit: the per-dialog ratios of one observe() call are
+    summed as fp32 tensors and the numerator stays an fp32 tensor (NDCG above adds Python floats -- the same value to ~1e-8,
+    which is what the generative gate asks; the discriminative evaluation is held to bit equality with the reference)."""
+
+    def observe(self, predicted_scores, target_relevance):
+        ranks = scores_to_ranks(predicted_scores.detach().unsqueeze(1)).squeeze(1)
+        rel = target_relevance.to(ranks.device)
+        k = (rel != 0).sum(-1)
+        rankings = torch.sort(ranks, dim=-1)[1]
+        best = torch.sort(rel, dim=-1, descending=True)[1]
+        ratios = []
+        for b in range(ranks.shape[0]):
+            n = int(k[b])
+            disc = torch.log2(torch.arange(n).float() + 2)
+            dcg = (rel[b][rankings[b][:n]].cpu().float() / disc).sum(-1)
+            ideal = (rel[b][best[b][:n]].cpu().float() / disc).sum(-1)
+            ratios.append(dcg / ideal)
+        self._num = self._num + sum(ratios)
+        self._den += ranks.shape[0]

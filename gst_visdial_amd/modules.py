@@ -1,4 +1,4 @@
-"""Host-side mirror of the reference's module API for the enc_dec_a path.
+"""Host-side mirror of the reference's module API for the enc_dec_a path and for inference of the enc_only_a model.
 
 `VisualDialogEncoder`, `VisualDialogDecoder`, `EncoderDecoderModel`, `VLFusion` keep the constructor and
 forward signatures, return conventions and the `state_dict()` key layout of
@@ -274,7 +274,14 @@ def _check_master_current(engine, what):
 
 
 class VisualDialogEncoder(nn.Module):
-    """models/visual_dialog_encoder.py:7-76.  `params` is held by reference and re-read on every call."""
+    """models/visual_dialog_encoder.py:7-76.  `params` is held by reference and re-read on every call.
+
+    model = 'enc_dec_*': the encoder half of an EncoderDecoderModel (hidden states out).
+    model = 'enc_only_a': the discriminative model of evaluate_disc.py, INFERENCE only.  The module owns an encoder-only engine
+    and `forward` returns the reference's 7-tuple with `seq_relationship_score` [B, 2] fp32 in place 3 and None everywhere
+    else -- including `prediction_scores_t`, the MLM logits over all B*T tokens (6 GB at 200 x 256 x 30522), which the
+    reference computes and its only caller discards (evaluate_disc.py:79): deliberately not computed here.  train_disc.py (the
+    MLM / masked-region / NSP losses, their backward) is out of scope: a train mode or a module in training state raises."""
 
     def __init__(self, params):
         super().__init__()
@@ -285,21 +292,51 @@ class VisualDialogEncoder(nn.Module):
         self.config.__dict__["mode"] = params["mode"]
         self.config.validate()
         self.model_arch = params["model"]
-        if "enc_dec" not in self.model_arch:
-            raise NotImplementedError("gst_visdial_amd implements the enc_dec_* generative path only (model=%r)" % self.model_arch)
+        if "enc_dec" not in self.model_arch and self.model_arch != "enc_only_a":
+            raise NotImplementedError("gst_visdial_amd implements the enc_dec_* generative path and inference of the "
+                                      "discriminative enc_only_a model only (model=%r)" % self.model_arch)
         # the reference calls from_pretrained('bert-base-uncased') (network); here weights come from
         # load_state_dict / a checkpoint, with BERT-style N(0, 0.02) init as the starting point
         self.bert_pretrained = BertForMultiModalPreTraining(self.config)
         self._engine_owner = None
+        self._engine = None
+
+    @property
+    def engine(self):
+        """enc_only_a: the module's own encoder-only engine, built on first use (as EncoderDecoderModel.engine is)."""
+        if self.model_arch != "enc_only_a":
+            raise AttributeError("a VisualDialogEncoder of an enc_dec model runs on its EncoderDecoderModel's engine")
+        if self._engine is None:
+            from .engine import Engine
+            self._engine = Engine(self)
+        return self._engine
 
     def state_dict(self, *args, **kwargs):
         if not kwargs.get("prefix") and not (len(args) > 1 and args[1]):      # (a parent's state_dict() has checked already)
             _check_master_current(getattr(self, "_standalone_engine", None), "model.encoder.state_dict()")
         return super().state_dict(*args, **kwargs)
 
+    def _check_disc_inference(self):
+        mode = self.params["mode"]
+        if "train" in mode or self.training:
+            raise NotImplementedError(
+                "gst_visdial_amd runs the enc_only_a model for inference only (evaluate_disc.py): mode=%r, module.training=%s.  "
+                "train_disc.py -- the MLM, masked-region and NSP losses, their backward and optimizer -- is out of scope; use an "
+                "eval mode and call .eval()" % (mode, self.training))
+
+    def nsp_scores(self, input_ids, image_feat, image_loc, token_type_ids=None, attention_mask=None, image_attention_mask=None):
+        """enc_only_a: (seq_relationship_score [B, 2], softmax(score, 1)[:, 0] [B]), both fp32, the second straight from the
+        head kernel -- what evaluate_disc.py:81-83 ranks the answer options by."""
+        self._check_disc_inference()
+        return self.engine.nsp_scores(image_feat, image_loc, image_attention_mask, input_ids, token_type_ids, attention_mask)
+
     def forward(self, input_ids, image_feat, image_loc, sep_indices=None, token_type_ids=None, attention_mask=None,
                 masked_lm_labels=None, next_sentence_label=None, image_attention_mask=None, image_label=None,
                 image_target=None):
+        if self.model_arch == "enc_only_a":
+            # eval branch of models/visual_dialog_encoder.py:68-76; sep_indices / masked_lm_labels feed nothing in it
+            score, _ = self.nsp_scores(input_ids, image_feat, image_loc, token_type_ids, attention_mask, image_attention_mask)
+            return (None, None, None, score, None, None, None)
         from .engine import standalone_encoder_forward
         enc_t, enc_v = standalone_encoder_forward(self, input_ids, image_feat, image_loc, token_type_ids, attention_mask,
                                                   image_attention_mask)

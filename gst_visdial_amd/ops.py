@@ -797,6 +797,47 @@ def answer_scores(logits, lse, dec_ids, rows, U, scores):
                                                            dt(logits), _p(scores), _stream()))
 
 
+FUSION = {"mul": 0, "sum": 1}
+
+
+def nsp_head(xt, t_rows, xv, v_rows, wt, bt, wv, bv, wn, bn, B, fusion, z, prob0):
+    """NSP scores of the enc_only model in one launch (gstvd_nsp_head): row 0 of every batch row of the encoder's final
+    activations xt [B * t_rows, H] / xv [B * v_rows, Hv] (read in place, row strides taken from the tensors) -> poolers
+    wt [Hb, H], wv [Hb, Hv] (dtype of the activations) with fp32 biases -> `fusion` ('mul' | 'sum') -> wn [2, Hb], bn [2] in
+    fp32 -> z [B, 2] fp32 and prob0 [B] fp32 = softmax(z, 1)[:, 0]."""
+    lib = L.load()
+    if fusion not in FUSION:
+        raise L.GstvdError("nsp_head: fusion_method must be 'mul' or 'sum', got %r" % (fusion,))
+    if wt.dtype != xt.dtype or wv.dtype != xt.dtype or xv.dtype != xt.dtype:
+        raise L.GstvdError("nsp_head: activations and pooler weights must share one dtype")
+    for t in (bt, bv, wn, bn, z, prob0):
+        if t.dtype != torch.float32:
+            raise L.GstvdError("nsp_head: biases, the classifier and the outputs are fp32")
+    if xt.shape[0] < B * t_rows or xv.shape[0] < B * v_rows or z.shape[0] < B or prob0.shape[0] < B or prob0.stride(0) != 1 \
+            or z.stride(-1) != 1 or xt.stride(-1) != 1 or xv.stride(-1) != 1 or wt.stride(-1) != 1 or wv.stride(-1) != 1 \
+            or wn.stride(-1) != 1 or bt.numel() != wt.shape[0] or bv.numel() != wt.shape[0] or wv.shape[0] != wt.shape[0] \
+            or tuple(wn.shape) != (2, wt.shape[0]) or bn.numel() != 2:
+        raise L.GstvdError("nsp_head: operand shapes do not match")
+    d = L.NspHeadDesc()
+    d.xt, d.ldt, d.t_rows = _p(xt), xt.stride(0), t_rows
+    d.xv, d.ldv, d.v_rows = _p(xv), xv.stride(0), v_rows
+    d.wt, d.ldwt, d.wv, d.ldwv = _p(wt), wt.stride(0), _p(wv), wv.stride(0)
+    d.bt, d.bv, d.wn, d.ldwn, d.bn = _p(bt), _p(bv), _p(wn), wn.stride(0), _p(bn)
+    d.z, d.ldz, d.prob0 = _p(z), z.stride(0), _p(prob0)
+    d.B, d.H, d.Hv, d.Hb = B, wt.shape[1], wv.shape[1], wt.shape[0]
+    d.dtype, d.fusion = dt(xt), FUSION[fusion]
+    e0 = _prof_begin()
+    buf = C.create_string_buffer(256) if e0 is not None else None
+    if buf is not None:
+        d.kernel_name, d.kernel_name_len = C.addressof(buf), 256
+    L.check("gstvd_nsp_head", lib.gstvd_nsp_head(C.byref(d), _stream()))
+    if e0 is not None:          # keyed by the symbol the call itself reports having launched
+        H, Hv, Hb = d.H, d.Hv, d.Hb
+        _prof_end(e0, "nsp_head:" + buf.value.decode(), 2.0 * B * Hb * (H + Hv + 2),
+                  float(Hb * (H + Hv) * wt.element_size() + B * (H + Hv) * xt.element_size() + B * 12), (B, H, Hv, Hb))
+    return z, prob0
+
+
 def vl_split(d_enc, B, R, T, H, d_v, d_t, p, site_v, site_t, rng):
     lib = L.load()
     L.check("gstvd_vl_split", lib.gstvd_vl_split(_p(d_enc), B, R, T, H, dt(d_enc), _p(d_v), _p(d_t), p, site_v, site_t,

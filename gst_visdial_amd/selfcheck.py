@@ -130,3 +130,30 @@ def dropout_keep_masks(engine):
             m = m[..., :s["Lk"]]
         out[label] = (m != 0).cpu()
     return out
+
+
+def build_tiny_disc_encoder(precision="fp32", device=None, mode="vd_eval_val", cfg_file="tiny_cfg.json", fixture="tiny_disc.npz",
+                            **extra_params):
+    """The enc_only_a encoder of tests/golden/tiny_disc.npz (tools/make_golden_disc.py): -> (encoder in eval state, params,
+    fixture).  `device` None: left on the CPU (construction / state-dict checks need no GPU)."""
+    from .modules import VisualDialogEncoder
+    with open(os.path.join(GOLDEN, cfg_file)) as f:
+        cfg = json.load(f)
+    d = tempfile.mkdtemp(prefix="gstvd_cfg_")
+    with open(os.path.join(d, "enc.json"), "w") as f:
+        json.dump(cfg["enc"], f)
+    params = dict(model_enc_config=os.path.join(d, "enc.json"), gpu_ids=[0], model="enc_only_a", mode=mode, batch_size=1,
+                  device=torch.device(device if device is not None else "cpu"), amd_precision=precision)
+    params.update(extra_params)
+    fx = load_npz(fixture)
+    enc = VisualDialogEncoder(params)
+    enc.load_state_dict({k[len("state::"):]: v for k, v in fx.items() if k.startswith("state::")}, strict=True)
+    enc.eval()
+    if device is not None:
+        enc = enc.to(device)
+    return enc, params, fx
+
+
+def disc_batch(fx):
+    """The fixture's batch in the disc eval dataloader's layout (per-dialog image tensors, [B, rounds, options, L] text tensors)."""
+    return {k[4:]: v.clone() for k, v in fx.items() if k.startswith("in::")}

@@ -360,6 +360,31 @@ int32_t gstvd_gemm_group_caps(void);
 int gstvd_gemm_kernel_name(const gstvd_gemm_t* g, int32_t splits, char* buf, int32_t buf_len);
 int gstvd_gemm_grouped_kernel_name(int32_t dtype_in, int32_t dtype_out, int32_t a_kmajor, int32_t b_kmajor, char* buf, int32_t buf_len);
 
+/* ---- (ABI 9) NSP head of the discriminative enc_only model: poolers + fusion + bi_seq_relationship + 2-way softmax ------------
+ * What evaluate_disc.py:79-83 ranks by, in ONE launch on the encoder's final activations:
+ *   t0 = xt[b * t_rows * ldt + 0 .. H),  v0 = xv[b * v_rows * ldv + 0 .. Hv)       first token / region of batch row b, read in
+ *                                                                                  place (models/vilbert_dialog.py:924,938)
+ *   pt = relu(Wt t0 + bt),  pv = relu(Wv v0 + bv)                                  BertTextPooler / BertImagePooler, :915-941
+ *   f  = pt * pv  (fusion 0, 'mul')  or  pt + pv  (fusion 1, 'sum')                BertPreTrainingHeads.forward, :1030-1033
+ *                                                                                  (its Dropout is the identity in eval)
+ *   z  = Wn f + bn                    -> z[b * ldz + 0..1], fp32                   cls.bi_seq_relationship, :1038
+ *   prob0 = exp(z0 - m) / (exp(z0 - m) + exp(z1 - m)), m = max(z0, z1)  -> prob0[b]  F.softmax(.., 1)[:, 0], evaluate_disc.py:81-83
+ * dtype = type of xt, xv, wt [Hb, ldwt >= H], wv [Hb, ldwv >= Hv]: GSTVD_BF16 (fp32 accumulation on the MFMA) or GSTVD_F32 (the
+ * f32-input MFMA).  bt, bv [Hb], wn [2, ldwn >= Hb], bn [2] are fp32 in both; pt, pv and f never leave fp32 registers.
+ * One workgroup owns 16 batch rows and all Hb columns: no cross-workgroup reduction, sums in a fixed order, bit-reproducible.
+ * Constraints: B >= 1; H, Hv, Hb multiples of 16 and <= 1024; row strides multiples of 8 (bf16) / 4 (fp32) elements; every
+ * pointer 16-byte aligned.  kernel_name (HOST pointer or NULL): receives the mangled symbol of the kernel the call launched. */
+typedef struct {
+  const void* xt; int64_t ldt; int64_t t_rows;
+  const void* xv; int64_t ldv; int64_t v_rows;
+  const void* wt; int64_t ldwt; const void* wv; int64_t ldwv;
+  const float* bt; const float* bv; const float* wn; int64_t ldwn; const float* bn;
+  float* z; int64_t ldz; float* prob0;
+  int32_t B, H, Hv, Hb, dtype, fusion;
+  char* kernel_name; int32_t kernel_name_len; int32_t reserved_;
+} gstvd_nsp_head_t;
+int gstvd_nsp_head(const gstvd_nsp_head_t* a, gstvd_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
