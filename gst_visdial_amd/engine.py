@@ -7,12 +7,8 @@ Replaces, for the modules of `modules.py`, the eager PyTorch arithmetic of
 and autograd's backward of all of it (train_gen.py:324) by a fixed schedule of HIP kernels called through
 the C ABI (`ops`).  Design points:
 
-  * parameters live in ONE flat fp32 buffer `P` (forward order), gradients in one flat fp32 buffer `G`,
-    bf16 shadow weights (throughput mode) in one flat bf16 buffer `S`; the nn.Parameters are views.
-    Q/K/V (and the co-attention / cross-attention K,V of all decoder layers) are laid out contiguously
-    so each projection group is ONE GEMM, and a data-parallel all-reduce is a handful of large slices;
-  * activations come from a bump arena that is rewound every step -> static addresses (hipGraph friendly),
-    no allocator traffic; nothing of size [Lq, Lk] is ever stored (attention saves only LSE);
+  * parameters, gradients and bf16 shadow weights live in flat buffers, activations in a bump arena that is rewound
+    every step (storage.py: `FlatParams`, `Arena`, `Act`);
   * forward records a tape of backward closures; backward replays it in reverse.  Residual gradients are
     accumulated in the dgrad GEMM epilogue, GELU' in the dgrad epilogue, bias gradients come out of the
     LayerNorm backward partial sums; dropout masks are regenerated from (seed, step, site, index);
@@ -22,6 +18,7 @@ the C ABI (`ops`).  Design points:
 
 Numerics: precision 'fp32' runs every GEMM on the exact-fp32 MFMA (parity gate: logits within 1e-4 of the
 oracle); 'bf16' stores activations/weights in bf16 with fp32 accumulation and fp32 LN/softmax/CE statistics.
+The sampling decode (`sample`, `rescore_sampled`) is engine_decode.py.
 """
 import os
 import weakref
@@ -29,310 +26,13 @@ import weakref
 import torch
 
 from . import ops
-from . import _lib as _libmod
 from .config import encoder_schedule
+from .engine_decode import DecodeMixin
+from .storage import Act, Arena, FlatParams
 from ._lib import GstvdError, EPI_GELU, EPI_DGELU, LN_RESID, LN_EMBED, LN_IMAGE
 
 
 EARLY_WGRAD = 1     # 0 (tests / tools patch the attribute): the final grouped weight-gradient launch waits for the embedding backward
-
-
-def _round_up(x, m):
-    return (x + m - 1) // m * m
-
-
-class Act(object):
-    """An activation [M, N] in the arena plus (during backward) its gradient."""
-    __slots__ = ("t", "g", "M", "N", "gelu_aux", "bias_done", "prod", "dgrad_done")
-
-    def __init__(self, t, M, N):
-        self.t, self.g, self.M, self.N = t, None, M, N
-        self.gelu_aux, self.bias_done = None, False
-        self.prod, self.dgrad_done = None, False      # the Linear that produced it (input, weight, K_in, need_dx); see _ln_bwd
-
-
-class Arena(object):
-    """Bump allocator over large device chunks; `reset()` rewinds, so a fixed call sequence gets fixed addresses
-    (hipGraph friendly).  The request sequence of a step is identical from step to step, so the tensor views are
-    memoised by sequence index: steady-state allocation is a list lookup, no tensor construction."""
-
-    _ESZ = {torch.float32: 4, torch.bfloat16: 2, torch.int64: 8, torch.uint8: 1, torch.int32: 4}
-
-    def __init__(self, device, chunk_bytes=1 << 28):
-        self.device, self.chunk_bytes = device, chunk_bytes
-        self.chunks, self.ci, self.off = [], 0, 0
-        self.memo, self.seq = [], 0
-
-    def reset(self):
-        self.ci, self.off, self.seq = 0, 0, 0
-
-    def rewind(self, mark):
-        """Back to a position returned by `mark()` (decode loops reuse the same scratch every step)."""
-        self.ci, self.off, self.seq = mark
-
-    def mark(self):
-        return (self.ci, self.off, self.seq)
-
-    def alloc(self, numel, dtype, shape=None):
-        nbytes = _round_up(numel * self._ESZ[dtype], 256)
-        i = self.seq
-        self.seq = i + 1
-        if i < len(self.memo):
-            m = self.memo[i]
-            if m[0] == numel and m[1] is dtype and m[2] == shape and m[3] == self.ci and m[4] == self.off:
-                self.ci, self.off = m[5], m[6]
-                return m[7]
-            del self.memo[i:]                 # the sequence diverged (different shapes): rebuild from here
-        ci0, off0 = self.ci, self.off
-        while True:
-            if self.ci >= len(self.chunks):
-                self.chunks.append(torch.empty(max(self.chunk_bytes, nbytes), dtype=torch.uint8, device=self.device))
-            c = self.chunks[self.ci]
-            if self.off + nbytes <= c.numel():
-                out = c[self.off:self.off + nbytes].view(dtype)[:numel]
-                if shape is not None:
-                    out = out.view(shape)
-                self.off += nbytes
-                self.memo.append((numel, dtype, shape, ci0, off0, self.ci, self.off, out))
-                return out
-            self.ci, self.off = self.ci + 1, 0
-
-
-class FlatParams(object):
-    """Flat storage plan.  `slots[name] = (offset, shape)` are engine views (possibly fused groups of several
-    nn.Parameters); every live nn.Parameter becomes a view of `P` and its `.grad` a view of `G`."""
-
-    def __init__(self, model, precision):
-        # `model`: an EncoderDecoderModel, or (encoder-only form) a VisualDialogEncoder of the discriminative enc_only arch
-        self.enc_only = not hasattr(model, "decoder")
-        encoder = model if self.enc_only else model.encoder
-        enc_cfg = encoder.config
-        bert = encoder.bert_pretrained.bert
-        self.slots, self.items, self.pads = {}, [], []
-        self.placed = {}
-        self.off = 0
-        H, Hv, Hb = enc_cfg.hidden_size, enc_cfg.v_hidden_size, enc_cfg.bi_hidden_size
-        if self.enc_only:
-            dec_cfg = gen = lm_w = None       # no decoder slots, no LM head: the word table keeps its own row count
-            self.Vp = 0
-        else:
-            dec_cfg = model.decoder.config
-            gen = model.decoder.decoder
-            V = dec_cfg.vocab_size
-            self.Vp = _round_up(V, 64)
-            lm_w = gen.lm_head.decoder.weight
-
-        def place(name, params, shape=None, pad_rows_to=None):
-            """Lay `params` out back to back under one fused slot `name`."""
-            self.off = _round_up(self.off, 64)
-            start = self.off
-            for p in params:
-                if id(p) in self.placed:
-                    raise GstvdError("parameter shared between two fused groups: " + name)
-                self.placed[id(p)] = self.off
-                self.items.append((p, self.off))
-                self.off += p.numel()
-            if pad_rows_to is not None:
-                cols = params[0].shape[1] if params[0].dim() == 2 else 1
-                want = pad_rows_to * cols
-                self.pads.append((self.off, start + want))
-                self.off = start + want
-            n = self.off - start
-            if shape is None:
-                shape = tuple(params[0].shape) if len(params) == 1 and pad_rows_to is None else (n,)
-            self.slots[name] = (start, shape)
-
-        def emb(prefix, mod):
-            w = mod.word_embeddings.weight
-            place(prefix + ".word", [w], shape=(self.Vp if w is lm_w else w.shape[0], w.shape[1]),
-                  pad_rows_to=self.Vp if w is lm_w else None)
-            place(prefix + ".pos", [mod.position_embeddings.weight])
-            place(prefix + ".tt", [mod.token_type_embeddings.weight])
-            place(prefix + ".tte", [mod.token_type_embeddings_extension.weight])
-            place(prefix + ".ln.w", [mod.LayerNorm.weight])
-            place(prefix + ".ln.b", [mod.LayerNorm.bias])
-
-        def attn_out_ffn(p, lay, hid, inter):
-            place(p + ".ao.w", [lay.attention.output.dense.weight]); place(p + ".ao.b", [lay.attention.output.dense.bias])
-            place(p + ".ln1.w", [lay.attention.output.LayerNorm.weight]); place(p + ".ln1.b", [lay.attention.output.LayerNorm.bias])
-
-        def ffn(p, inter_mod, out_mod, tag_i, tag_o, tag_ln):
-            place(p + tag_i + ".w", [inter_mod.dense.weight]); place(p + tag_i + ".b", [inter_mod.dense.bias])
-            place(p + tag_o + ".w", [out_mod.dense.weight]); place(p + tag_o + ".b", [out_mod.dense.bias])
-            place(p + tag_ln + ".w", [out_mod.LayerNorm.weight]); place(p + tag_ln + ".b", [out_mod.LayerNorm.bias])
-
-        def qkv(p, tag, q, k, v, hid_out, hid_in):
-            place(p + tag + ".w", [q.weight, k.weight, v.weight], shape=(3 * hid_out, hid_in))
-            place(p + tag + ".b", [q.bias, k.bias, v.bias], shape=(3 * hid_out,))
-
-        def bert_layer(p, lay, hid, inter):
-            s = lay.attention.self
-            qkv(p, ".qkv", s.query, s.key, s.value, hid, hid)
-            attn_out_ffn(p, lay, hid, inter)
-            ffn(p, lay.intermediate, lay.output, ".fi", ".fo", ".ln2")
-
-        self.enc_emb = bert.embeddings
-        self.dec_emb = None if self.enc_only else gen.bert.embeddings
-        emb("emb", self.enc_emb)
-        ve = bert.v_embeddings
-        place("vemb.img.w", [ve.image_embeddings.weight]); place("vemb.img.b", [ve.image_embeddings.bias])
-        place("vemb.loc.w", [ve.image_location_embeddings.weight]); place("vemb.loc.b", [ve.image_location_embeddings.bias])
-        place("vemb.ln.w", [ve.LayerNorm.weight]); place("vemb.ln.b", [ve.LayerNorm.bias])
-        self.marks = {}
-        for kind, i in encoder_schedule(enc_cfg):
-            self.marks[(kind, i)] = _round_up(self.off, 64)
-            if kind == "t":
-                bert_layer("t%d" % i, bert.encoder.layer[i], H, enc_cfg.intermediate_size)
-            elif kind == "v":
-                bert_layer("v%d" % i, bert.encoder.v_layer[i], Hv, enc_cfg.v_intermediate_size)
-            else:
-                c, p = bert.encoder.c_layer[i], "c%d" % i
-                b = c.biattention
-                qkv(p, ".qkv1", b.query1, b.key1, b.value1, Hb, Hv)
-                qkv(p, ".qkv2", b.query2, b.key2, b.value2, Hb, H)
-                o = c.biOutput
-                place(p + ".d1.w", [o.dense1.weight]); place(p + ".d1.b", [o.dense1.bias])
-                place(p + ".ln1.w", [o.LayerNorm1.weight]); place(p + ".ln1.b", [o.LayerNorm1.bias])
-                place(p + ".d2.w", [o.dense2.weight]); place(p + ".d2.b", [o.dense2.bias])
-                place(p + ".ln2.w", [o.LayerNorm2.weight]); place(p + ".ln2.b", [o.LayerNorm2.bias])
-                ffn(p, c.v_intermediate, c.v_output, ".vfi", ".vfo", ".vln")
-                ffn(p, c.t_intermediate, c.t_output, ".tfi", ".tfo", ".tln")
-        if self.enc_only:
-            # the NSP head (models/vilbert_dialog.py:915-941,1038) is live here; cls.predictions.*, cls.imagePredictions.*,
-            # sep_embeddings and q_dense* stay in the dead buffer, as in the enc_dec form
-            cls = encoder.bert_pretrained.cls
-            self.marks["nsp"] = _round_up(self.off, 64)
-            place("pool.t.w", [bert.t_pooler.dense.weight]); place("pool.t.b", [bert.t_pooler.dense.bias])
-            place("pool.v.w", [bert.v_pooler.dense.weight]); place("pool.v.b", [bert.v_pooler.dense.bias])
-            place("nsp.w", [cls.bi_seq_relationship.weight]); place("nsp.b", [cls.bi_seq_relationship.bias])
-            self._finish(model, precision)
-            return
-        self.marks["vlf"] = _round_up(self.off, 64)
-        place("vlf.v.w", [model.vlfusion.fc_v.weight]); place("vlf.v.b", [model.vlfusion.fc_v.bias])
-        place("vlf.l.w", [model.vlfusion.fc_l.weight]); place("vlf.l.b", [model.vlfusion.fc_l.bias])
-        self.marks["dec"] = _round_up(self.off, 64)
-        if self.dec_emb is not self.enc_emb:
-            emb("demb", self.dec_emb)
-        layers = gen.bert.encoder.layer
-        Hd, L = dec_cfg.hidden_size, len(layers)
-        kvw, kvb = [], []
-        for lay in layers:
-            cs = lay.crossattention.self
-            kvw += [cs.key.weight, cs.value.weight]
-            kvb += [cs.key.bias, cs.value.bias]
-        place("dec.ckv.w", kvw, shape=(2 * L * Hd, Hd))
-        place("dec.ckv.b", kvb, shape=(2 * L * Hd,))
-        for i, lay in enumerate(layers):
-            p = "d%d" % i
-            self.marks[("d", i)] = _round_up(self.off, 64)
-            s = lay.attention.self
-            qkv(p, ".qkv", s.query, s.key, s.value, Hd, Hd)
-            attn_out_ffn(p, lay, Hd, dec_cfg.intermediate_size)
-            c = lay.crossattention
-            place(p + ".cq.w", [c.self.query.weight]); place(p + ".cq.b", [c.self.query.bias])
-            place(p + ".co.w", [c.output.dense.weight]); place(p + ".co.b", [c.output.dense.bias])
-            place(p + ".ln2.w", [c.output.LayerNorm.weight]); place(p + ".ln2.b", [c.output.LayerNorm.bias])
-            ffn(p, lay.intermediate, lay.output, ".fi", ".fo", ".ln3")
-        self.marks["lm"] = _round_up(self.off, 64)
-        if id(lm_w) in self.placed:
-            wname = "emb.word" if lm_w is self.enc_emb.word_embeddings.weight else "demb.word"
-            self.slots["lm.w"] = self.slots[wname]
-        else:
-            place("lm.w", [lm_w], shape=(self.Vp, lm_w.shape[1]), pad_rows_to=self.Vp)
-        place("lm.b", [gen.lm_head.bias], shape=(self.Vp,), pad_rows_to=self.Vp)
-        self._finish(model, precision)
-
-    def _finish(self, model, precision):
-        self.n_live = _round_up(self.off, 64)
-        self.live = [p for p, _ in self.items]
-        live_ids = set(id(p) for p in self.live)
-        self.dead = [p for p in model.parameters() if id(p) not in live_ids]
-        self.precision = precision
-        self.P = self.G = self.S = self.D = None
-        self.stale_guard = None       # callable -> True while fp32 masters of other ranks' shards are old (set by the engine)
-
-    # -- materialise on the device the parameters currently live on ------------------------------------
-    def materialize(self, device):
-        P = torch.zeros(self.n_live, dtype=torch.float32, device=device)
-        for p, off in self.items:
-            P[off:off + p.numel()].copy_(p.data.reshape(-1))
-        nd = sum(p.numel() for p in self.dead)
-        D = torch.empty(max(nd, 1), dtype=torch.float32, device=device)
-        o = 0
-        for p in self.dead:
-            D[o:o + p.numel()].copy_(p.data.reshape(-1))
-            p.data = D[o:o + p.numel()].view(p.shape)
-            o += p.numel()
-        for p, off in self.items:
-            p.data = P[off:off + p.numel()].view(p.shape)
-        self.P, self.D = P, D
-        # (encoder-only form: inference only -- no gradient buffer, no gradient views)
-        self.G = None if self.enc_only else torch.zeros(self.n_live, dtype=torch.float32, device=device)
-        self.S = torch.empty(self.n_live, dtype=torch.bfloat16, device=device) if self.precision == "bf16" else None
-        self.grad_views = [] if self.enc_only else [self.G[off:off + p.numel()].view(p.shape) for p, off in self.items]
-        self.ptrs = [(p, P[off:off + p.numel()].data_ptr()) for p, off in self.items]
-        self.shadow_version = None
-        self.device = device
-
-    def is_materialized(self):
-        if self.P is None:
-            return False
-        for p, ptr in self.ptrs:
-            if p.data_ptr() != ptr:
-                return False
-        return True
-
-    def version(self):
-        return sum(p._version for p in self.live)
-
-    def refresh_shadow(self, force=False):
-        if self.S is None:
-            return
-        v = self.version()
-        if force or v != self.shadow_version:
-            if self.shadow_version is not None and self.stale_guard is not None and self.stale_guard():
-                # sharded optimizer (pipeline.BackwardPipeline(shard_update=True)): P holds current master weights only for this
-                # rank's shards, S holds the freshly GATHERED shadows of all of them -- a re-cast would replace other ranks' current
-                # bf16 weights by this rank's old masters and the ranks would diverge silently
-                from ._lib import GstvdError
-                raise GstvdError("a parameter was modified in place while the optimizer is sharded over the ranks: the bf16 shadow "
-                                 "weights cannot be re-derived from this rank's fp32 masters (current only for its own shards).  "
-                                 "Call pipe.sync_master() on EVERY rank before editing parameters.")
-            ops.cast(self.P, self.S)
-            self.shadow_version = v
-
-    def fp32_read_ranges(self):
-        """Sorted, disjoint flat ranges [x, y) whose fp32 values the forward reads directly (Engine.Pv: biases, LayerNorm gain /
-        bias, the embedding tables, the image-location projection) -- everything in [0, n_live) that is not EXCLUSIVELY a GEMM
-        weight (Engine.W: read from the bf16 shadow buffer in bf16 mode).  pipeline.BackwardPipeline(shard_update=True) gathers
-        these in fp32; the GEMM weights only travel as bf16 shadows."""
-        def numel(shape):
-            n = 1
-            for d in shape:
-                n *= d
-            return n
-        non_gemm = ("ln.w", "ln1.w", "ln2.w", "ln3.w", "vln.w", "tln.w", "vemb.loc.w", "nsp.w")
-        by_start = {}
-        for name, (off, shape) in self.slots.items():
-            gemm = name.endswith(".w") and not name.endswith(non_gemm)
-            by_start.setdefault((off, numel(shape)), []).append(gemm)
-        shadow_only = sorted(k for k, flags in by_start.items() if all(flags))      # (the tied LM head aliases an embedding table: not all)
-        out, pos = [], 0
-        for off, n in shadow_only:
-            if off > pos:
-                out.append((pos, off))
-            pos = max(pos, off + n)
-        if pos < self.n_live:
-            out.append((pos, self.n_live))
-        return out
-
-    def view(self, buf, name):
-        off, shape = self.slots[name]
-        n = 1
-        for s in shape:
-            n *= s
-        return buf[off:off + n].view(shape)
-
 
 _DEVICE_STREAMS = {}
 
@@ -349,7 +49,7 @@ def device_streams(device):
     return _DEVICE_STREAMS[key]
 
 
-class Engine(object):
+class Engine(DecodeMixin):
     def __init__(self, model):
         # weak: the model owns the engine, not the other way round -- no reference cycle, so dropping the model frees the
         # flat buffers, the arena and any captured decode sessions by reference counting, not at some later GC pass
@@ -374,6 +74,7 @@ class Engine(object):
         self.rng = None
         self._decode_sessions = {}
         self._last_decode = None
+        self._early, self._early_fused = False, ()
         self.anchor = None
         self._emb_span_ok = {}
         self.pipe = None               # BackwardPipeline (pipeline.py): slice-wise wgrad / all-reduce / AdamW on the aux stream
@@ -407,6 +108,14 @@ class Engine(object):
         new._setup(weakref.ref(owner), copy.deepcopy(self.enc_cfg, memo), copy.deepcopy(self.dec_cfg, memo),
                    copy.deepcopy(orig.params, memo))      # (dec_cfg is None for the encoder-only form, and stays None)
         return new
+
+    @staticmethod
+    def _fused_sampling(P, vocab):
+        """The fused sampling kernel covers the reference's settings (generate.py:138-141,177-180: top_k 7, top_p 0; BERT's
+        30522-token vocabulary) and, since ABI 6, any top_k and top_p; only a vocabulary beyond one CU's LDS takes the torch-op
+        form of the filters, issued eagerly step by step (no captured token graph).  (Defined on Engine, not in DecodeMixin, which
+        reaches it through `self`: a test swaps it on this class.)"""
+        return vocab <= ops.SAMPLE_MAX_VOCAB        # (any top_k, any top_p: both filters run inside the sampling launch since ABI 6)
 
     def close(self):
         """Drop captured decode sessions (hipGraphs + their private pool) now."""
@@ -528,10 +237,7 @@ class Engine(object):
             return
         if any(self.wgrads.pending_into(self.Gv[n]) for n in ("emb.word", "emb.pos", "emb.tt", "emb.tte") if n in self.Gv):
             return      # a queued GEMM writes a table the embedding's backward is about to add into (tied LM head): keep the order
-        for src in (self.main, self.side):
-            ev = torch.cuda.Event()
-            ev.record(src)
-            self.aux.wait_event(ev)
+        self._wait_for(self.aux, self.main, self.side)
         with torch.cuda.stream(self.aux):
             self._early_fused = self.wgrads.flush(fuse=p.fuse_handle())
         self._early = True
@@ -547,7 +253,7 @@ class Engine(object):
 
     def _emit(self, off):
         """Hand the finished slice [off, pipe.hi) to the backward pipeline on the auxiliary stream."""
-        if getattr(self.pipe, "segmenter", None) is not None:
+        if self.pipe.segmenter is not None:
             # Segmented capture (graph.SegmentedStep: the fall-back when a whole-step capture WITH its collectives is refused): the
             # slice's collective is issued eagerly BETWEEN two captured graphs, so the capture is cut here.  A capture can only end
             # with every forked stream joined into its origin: the vision stream joins, the slice's weight gradients and column
@@ -557,9 +263,7 @@ class Engine(object):
             if self.use_streams:
                 self._wait("t", "v")
                 if self.aux_busy:
-                    ev = torch.cuda.Event()
-                    ev.record(self.aux)
-                    self.main.wait_event(ev)
+                    self._wait_for(self.main, self.aux)
                     self.aux_busy = False
             fused, direct = self._flush_wgrads()
             self.colsums.flush()
@@ -567,24 +271,7 @@ class Engine(object):
             if self.use_streams:
                 self._wait("v", "t")
             return
-        for src in ([self.main, self.side] if self.use_streams else [self.main]):
-            ev = torch.cuda.Event()
-            ev.record(src)
-            self.aux.wait_event(ev)
-        if off == 0 and self.use_streams and getattr(self, "_early", False):
-            # the grouped launch is already running (see _early_final_wgrads); a GEMM queued after it (none in this model) goes plain
-            self._early = False
-            fused = self._early_fused
-            with torch.cuda.stream(self.aux):
-                self.wgrads.flush()
-            self.colsums.flush()
-            ev = torch.cuda.Event()
-            ev.record(self.main)
-            self.aux.wait_event(ev)
-            with torch.cuda.stream(self.aux):
-                self.pipe.run_slice(off, self.pipe.hi, fused=fused)
-            self.aux_busy = True
-            return
+        self._wait_for(self.aux, *((self.main, self.side) if self.use_streams else (self.main,)))
         if off == 0 and self.use_streams:
             # the last slice, after backward's last kernel: the main stream has nothing left to do, so the slice's column
             # reductions run there, beside its grouped weight-gradient launch on the auxiliary stream (which then waits for them).
@@ -592,13 +279,17 @@ class Engine(object):
             # j+1, also with the weight-gradient launch confined to 160-224 CUs: 13.73-14.01 ms against 13.72 ms, resp. +0.3 ms --
             # the two full-chip kernels do not share the chip profitably; profiles/r03_chunk_sweep.txt.  Not kept.)
             with torch.cuda.stream(self.aux):
-                fused, direct = self._flush_wgrads()
+                if self._early:
+                    # the grouped launch is already running (see _early_final_wgrads); a GEMM queued after it (none in this model) goes plain
+                    self._early = False
+                    self.wgrads.flush()
+                    fused, direct = self._early_fused, ()
+                else:
+                    fused, direct = self._flush_wgrads()
             # (issuing these reductions from the vision stream instead does not let the grouped launch start earlier:
-            # 12.30 / 12.34 vs 12.31 / 12.35 ms, tools/r05_s14.sh)
+            # 12.30 / 12.34 vs 12.31 / 12.35 ms, tools/attic/r05_s14.sh)
             self.colsums.flush()
-            ev = torch.cuda.Event()
-            ev.record(self.main)
-            self.aux.wait_event(ev)
+            self._wait_for(self.aux, self.main)
             with torch.cuda.stream(self.aux):
                 self.pipe.run_slice(off, self.pipe.hi, fused=fused, direct=direct)
         else:
@@ -631,9 +322,7 @@ class Engine(object):
     def _flush_aux(self):
         """Run the queued (decoder + LM head) weight-gradient group and column reductions on a third stream so they
         overlap the encoder's backward chain; joined back before the final flush."""
-        ev = torch.cuda.Event()
-        ev.record(self.main)
-        self.aux.wait_event(ev)
+        self._wait_for(self.aux, self.main)
         with torch.cuda.stream(self.aux):
             self.wgrads.flush()
             self.colsums.flush()
@@ -642,11 +331,17 @@ class Engine(object):
     def _stream_of(self, tag):
         return self.side if tag == "v" else self.main
 
+    @staticmethod
+    def _wait_for(dst, *srcs):
+        """Stream `dst` waits for everything queued so far on the streams `srcs` (one event per source, in the given order)."""
+        for src in srcs:
+            ev = torch.cuda.Event()
+            ev.record(src)
+            dst.wait_event(ev)
+
     def _wait(self, waiter, waitee):
-        """Stream `waiter` waits for everything queued so far on stream `waitee`."""
-        ev = torch.cuda.Event()
-        ev.record(self._stream_of(waitee))
-        self._stream_of(waiter).wait_event(ev)
+        """The same by stream tag ("t" = main, "v" = vision)."""
+        self._wait_for(self._stream_of(waiter), self._stream_of(waitee))
 
     def sync(self, waiter, waitee):
         """Forward dependency (ops on `waiter` after this point read results of `waitee`); backward mirrors it."""
@@ -987,6 +682,11 @@ class Engine(object):
         self._lin_bwd(xv, yv, "vlf.v.w", "vlf.v.b", H, Hv, True)
         self._lin_bwd(xt, yt, "vlf.l.w", "vlf.l.b", H, H, True)
 
+    def _cross_kv(self, enc):
+        """The cross-attention K/V projection of ALL decoder layers over the encoder states: one GEMM, [rows, 2 * L * H]."""
+        c = self.dec_cfg
+        return self.lin(enc, "dec.ckv.w", "dec.ckv.b", 2 * c.num_hidden_layers * c.hidden_size, c.hidden_size)
+
     def decoder(self, enc, I, kv=None, kv_group=1):
         """BertGenerationEncoder + HF BertEncoder (self-attn -> cross-attn -> FFN, post-LN) + LM head.
         kv_group > 1 (inference): `kv_group` consecutive decoder rows attend to the same encoder row."""
@@ -998,18 +698,16 @@ class Engine(object):
         self.mark("dec")
         if self.rec and self.use_streams and self.pipe is None:
             self.tape.append(("t", self._flush_aux))      # backward: the decoder's gradients are complete here
-        kv_on_side = False
-        if kv is None:
-            if self.use_streams:
-                # the cross-attention K/V of all layers (one 4688 x 18432 x 768 GEMM, 0.19 ms; its input gradient as much) goes
-                # to the side stream, idle since the encoder joined: it runs beside the decoder's embedding and the first layer's
-                # self-attention sub-layer, and in backward its input gradient beside what is left of the decoder's backward
-                self.sync("v", "t")
-                with self.on("v"):
-                    kv = self.lin(enc, "dec.ckv.w", "dec.ckv.b", 2 * L * H, H)
-                kv_on_side = True
-            else:
-                kv = self.lin(enc, "dec.ckv.w", "dec.ckv.b", 2 * L * H, H)
+        kv_on_side = kv is None and self.use_streams
+        if kv_on_side:
+            # the cross-attention K/V of all layers (one 4688 x 18432 x 768 GEMM, 0.19 ms; its input gradient as much) goes
+            # to the side stream, idle since the encoder joined: it runs beside the decoder's embedding and the first layer's
+            # self-attention sub-layer, and in backward its input gradient beside what is left of the decoder's backward
+            self.sync("v", "t")
+            with self.on("v"):
+                kv = self._cross_kv(enc)
+        elif kv is None:
+            kv = self._cross_kv(enc)
         shared = self.flat.dec_emb is self.flat.enc_emb
         # the embedding MODULE's own dropout: with the shared module of train_gen.py:293 that is the ENCODER config's
         # hidden_dropout_prob (vilbert_dialog.py:321), whoever calls it (tests/golden/tiny_train_dropout.npz)
@@ -1087,47 +785,57 @@ class Engine(object):
         I["feats_grad"] = bool(feats.requires_grad and torch.is_grad_enabled())
         return I
 
-    def _begin(self, device, record):
+    def _begin(self, device, record, inference=False):
+        """Start of every engine call.  `inference`: dropout off whatever the module's mode (the RNG still advances with it)."""
         self.prepare(device)
         self._last_decode = None          # the arena is rewound: a previous decode call's encoder states are about to be overwritten
         self.arena.reset()
-        self.tape, self.rec = [], record
-        self.tag = "t"
+        self.tape, self.rec, self.tag = [], record, "t"
         self.main = torch.cuda.current_stream()
-        self._site = 0
-        self.site_log = {}
-        self.train = bool(self.model.training)
-        if self.train:
+        self._site, self.site_log = 0, {}
+        training = bool(self.model.training)
+        self.train = training and not inference
+        if training:
             self.rng.advance()
+
+    def _shift_labels(self, dec_ids):
+        """The reference's labels=None branch (visual_dialog_decoder.py:53-57): labels are the ids shifted left; then [SEP] becomes
+        [PAD] in the CALLER's `dec_ids`, in place."""
+        dc = self.dec_cfg
+        labels = dec_ids.new_zeros(dec_ids.shape)
+        labels[:, :-1] = dec_ids[:, 1:].clone()
+        dec_ids.masked_fill_(dec_ids == dc.eos_token_id, dc.pad_token_id)
+        return labels
+
+    def _ce(self, logits, labels, rows, U, mean=True):
+        """Cross-entropy of the LM head's `logits` ([rows * U, Vp] Act) against `labels` [rows, U], [PAD] ignored.
+        -> (loss, logits[:, :, :V], ce): `loss` is the mean over the counted tokens or the per-token losses, and like the logits a
+        VIEW of the arena (rewound by the next engine call: no-grad callers copy); `ce` holds what backward / scoring read."""
+        dc = self.dec_cfg
+        Md, V = rows * U, dc.vocab_size
+        lab = labels.contiguous().view(-1)
+        row_loss, lse, stats = self.vec(Md), self.vec(Md), self.vec(4)
+        ops.ce_fwd(logits.t, lab, Md, V, row_loss, lse, stats, ignore_index=dc.pad_token_id)
+        ce = dict(lab=lab, row_loss=row_loss, lse=lse, stats=stats, Md=Md, V=V, pad=dc.pad_token_id)
+        return (stats[2] if mean else row_loss), logits.t.view(rows, U, self.flat.Vp)[:, :, :V], ce
 
     def step(self, feats, loc, img_mask, ids, segs, att_mask, dec_ids, dec_mask, labels, loss_reduction=True):
         """EncoderDecoderModel.forward, train/eval branch -> (loss, logits)."""
         record = torch.is_grad_enabled()
         self._begin(ids.device, record)
-        dc = self.dec_cfg
-        if labels is None:    # visual_dialog_decoder.py:53-57: shift left, then mutate the caller's ids in place
-            labels = dec_ids.new_zeros(dec_ids.shape)
-            labels[:, :-1] = dec_ids[:, 1:].clone()
-            dec_ids.masked_fill_(dec_ids == dc.eos_token_id, dc.pad_token_id)
+        if labels is None:
+            labels = self._shift_labels(dec_ids)
         I = self._inputs(feats, loc, img_mask, ids, segs, att_mask, dec_ids, dec_mask)
-        Bn, U, V = I["B"], I["U"], dc.vocab_size
         xt, xv = self.encoder(I)
         enc = self.fusion(xt, xv, I)
         y, logits = self.decoder(enc, I)
-        Md = Bn * U
-        lab = labels.contiguous().view(-1)
-        row_loss, lse, stats = self.vec(Md), self.vec(Md), self.vec(4)
-        ops.ce_fwd(logits.t, lab, Md, V, row_loss, lse, stats, ignore_index=dc.pad_token_id)
-        st = dict(I=I, logits=logits, lab=lab, lse=lse, stats=stats, Md=Md, V=V, mean=bool(loss_reduction), tape=self.tape,
-                  pad=dc.pad_token_id)
-        self.last = dict(enc_t=xt, enc_v=xv, enc=enc, dec_hidden=y, logits=logits, lse=lse, row_loss=row_loss)
-        lv = logits.t.view(Bn, U, self.flat.Vp)[:, :, :V]
+        loss_raw, lv, ce = self._ce(logits, labels, I["B"], I["U"], loss_reduction)
+        st = dict(ce, I=I, logits=logits, mean=bool(loss_reduction), tape=self.tape)
+        self.last = dict(enc_t=xt, enc_v=xv, enc=enc, dec_hidden=y, logits=logits, lse=ce["lse"], row_loss=ce["row_loss"])
         if record:
-            loss_raw = stats[2] if loss_reduction else row_loss
             loss = _StepFn.apply(self.anchor, feats if I["feats_grad"] else None, self, st, loss_raw)
             return loss, lv
-        loss = stats[2].clone() if loss_reduction else row_loss.clone()
-        return loss, lv.to(torch.float32, copy=True)      # a copy: the arena is rewound by the next engine call
+        return loss_raw.clone(), lv.to(torch.float32, copy=True)      # copies: the arena is rewound by the next engine call
 
     def backward(self, st, gloss):
         """Replay the tape: fills the flat gradient buffer, assigns `.grad` views, returns d loss / d image features."""
@@ -1170,9 +878,7 @@ class Engine(object):
             if tail is not None:                       # communication stream (all-reduce + AdamW of the slices): join it here
                 self.main.wait_event(tail)
         if self.aux_busy:
-            ev = torch.cuda.Event()
-            ev.record(self.aux)
-            self.main.wait_event(ev)
+            self._wait_for(self.main, self.aux)
             self.aux_busy = False
         self.wgrads.flush()
         self.colsums.flush()
@@ -1203,23 +909,18 @@ class Engine(object):
         E, rows = ids.shape[0], dec_ids.shape[0]
         if rows != E * group:
             raise GstvdError("score_candidates: %d decoder rows for %d encoder rows x %d candidates" % (rows, E, group))
-        self._begin(ids.device, False)
-        self.train = False
+        self._begin(ids.device, False, inference=True)
         dec_in = dec_ids.masked_fill(dec_ids == dc.eos_token_id, dc.pad_token_id)
         I = self._inputs(feats, loc, img_mask, ids, segs, att_mask, dec_in, dec_mask)
         xt, xv = self.encoder(I)
         enc = self.fusion(xt, xv, I)
-        L, H = dc.num_hidden_layers, dc.hidden_size
-        kv = self.lin(enc, "dec.ckv.w", "dec.ckv.b", 2 * L * H, H)
-        _, logits = self.decoder(enc, I, kv, kv_group=group)
-        U, V = I["U"], dc.vocab_size
-        Md = rows * U
-        tgt = dec_ids.new_zeros(dec_ids.shape)
+        _, logits = self.decoder(enc, I, self._cross_kv(enc), kv_group=group)
+        U = I["U"]
+        tgt = dec_ids.new_zeros(dec_ids.shape)      # (not _shift_labels: the caller's `dec_ids` stays as it is, see `dec_in`)
         tgt[:, :-1] = dec_ids[:, 1:]
-        row_loss, lse, stats = self.vec(Md), self.vec(Md), self.vec(4)
-        ops.ce_fwd(logits.t, tgt.contiguous().view(-1), Md, V, row_loss, lse, stats, ignore_index=dc.pad_token_id)
+        ce = self._ce(logits, tgt, rows, U)[2]
         scores = torch.empty(rows, dtype=torch.float32, device=ids.device)
-        ops.answer_scores(logits.t, lse, dec_ids.contiguous(), rows, U, scores)
+        ops.answer_scores(logits.t, ce["lse"], dec_ids.contiguous(), rows, U, scores)
         return scores
 
     # ------------------------------------------------------------------------------------------ discriminative ranking
@@ -1232,8 +933,7 @@ class Engine(object):
         whose outputs the reference's only caller discards (evaluate_disc.py:79), are not computed."""
         if not self.enc_only:
             raise GstvdError("nsp_scores belongs to the encoder-only engine of an enc_only VisualDialogEncoder")
-        self._begin(ids.device, False)
-        self.train = False
+        self._begin(ids.device, False, inference=True)
         dummy = ids.new_zeros(ids.shape[0], 1)
         I = self._inputs(feats, loc, img_mask, ids, segs, att_mask, dummy, None)
         xt, xv = self.encoder(I)
@@ -1244,259 +944,6 @@ class Engine(object):
                      self.Pv["nsp.w"], self.Pv["nsp.b"], Bn, self.enc_cfg.fusion_method, z, prob0)
         self.last = dict(enc_t=xt, enc_v=xv)
         return z, prob0
-
-    # ------------------------------------------------------------------------------------------ sampling decode
-    def _decode_plan(self, ins, L0, max_seq_len):
-        """Builds the two device programs of a decode call on the engine's arena: `encode()` (encoder, VLFusion, the
-        cross-attention K/V of all decoder layers -- once per call) and `one_token(tok, t)` (ONE token per row through
-        the decoder stack at position t, its self-attention K/V appended to the per-layer caches) -> fp32 logits [B, V].
-        `ins` = (feats, loc, img_mask, ids, segs, att_mask, dec_ids) are the tensors the kernels read."""
-        feats, loc, img_mask, ids, segs, att_mask, dec_ids = ins
-        dc = self.dec_cfg
-        st = {}
-
-        def encode():
-            self._begin(ids.device, False)
-            self.train = False
-            I = self._inputs(feats, loc, img_mask, ids, segs, att_mask, dec_ids, None)
-            xt, xv = self.encoder(I)
-            enc = self.fusion(xt, xv, I)
-            Bn = I["B"]
-            L, H = dc.num_hidden_layers, dc.hidden_size
-            st["I"], st["Bn"], st["S"] = I, Bn, I["R"] + I["T"]
-            st["kv"] = self.lin(enc, "dec.ckv.w", "dec.ckv.b", 2 * L * H, H)      # cross K/V of all layers, once
-            Umax = L0 + max_seq_len
-            st["Umax"] = Umax
-            # per-layer cache of the fused Q|K|V rows, [B, Umax, 3H]: the QKV GEMM of position t writes its output rows straight
-            # into cache[:, t] (row stride Umax*3H), attention reads K / V from the same rows -- no append copies
-            st["QKVc"] = [Act(self.buf(Bn * Umax, 3 * H), Bn * Umax, 3 * H) for _ in range(L)]
-            st["mark"] = self.arena.mark()
-
-        def one_token(tok, t):
-            I, Bn, S, kv, QKVc, Umax = st["I"], st["Bn"], st["S"], st["kv"], st["QKVc"], st["Umax"]
-            V, Vp = dc.vocab_size, self.flat.Vp
-            L, H, nh, eps = dc.num_hidden_layers, dc.hidden_size, dc.num_attention_heads, dc.layer_norm_eps
-            d = H // nh
-            prefix = "emb" if self.flat.dec_emb is self.flat.enc_emb else "demb"
-            self.arena.rewind(st["mark"])
-            y = self.embed(prefix, tok.contiguous(), None, Bn, 1, dc, pos_offset=t)
-            # bf16: the three LayerNorms of a layer are folded into the Linears that read them (gstvd_gemv_ln) and the residual
-            # adds into the epilogues of the Linears in front of them -- 8 launches per layer instead of 11.  `pre` = the
-            # rows whose LayerNorm (parameters `lnp`) the next Linear still has to apply.
-            fuse = (self.adt is torch.bfloat16 and Bn <= 16 and H <= 1024
-                    and bool(self.model.params.get("amd_decode_fuse_ln", True)))       # (the switch exists for the parity test)
-            I_ = dc.intermediate_size
-            pre, lnp = None, None
-            for i in range(L):
-                p = "d%d" % i
-                rows_t = QKVc[i].t.view(Bn, Umax, 3 * H)[:, t]                     # [Bn, 3H] view, row stride Umax * 3H
-                if pre is None:
-                    ops.gemm(y.t, self.W[p + ".qkv.w"], rows_t, Bn, 3 * H, H, bias=self.Pv[p + ".qkv.b"])
-                else:
-                    y = self.act(Bn, H)
-                    ops.gemv_ln(pre.t, self.W[p + ".qkv.w"], rows_t, Bn, 3 * H, H, self.Pv[lnp + ".w"], self.Pv[lnp + ".b"], eps,
-                                y_out=y.t, bias=self.Pv[p + ".qkv.b"])
-                qkv = Act(rows_t, Bn, 3 * H)
-                ctx = self.attn((qkv, 0), (QKVc[i], H), (QKVc[i], 2 * H), Bn, nh, 1, t + 1, d, None, False, -10000.0, 0.0,
-                                kv_bstride=Umax)
-                if fuse:
-                    pre1, y1, q = self.act(Bn, H), self.act(Bn, H), self.act(Bn, H)
-                    ops.gemm(ctx.t, self.W[p + ".ao.w"], pre1.t, Bn, H, H, bias=self.Pv[p + ".ao.b"], addend=y.t)
-                    ops.gemv_ln(pre1.t, self.W[p + ".cq.w"], q.t, Bn, H, H, self.Pv[p + ".ln1.w"], self.Pv[p + ".ln1.b"], eps,
-                                y_out=y1.t, bias=self.Pv[p + ".cq.b"])
-                    ctx = self.attn((q, 0), (kv, 2 * i * H), (kv, (2 * i + 1) * H), Bn, nh, 1, S, d, I["emask"], False, -1e9, 0.0)
-                    pre2, y2, a, aux = self.act(Bn, H), self.act(Bn, H), self.act(Bn, I_), self.buf(Bn, I_)
-                    ops.gemm(ctx.t, self.W[p + ".co.w"], pre2.t, Bn, H, H, bias=self.Pv[p + ".co.b"], addend=y1.t)
-                    ops.gemv_ln(pre2.t, self.W[p + ".fi.w"], a.t, Bn, I_, H, self.Pv[p + ".ln2.w"], self.Pv[p + ".ln2.b"], eps,
-                                y_out=y2.t, bias=self.Pv[p + ".fi.b"], aux=aux, epi=EPI_GELU)
-                    pre = self.act(Bn, H)
-                    ops.gemm(a.t, self.W[p + ".fo.w"], pre.t, Bn, H, I_, bias=self.Pv[p + ".fo.b"], addend=y2.t)
-                    lnp = p + ".ln3"
-                    continue
-                ao = self.lin(ctx, p + ".ao.w", p + ".ao.b", H, H)
-                y1 = self.ln(ao, y, p + ".ln1.w", p + ".ln1.b", H, 0.0, None, eps)
-                q = self.lin(y1, p + ".cq.w", p + ".cq.b", H, H)
-                ctx = self.attn((q, 0), (kv, 2 * i * H), (kv, (2 * i + 1) * H), Bn, nh, 1, S, d, I["emask"], False, -1e9, 0.0)
-                co = self.lin(ctx, p + ".co.w", p + ".co.b", H, H)
-                y2 = self.ln(co, y1, p + ".ln2.w", p + ".ln2.b", H, 0.0, None, eps)
-                a = self.lin(y2, p + ".fi.w", p + ".fi.b", dc.intermediate_size, H, gelu=True)
-                fo = self.lin(a, p + ".fo.w", p + ".fo.b", H, dc.intermediate_size)
-                y = self.ln(fo, y2, p + ".ln3.w", p + ".ln3.b", H, 0.0, None, eps)
-            if pre is not None:
-                # (the LM head keeps LayerNorm + Linear as two launches: 1908 workgroups of the LN-in kernel, each holding
-                # gamma / beta in registers, stream the 47 MB of vocabulary weights at a quarter of the plain kernel's rate)
-                y = self.ln(pre, None, lnp + ".w", lnp + ".b", H, 0.0, None, eps)
-            return self.lin(y, "lm.w", "lm.b", Vp, H).t[:, :V]         # [Bn, V] view of the arena (row stride Vp), activation dtype
-
-        return encode, one_token, st
-
-    @staticmethod
-    def _fused_sampling(P, vocab):
-        """The fused sampling kernel covers the reference's settings (generate.py:138-141,177-180: top_k 7, top_p 0; BERT's
-        30522-token vocabulary) and, since ABI 6, any top_k and top_p; only a vocabulary beyond one CU's LDS takes the torch-op
-        form of the filters, issued eagerly step by step (no captured token graph)."""
-        return vocab <= ops.SAMPLE_MAX_VOCAB        # (any top_k, any top_p: both filters run inside the sampling launch since ABI 6)
-
-    @staticmethod
-    def _sampling_step(logits, cur, pos, hist, P, u_row):
-        """One step of models/visual_dialog_model.py:96-108 on static buffers: cur[pos] <- the token drawn from `logits`
-        (temperature, n-gram ban against `hist`, top-k / top-p, softmax, inverse-CDF draw from the uniforms `u_row`).
-        `cur` is the TIME-MAJOR id buffer [L0 + max_seq_len, B]: position t of all rows is one contiguous row, which the next
-        token step's embedding reads as it is.  Free of host synchronisation and of generator state, so the token graph
-        captures it together with the decoder stack."""
-        from . import decoding
-        if Engine._fused_sampling(P, logits.shape[-1]):
-            # the n-gram ban (utils/decoding_utils.py:38-77) runs inside the sampling launch: `hist` and the time-major id buffer
-            # are all it needs (round 4 built a [B, V + 1] mask with ten torch launches per token: +2 ms per questioner decode)
-            ops.sample_topk(logits, P["temperature"], P["top_k"], u_row, cur[pos], None,
-                            ngram=(hist, cur, pos, P["ngram"]) if P["ngram"] > 0 else None, top_p=P["top_p"])
-            return
-        last = logits.float() / P["temperature"]
-        last = decoding.batch_ngram_blocking(last, hist, cur[:pos].t(), ngram_size=P["ngram"])
-        last = decoding.batch_top_k_top_p_sampling(last, top_k=P["top_k"], top_p=P["top_p"])
-        prob = torch.softmax(last, dim=-1)
-        cur[pos] = decoding.draw_from_uniform(prob, u_row).view(-1)
-
-    def _decode_session(self, ins, L0, max_seq_len, P):
-        """hipGraph form of a decode call (generate.py's loop calls sample() with the same shapes and settings batch after
-        batch): static copies of the inputs, one captured graph for `encode` and ONE for the whole token loop -- every decoder
-        position's stack AND its sampling step (filters, softmax, draw, append), so that nothing of the loop is issued from
-        the host at replay (round 1-2 replayed one graph per position and ran ~25 small torch kernels per step eagerly in
-        between: the loop was bound by host issue).
-        Returns (refresh(ins, uniforms), run_encode(), run_tokens(), st, cur, last_logits)."""
-        static = tuple(x.clone() if x is not None else None for x in ins)
-        ids, segs, dec_ids = static[3], static[4], static[6]
-        Bn, dev = ids.shape[0], ids.device
-        steps = L0 + max_seq_len - 1
-        cur = torch.zeros(L0 + max_seq_len, Bn, dtype=torch.long, device=dev)      # time-major (see _sampling_step)
-        u_buf = torch.zeros(max_seq_len, Bn, dtype=torch.float32, device=dev)
-        encode, one_token, st = self._decode_plan(static, L0, max_seq_len)
-        from .graph import capture, gc_quiet
-        with gc_quiet():
-            g_enc = torch.cuda.CUDAGraph()
-            with capture(g_enc):
-                encode()
-                hist = ids * (segs == 0).long()
-            g_dec = torch.cuda.CUDAGraph()
-            with capture(g_dec, pool=g_enc.pool(), quiesce=False):
-                cur[:L0] = dec_ids.t()
-                for t in range(steps):
-                    logits = one_token(cur[t], t)
-                    if t >= L0 - 1:
-                        self._sampling_step(logits, cur, t + 1, hist, P, u_buf[t - (L0 - 1)])
-
-        def refresh(new, uniforms):
-            for dst, src in zip(static, new):
-                if dst is not None:
-                    dst.copy_(src)
-            u_buf.copy_(uniforms)
-
-        return refresh, g_enc.replay, g_dec.replay, st, cur, logits
-
-    @torch.no_grad()
-    def sample(self, feats, loc, img_mask, ids, segs, att_mask, dec_ids, temperature=1.0, top_k=0, top_p=0.0,
-               ngram_blocking_size=0, max_seq_len=18, uniforms=None, **_):
-        """models/visual_dialog_model.py:74-120: 18 sampling steps (temperature, n-gram blocking, top-k / top-p, multinomial
-        draw, [PAD] after the first [SEP]).  The reference re-runs the whole decoder on the growing prefix and re-projects
-        the cross-attention K/V of all 37+T encoder states in all 12 layers at every step (use_cache=False); here the
-        encoder, VLFusion and the cross K/V projection run once, and each step feeds ONE token per row through the stack,
-        appending its self-attention K/V to a [B, Umax, H] cache per layer.  Same arithmetic, O(U) instead of O(U^2).
-        From the second call with the same shapes and sampling settings on (params['amd_decode_graph'], default on) the
-        device work is replayed from two captured hipGraphs (the encoder side; the whole token loop incl. its sampling
-        steps): ~3000 launches per call leave the host.
-        Token-id work (filters, n-gram ban, EOS fill) is integer-exact torch index plumbing (decoding.py), free of host syncs.
-        Token t is drawn by inverse CDF from uniforms[t] ([max_seq_len, B] in (0, 1); drawn from torch's default generator when
-        the caller passes none) instead of torch.multinomial (whose stream is device specific) -- the same rule the oracle
-        applies to the reference, so sampled ids can be compared under real sampling."""
-        from . import decoding
-        dc = self.dec_cfg
-        if segs is None:
-            segs = torch.zeros_like(ids)
-        ins = (feats, loc, img_mask, ids, segs, att_mask, dec_ids)
-        L0 = dec_ids.shape[1]
-        Bn = ids.shape[0]
-        P = dict(temperature=float(temperature), top_k=int(top_k), top_p=float(top_p), ngram=int(ngram_blocking_size))
-        sig = (L0, max_seq_len, tuple(sorted(P.items()))) + tuple((tuple(x.shape), x.dtype) if x is not None else None for x in ins)
-        if uniforms is None:
-            # the call's randomness, drawn ONCE from torch's default CUDA generator (eagerly: no generator state inside the
-            # captured graphs); every step then draws by inverse CDF -- the same distribution as the reference's
-            # torch.multinomial (whose stream is device specific anyway), and the same ids from eager issue and graph replay
-            u = torch.rand(max_seq_len, Bn, device=ids.device, dtype=torch.float32).clamp_min_(1e-12)
-        else:
-            u = uniforms.to(ids.device, torch.float32)
-            if u.dim() != 2 or u.shape[0] < max_seq_len or u.shape[1] != Bn:
-                raise GstvdError("uniforms must be [max_seq_len = %d, batch = %d] (one draw per step and row), got %s"
-                                 % (max_seq_len, Bn, tuple(u.shape)))
-            u = u[:max_seq_len].contiguous()
-        use_graph = bool(self.model.params.get("amd_decode_graph", True)) and self._fused_sampling(P, dc.vocab_size)
-        # parameters edited since the last call (load_state_dict, an optimizer step): the captured graphs read the flat
-        # buffers / bf16 shadow, so bring those up to date OUTSIDE the graphs; a re-materialised buffer drops the sessions
-        self.prepare(ids.device)
-        sess = self._decode_sessions.get(sig) if use_graph else None
-        if sess is not None:
-            refresh, run_encode, run_tokens, dst, cur, last_logits = sess
-            refresh(ins, u)
-            run_encode()
-            run_tokens()
-            cur, logits = cur.clone(), last_logits
-        else:
-            run_encode, one_token, dst = self._decode_plan(ins, L0, max_seq_len)
-            run_encode()
-            hist = ids * (segs == 0).long()
-            cur = torch.zeros(L0 + max_seq_len, Bn, dtype=torch.long, device=ids.device)
-            cur[:L0] = dec_ids.t()
-            calls0 = _libmod.N_CALLS[0]
-            for t in range(L0 + max_seq_len - 1):
-                logits = one_token(cur[t], t)
-                if t >= L0 - 1:                            # (earlier positions only consume the given prefix)
-                    self._sampling_step(logits, cur, t + 1, hist, P, u[t - (L0 - 1)])
-            self.decode_lib_calls_per_token = (_libmod.N_CALLS[0] - calls0) / float(L0 + max_seq_len - 1)
-        self.last = dict(decode_logits=logits.float())    # last position's raw logits (tests / debugging)
-        # the encoder side of this call (cross-attention K/V of all layers, masks) stays valid in the arena until the next
-        # engine call: `rescore_sampled` scores the sampled answer against it without a second encoder pass
-        out = decoding.pad_after_eos(cur[L0:].t().contiguous(), dc.eos_token_id, dc.pad_token_id)
-        if use_graph and sess is None:
-            # first call with these shapes ran eagerly (it also initialised every lazily built table / attribute / arena
-            # chunk); capture now so the next batch replays
-            if len(self._decode_sessions) >= 4:
-                self._decode_sessions.clear()
-            self._decode_sessions[sig] = self._decode_session(ins, L0, max_seq_len, P)
-        # (after the capture: capturing runs the Python side of encode() again -- which rewinds the arena bookkeeping and drops
-        # this marker -- but executes nothing, so the eager call's encoder states are still what the arena holds)
-        self._last_decode = (dst, ids.shape[0], self.arena)
-        return out
-
-
-    @torch.no_grad()
-    def rescore_sampled(self, dec_ids, dec_mask=None, loss_reduction=False):
-        """The "ppl trick" of generate.py:183-211 fused onto the decode call that produced the answer: ONE teacher-forced
-        decoder pass over `dec_ids` against the encoder states / cross-attention K/V that the last `sample()` call left in
-        the arena (same context by construction: the answer was sampled from it) -- no second encoder run, no second K/V
-        projection.  Same conventions as the reference's labels=None branch (visual_dialog_decoder.py:53-57): labels are
-        the ids shifted left, `dec_ids` has [SEP] -> [PAD] in place.  Returns (loss, logits) like `step`."""
-        ld = getattr(self, "_last_decode", None)
-        if ld is None or ld[2] is not self.arena or ld[1] != dec_ids.shape[0]:
-            raise GstvdError("rescore_sampled: no decode state of a matching sample() call to reuse")
-        st = ld[0]
-        dc = self.dec_cfg
-        self.arena.rewind(st["mark"])
-        self.tape, self.rec, self.tag, self.train = [], False, "t", False
-        self.main = torch.cuda.current_stream()
-        labels = dec_ids.new_zeros(dec_ids.shape)
-        labels[:, :-1] = dec_ids[:, 1:].clone()
-        dec_ids.masked_fill_(dec_ids == dc.eos_token_id, dc.pad_token_id)
-        I = dict(st["I"])
-        Bn, U, V = I["B"], dec_ids.shape[1], dc.vocab_size
-        I["U"] = U
-        I["dec_ids"] = dec_ids.contiguous().view(-1)
-        I["dmask"] = dec_mask.float().contiguous() if dec_mask is not None else None
-        _, logits = self.decoder(None, I, kv=st["kv"])
-        Md = Bn * U
-        row_loss, lse, stats = self.vec(Md), self.vec(Md), self.vec(4)
-        ops.ce_fwd(logits.t, labels.contiguous().view(-1), Md, V, row_loss, lse, stats, ignore_index=dc.pad_token_id)
-        self._last_decode = None                  # the decode scratch behind the mark has been overwritten
-        loss = stats[2].clone() if loss_reduction else row_loss.clone()
-        return loss, logits.t.view(Bn, U, self.flat.Vp)[:, :, :V].to(torch.float32, copy=True)
 
 
 class _StepFn(torch.autograd.Function):
@@ -1547,17 +994,13 @@ def standalone_decoder_forward(module, dec_ids, attention_mask, enc_hidden, enc_
         raise GstvdError("VisualDialogDecoder.forward alone is inference only on the MI355X engine (eval() + torch.no_grad()); "
                          "train through EncoderDecoderModel(...)")
     with torch.no_grad():
-        eng._begin(dec_ids.device, False)
-        eng.train = False
-        dc = eng.dec_cfg
+        eng._begin(dec_ids.device, False, inference=True)
         if labels is None:
-            labels = dec_ids.new_zeros(dec_ids.shape)
-            labels[:, :-1] = dec_ids[:, 1:].clone()
-            dec_ids.masked_fill_(dec_ids == dc.eos_token_id, dc.pad_token_id)
+            labels = eng._shift_labels(dec_ids)
         Bn, S, H = enc_hidden.shape
-        U, V = dec_ids.shape[1], dc.vocab_size
-        if H != dc.hidden_size:
-            raise GstvdError("encoder_hidden_states width %d != decoder hidden size %d" % (H, dc.hidden_size))
+        U = dec_ids.shape[1]
+        if H != eng.dec_cfg.hidden_size:
+            raise GstvdError("encoder_hidden_states width %d != decoder hidden size %d" % (H, eng.dec_cfg.hidden_size))
         enc = eng.act(Bn * S, H)
         enc.t.copy_(enc_hidden.reshape(Bn * S, H))
         em = enc_mask if enc_mask is not None else torch.ones(Bn, S, device=dec_ids.device)
@@ -1565,8 +1008,5 @@ def standalone_decoder_forward(module, dec_ids, attention_mask, enc_hidden, enc_
         I = dict(B=Bn, T=S, R=0, U=U, emask=em.float().contiguous(), dmask=dm.float().contiguous(),
                  dec_ids=dec_ids.contiguous().view(-1))
         y, logits = eng.decoder(enc, I)
-        Md = Bn * U
-        row_loss, lse, stats = eng.vec(Md), eng.vec(Md), eng.vec(4)
-        ops.ce_fwd(logits.t, labels.contiguous().view(-1), Md, V, row_loss, lse, stats, ignore_index=dc.pad_token_id)
-        loss = stats[2].clone() if loss_reduction else row_loss.clone()
-        return loss, logits.t.view(Bn, U, eng.flat.Vp)[:, :, :V].float()
+        loss, lv, _ = eng._ce(logits, labels, Bn, U, loss_reduction)
+        return loss.clone(), lv.float()

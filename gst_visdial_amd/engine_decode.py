@@ -1,0 +1,246 @@
+"""Sampling decode of the engine (models/visual_dialog_model.py:74-120, generate.py:183-211): one token per row and step
+through the decoder stack against per-layer K/V caches, the captured hipGraph form of the loop, and the perplexity re-score
+of the sampled answer.  `DecodeMixin` is the decode half of `engine.Engine`; it uses the engine's op helpers and schedule."""
+import torch
+
+from . import ops
+from . import _lib as _libmod
+from .storage import Act
+from ._lib import GstvdError, EPI_GELU
+
+
+class DecodeMixin(object):
+    def _decode_plan(self, ins, L0, max_seq_len):
+        """Builds the two device programs of a decode call on the engine's arena: `encode()` (encoder, VLFusion, the
+        cross-attention K/V of all decoder layers -- once per call) and `one_token(tok, t)` (ONE token per row through
+        the decoder stack at position t, its self-attention K/V appended to the per-layer caches) -> fp32 logits [B, V].
+        `ins` = (feats, loc, img_mask, ids, segs, att_mask, dec_ids) are the tensors the kernels read."""
+        feats, loc, img_mask, ids, segs, att_mask, dec_ids = ins
+        dc = self.dec_cfg
+        st = {}
+
+        def encode():
+            self._begin(ids.device, False, inference=True)
+            I = self._inputs(feats, loc, img_mask, ids, segs, att_mask, dec_ids, None)
+            xt, xv = self.encoder(I)
+            enc = self.fusion(xt, xv, I)
+            Bn = I["B"]
+            L, H = dc.num_hidden_layers, dc.hidden_size
+            st["I"], st["Bn"], st["S"] = I, Bn, I["R"] + I["T"]
+            st["kv"] = self._cross_kv(enc)                                       # cross K/V of all layers, once
+            Umax = L0 + max_seq_len
+            st["Umax"] = Umax
+            # per-layer cache of the fused Q|K|V rows, [B, Umax, 3H]: the QKV GEMM of position t writes its output rows straight
+            # into cache[:, t] (row stride Umax*3H), attention reads K / V from the same rows -- no append copies
+            st["QKVc"] = [Act(self.buf(Bn * Umax, 3 * H), Bn * Umax, 3 * H) for _ in range(L)]
+            st["mark"] = self.arena.mark()
+
+        def one_token(tok, t):
+            I, Bn, S, kv, QKVc, Umax = st["I"], st["Bn"], st["S"], st["kv"], st["QKVc"], st["Umax"]
+            V, Vp = dc.vocab_size, self.flat.Vp
+            L, H, nh, eps = dc.num_hidden_layers, dc.hidden_size, dc.num_attention_heads, dc.layer_norm_eps
+            d = H // nh
+            prefix = "emb" if self.flat.dec_emb is self.flat.enc_emb else "demb"
+            self.arena.rewind(st["mark"])
+            y = self.embed(prefix, tok.contiguous(), None, Bn, 1, dc, pos_offset=t)
+            # bf16: the three LayerNorms of a layer are folded into the Linears that read them (gstvd_gemv_ln) and the residual
+            # adds into the epilogues of the Linears in front of them -- 8 launches per layer instead of 11.  `pre` = the
+            # rows whose LayerNorm (parameters `lnp`) the next Linear still has to apply.
+            fuse = (self.adt is torch.bfloat16 and Bn <= 16 and H <= 1024
+                    and bool(self.model.params.get("amd_decode_fuse_ln", True)))       # (the switch exists for the parity test)
+            I_ = dc.intermediate_size
+            pre, lnp = None, None
+            for i in range(L):
+                p = "d%d" % i
+                rows_t = QKVc[i].t.view(Bn, Umax, 3 * H)[:, t]                     # [Bn, 3H] view, row stride Umax * 3H
+                if pre is None:
+                    ops.gemm(y.t, self.W[p + ".qkv.w"], rows_t, Bn, 3 * H, H, bias=self.Pv[p + ".qkv.b"])
+                else:
+                    y = self.act(Bn, H)
+                    ops.gemv_ln(pre.t, self.W[p + ".qkv.w"], rows_t, Bn, 3 * H, H, self.Pv[lnp + ".w"], self.Pv[lnp + ".b"], eps,
+                                y_out=y.t, bias=self.Pv[p + ".qkv.b"])
+                qkv = Act(rows_t, Bn, 3 * H)
+                ctx = self.attn((qkv, 0), (QKVc[i], H), (QKVc[i], 2 * H), Bn, nh, 1, t + 1, d, None, False, -10000.0, 0.0,
+                                kv_bstride=Umax)
+                if fuse:
+                    pre1, y1, q = self.act(Bn, H), self.act(Bn, H), self.act(Bn, H)
+                    ops.gemm(ctx.t, self.W[p + ".ao.w"], pre1.t, Bn, H, H, bias=self.Pv[p + ".ao.b"], addend=y.t)
+                    ops.gemv_ln(pre1.t, self.W[p + ".cq.w"], q.t, Bn, H, H, self.Pv[p + ".ln1.w"], self.Pv[p + ".ln1.b"], eps,
+                                y_out=y1.t, bias=self.Pv[p + ".cq.b"])
+                    ctx = self.attn((q, 0), (kv, 2 * i * H), (kv, (2 * i + 1) * H), Bn, nh, 1, S, d, I["emask"], False, -1e9, 0.0)
+                    pre2, y2, a, aux = self.act(Bn, H), self.act(Bn, H), self.act(Bn, I_), self.buf(Bn, I_)
+                    ops.gemm(ctx.t, self.W[p + ".co.w"], pre2.t, Bn, H, H, bias=self.Pv[p + ".co.b"], addend=y1.t)
+                    ops.gemv_ln(pre2.t, self.W[p + ".fi.w"], a.t, Bn, I_, H, self.Pv[p + ".ln2.w"], self.Pv[p + ".ln2.b"], eps,
+                                y_out=y2.t, bias=self.Pv[p + ".fi.b"], aux=aux, epi=EPI_GELU)
+                    pre = self.act(Bn, H)
+                    ops.gemm(a.t, self.W[p + ".fo.w"], pre.t, Bn, H, I_, bias=self.Pv[p + ".fo.b"], addend=y2.t)
+                    lnp = p + ".ln3"
+                    continue
+                ao = self.lin(ctx, p + ".ao.w", p + ".ao.b", H, H)
+                y1 = self.ln(ao, y, p + ".ln1.w", p + ".ln1.b", H, 0.0, None, eps)
+                q = self.lin(y1, p + ".cq.w", p + ".cq.b", H, H)
+                ctx = self.attn((q, 0), (kv, 2 * i * H), (kv, (2 * i + 1) * H), Bn, nh, 1, S, d, I["emask"], False, -1e9, 0.0)
+                co = self.lin(ctx, p + ".co.w", p + ".co.b", H, H)
+                y2 = self.ln(co, y1, p + ".ln2.w", p + ".ln2.b", H, 0.0, None, eps)
+                a = self.lin(y2, p + ".fi.w", p + ".fi.b", dc.intermediate_size, H, gelu=True)
+                fo = self.lin(a, p + ".fo.w", p + ".fo.b", H, dc.intermediate_size)
+                y = self.ln(fo, y2, p + ".ln3.w", p + ".ln3.b", H, 0.0, None, eps)
+            if pre is not None:
+                # (the LM head keeps LayerNorm + Linear as two launches: 1908 workgroups of the LN-in kernel, each holding
+                # gamma / beta in registers, stream the 47 MB of vocabulary weights at a quarter of the plain kernel's rate)
+                y = self.ln(pre, None, lnp + ".w", lnp + ".b", H, 0.0, None, eps)
+            return self.lin(y, "lm.w", "lm.b", Vp, H).t[:, :V]         # [Bn, V] view of the arena (row stride Vp), activation dtype
+
+        return encode, one_token, st
+
+    def _sampling_step(self, logits, cur, pos, hist, P, u_row):
+        """One step of models/visual_dialog_model.py:96-108 on static buffers: cur[pos] <- the token drawn from `logits`
+        (temperature, n-gram ban against `hist`, top-k / top-p, softmax, inverse-CDF draw from the uniforms `u_row`).
+        `cur` is the TIME-MAJOR id buffer [L0 + max_seq_len, B]: position t of all rows is one contiguous row, which the next
+        token step's embedding reads as it is.  Free of host synchronisation and of generator state, so the token graph
+        captures it together with the decoder stack."""
+        from . import decoding
+        if self._fused_sampling(P, logits.shape[-1]):
+            # the n-gram ban (utils/decoding_utils.py:38-77) runs inside the sampling launch: `hist` and the time-major id buffer
+            # are all it needs (round 4 built a [B, V + 1] mask with ten torch launches per token: +2 ms per questioner decode)
+            ops.sample_topk(logits, P["temperature"], P["top_k"], u_row, cur[pos], None,
+                            ngram=(hist, cur, pos, P["ngram"]) if P["ngram"] > 0 else None, top_p=P["top_p"])
+            return
+        last = logits.float() / P["temperature"]
+        last = decoding.batch_ngram_blocking(last, hist, cur[:pos].t(), ngram_size=P["ngram"])
+        last = decoding.batch_top_k_top_p_sampling(last, top_k=P["top_k"], top_p=P["top_p"])
+        prob = torch.softmax(last, dim=-1)
+        cur[pos] = decoding.draw_from_uniform(prob, u_row).view(-1)
+
+    def _decode_session(self, ins, L0, max_seq_len, P):
+        """hipGraph form of a decode call (generate.py's loop calls sample() with the same shapes and settings batch after
+        batch): static copies of the inputs, one captured graph for `encode` and ONE for the whole token loop -- every decoder
+        position's stack AND its sampling step (filters, softmax, draw, append), so that nothing of the loop is issued from
+        the host at replay (round 1-2 replayed one graph per position and ran ~25 small torch kernels per step eagerly in
+        between: the loop was bound by host issue).
+        Returns (refresh(ins, uniforms), run_encode(), run_tokens(), st, cur, last_logits)."""
+        static = tuple(x.clone() if x is not None else None for x in ins)
+        ids, segs, dec_ids = static[3], static[4], static[6]
+        Bn, dev = ids.shape[0], ids.device
+        steps = L0 + max_seq_len - 1
+        cur = torch.zeros(L0 + max_seq_len, Bn, dtype=torch.long, device=dev)      # time-major (see _sampling_step)
+        u_buf = torch.zeros(max_seq_len, Bn, dtype=torch.float32, device=dev)
+        encode, one_token, st = self._decode_plan(static, L0, max_seq_len)
+        from .graph import capture, gc_quiet
+        with gc_quiet():
+            g_enc = torch.cuda.CUDAGraph()
+            with capture(g_enc):
+                encode()
+                hist = ids * (segs == 0).long()
+            g_dec = torch.cuda.CUDAGraph()
+            with capture(g_dec, pool=g_enc.pool(), quiesce=False):
+                cur[:L0] = dec_ids.t()
+                for t in range(steps):
+                    logits = one_token(cur[t], t)
+                    if t >= L0 - 1:
+                        self._sampling_step(logits, cur, t + 1, hist, P, u_buf[t - (L0 - 1)])
+
+        def refresh(new, uniforms):
+            for dst, src in zip(static, new):
+                if dst is not None:
+                    dst.copy_(src)
+            u_buf.copy_(uniforms)
+
+        return refresh, g_enc.replay, g_dec.replay, st, cur, logits
+
+    @torch.no_grad()
+    def sample(self, feats, loc, img_mask, ids, segs, att_mask, dec_ids, temperature=1.0, top_k=0, top_p=0.0,
+               ngram_blocking_size=0, max_seq_len=18, uniforms=None, **_):
+        """models/visual_dialog_model.py:74-120: 18 sampling steps (temperature, n-gram blocking, top-k / top-p, multinomial
+        draw, [PAD] after the first [SEP]).  The reference re-runs the whole decoder on the growing prefix and re-projects
+        the cross-attention K/V of all 37+T encoder states in all 12 layers at every step (use_cache=False); here the
+        encoder, VLFusion and the cross K/V projection run once, and each step feeds ONE token per row through the stack,
+        appending its self-attention K/V to a [B, Umax, H] cache per layer.  Same arithmetic, O(U) instead of O(U^2).
+        From the second call with the same shapes and sampling settings on (params['amd_decode_graph'], default on) the
+        device work is replayed from two captured hipGraphs (the encoder side; the whole token loop incl. its sampling
+        steps): ~3000 launches per call leave the host.
+        Token-id work (filters, n-gram ban, EOS fill) is integer-exact torch index plumbing (decoding.py), free of host syncs.
+        Token t is drawn by inverse CDF from uniforms[t] ([max_seq_len, B] in (0, 1); drawn from torch's default generator when
+        the caller passes none) instead of torch.multinomial (whose stream is device specific) -- the same rule the oracle
+        applies to the reference, so sampled ids can be compared under real sampling."""
+        from . import decoding
+        dc = self.dec_cfg
+        if segs is None:
+            segs = torch.zeros_like(ids)
+        ins = (feats, loc, img_mask, ids, segs, att_mask, dec_ids)
+        L0, Bn = dec_ids.shape[1], ids.shape[0]
+        P = dict(temperature=float(temperature), top_k=int(top_k), top_p=float(top_p), ngram=int(ngram_blocking_size))
+        sig = (L0, max_seq_len, tuple(sorted(P.items()))) + tuple((tuple(x.shape), x.dtype) if x is not None else None for x in ins)
+        if uniforms is None:
+            # the call's randomness, drawn ONCE from torch's default CUDA generator (eagerly: no generator state inside the
+            # captured graphs); every step then draws by inverse CDF -- the same distribution as the reference's
+            # torch.multinomial (whose stream is device specific anyway), and the same ids from eager issue and graph replay
+            u = torch.rand(max_seq_len, Bn, device=ids.device, dtype=torch.float32).clamp_min_(1e-12)
+        else:
+            u = uniforms.to(ids.device, torch.float32)
+            if u.dim() != 2 or u.shape[0] < max_seq_len or u.shape[1] != Bn:
+                raise GstvdError("uniforms must be [max_seq_len = %d, batch = %d] (one draw per step and row), got %s"
+                                 % (max_seq_len, Bn, tuple(u.shape)))
+            u = u[:max_seq_len].contiguous()
+        use_graph = bool(self.model.params.get("amd_decode_graph", True)) and self._fused_sampling(P, dc.vocab_size)
+        # parameters edited since the last call (load_state_dict, an optimizer step): the captured graphs read the flat
+        # buffers / bf16 shadow, so bring those up to date OUTSIDE the graphs; a re-materialised buffer drops the sessions
+        self.prepare(ids.device)
+        sess = self._decode_sessions.get(sig) if use_graph else None
+        if sess is not None:
+            refresh, run_encode, run_tokens, dst, cur, last_logits = sess
+            refresh(ins, u)
+            run_encode()
+            run_tokens()
+            cur, logits = cur.clone(), last_logits
+        else:
+            run_encode, one_token, dst = self._decode_plan(ins, L0, max_seq_len)
+            run_encode()
+            hist = ids * (segs == 0).long()
+            cur = torch.zeros(L0 + max_seq_len, Bn, dtype=torch.long, device=ids.device)
+            cur[:L0] = dec_ids.t()
+            calls0 = _libmod.N_CALLS[0]
+            for t in range(L0 + max_seq_len - 1):
+                logits = one_token(cur[t], t)
+                if t >= L0 - 1:                            # (earlier positions only consume the given prefix)
+                    self._sampling_step(logits, cur, t + 1, hist, P, u[t - (L0 - 1)])
+            self.decode_lib_calls_per_token = (_libmod.N_CALLS[0] - calls0) / float(L0 + max_seq_len - 1)
+        self.last = dict(decode_logits=logits.float())    # last position's raw logits (tests / debugging)
+        # the encoder side of this call (cross-attention K/V of all layers, masks) stays valid in the arena until the next
+        # engine call: `rescore_sampled` scores the sampled answer against it without a second encoder pass
+        out = decoding.pad_after_eos(cur[L0:].t().contiguous(), dc.eos_token_id, dc.pad_token_id)
+        if use_graph and sess is None:
+            # first call with these shapes ran eagerly (it also initialised every lazily built table / attribute / arena
+            # chunk); capture now so the next batch replays
+            if len(self._decode_sessions) >= 4:
+                self._decode_sessions.clear()
+            self._decode_sessions[sig] = self._decode_session(ins, L0, max_seq_len, P)
+        # (after the capture: capturing runs the Python side of encode() again -- which rewinds the arena bookkeeping and drops
+        # this marker -- but executes nothing, so the eager call's encoder states are still what the arena holds)
+        self._last_decode = (dst, ids.shape[0], self.arena)
+        return out
+
+    @torch.no_grad()
+    def rescore_sampled(self, dec_ids, dec_mask=None, loss_reduction=False):
+        """The "ppl trick" of generate.py:183-211 fused onto the decode call that produced the answer: ONE teacher-forced
+        decoder pass over `dec_ids` against the encoder states / cross-attention K/V that the last `sample()` call left in
+        the arena (same context by construction: the answer was sampled from it) -- no second encoder run, no second K/V
+        projection.  Same conventions as the reference's labels=None branch (visual_dialog_decoder.py:53-57): labels are
+        the ids shifted left, `dec_ids` has [SEP] -> [PAD] in place.  Returns (loss, logits) like `step`."""
+        ld = self._last_decode
+        if ld is None or ld[2] is not self.arena or ld[1] != dec_ids.shape[0]:
+            raise GstvdError("rescore_sampled: no decode state of a matching sample() call to reuse")
+        st = ld[0]
+        self.arena.rewind(st["mark"])
+        self.tape, self.rec, self.tag, self.train = [], False, "t", False
+        self.main = torch.cuda.current_stream()
+        labels = self._shift_labels(dec_ids)
+        I = dict(st["I"])
+        Bn, U = I["B"], dec_ids.shape[1]
+        I["U"] = U
+        I["dec_ids"] = dec_ids.contiguous().view(-1)
+        I["dmask"] = dec_mask.float().contiguous() if dec_mask is not None else None
+        _, logits = self.decoder(None, I, kv=st["kv"])
+        loss, lv, _ = self._ce(logits, labels, Bn, U, loss_reduction)
+        self._last_decode = None                  # the decode scratch behind the mark has been overwritten
+        return loss.clone(), lv.to(torch.float32, copy=True)

@@ -78,8 +78,7 @@ def main():
         arena_gb = sum(c.numel() for c in eng.arena.chunks) / 2.0 ** 30
 
         def encoder_only():
-            eng._begin(dev, False)
-            eng.train = False
+            eng._begin(dev, False, inference=True)
             I = eng._inputs(feats, loc, imask, ids, segs, att, ids.new_zeros(B, 1), None)
             return eng.encoder(I)
 
