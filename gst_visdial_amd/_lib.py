@@ -80,6 +80,21 @@ class NspHeadDesc(C.Structure):
                 ("kernel_name", _vp), ("kernel_name_len", _i32), ("reserved_", _i32)]
 
 
+class NspTrainDesc(C.Structure):
+    """gstvd_nsp_train_t: the NSP head in training form -- forward with dropout, saved pt / pv / keep flags and the soft-label
+    loss; backward down to the gradients in front of the two pooler ReLUs."""
+    _fields_ = [("xt", _vp), ("ldt", _i64), ("t_rows", _i64), ("xv", _vp), ("ldv", _i64), ("v_rows", _i64),
+                ("wt", _vp), ("ldwt", _i64), ("wv", _vp), ("ldwv", _i64),
+                ("bt", _vp), ("bv", _vp), ("wn", _vp), ("ldwn", _i64), ("bn", _vp),
+                ("labels", _vp), ("ldl", _i64),
+                ("z", _vp), ("ldz", _i64),
+                ("pt", _vp), ("pv", _vp), ("keep", _vp), ("row_loss", _vp), ("stats", _vp),
+                ("gscale", _vp), ("dwn", _vp), ("lddwn", _i64), ("dbn", _vp), ("dpt", _vp), ("dpv", _vp), ("lddp", _i64),
+                ("rng", _vp), ("p", _f32), ("site", _u32),
+                ("B", _i32), ("H", _i32), ("Hv", _i32), ("Hb", _i32), ("dtype", _i32), ("fusion", _i32), ("acc_w", _i32), ("acc_b", _i32),
+                ("kernel_name", _vp), ("kernel_name_len", _i32), ("reserved_", _i32)]
+
+
 class ColsumEntry(C.Structure):
     _fields_ = [("partial", _vp), ("out", _vp * 3), ("nblk", _i64), ("stride", _i64), ("H", _i64),
                 ("nvec", _i32), ("accumulate", _i32 * 3), ("blk0", _i32)]
@@ -134,6 +149,13 @@ SIGNATURES = {
     "gstvd_gemm_grouped_adamw": (_i32, [_vp, _vp, _i64, _i64, C.POINTER(AdamFuse), _vp, _i64, _vp]),
     "gstvd_gemm_grouped_adamw_kernel_name": (_i32, [C.c_char_p, _i32]),
     "gstvd_nsp_head": (_i32, [C.POINTER(NspHeadDesc), _vp]),
+    "gstvd_rows_gather": (_i32, [_vp, _i64, _i64, _vp, _i64, _i64, _i32, _vp, _i64, _vp]),
+    "gstvd_rows_scatter": (_i32, [_vp, _i64, _vp, _i64, _i64, _i32, _vp, _i64, _i64, _i32, _vp]),
+    "gstvd_rows_mul": (_i32, [_vp, _i64, _vp, _i64, _i64, _i64, _i32, _vp]),
+    "gstvd_kl_fwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp]),
+    "gstvd_kl_bwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _vp, _i64, _vp]),
+    "gstvd_nsp_train_fwd": (_i32, [C.POINTER(NspTrainDesc), _vp]),
+    "gstvd_nsp_train_bwd": (_i32, [C.POINTER(NspTrainDesc), _vp]),
 }
 
 _STATUS = {-1: "GSTVD_E_DTYPE", -2: "GSTVD_E_SHAPE", -3: "GSTVD_E_ALIGN", -4: "GSTVD_E_NULL", -5: "GSTVD_E_UNSUPPORTED"}

@@ -69,6 +69,9 @@ class BertConfig(_Cfg):
             raise NotImplementedError("with_coattention=False is not on the enc_dec_a path")
         if self.hidden_act != "gelu" or self.v_hidden_act != "gelu":
             raise NotImplementedError("only the erf GELU of the shipped configs is implemented")
+        if self.predict_feature and "enc_dec" not in str(getattr(self, "model_arch", "enc_dec")):
+            raise NotImplementedError("predict_feature=True (the MSE region loss of models/vilbert_dialog.py:1489-1493) is not "
+                                      "implemented; the shipped configs use the KL form")
 
 
 class DecoderConfig(_Cfg):

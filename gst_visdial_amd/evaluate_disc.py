@@ -1,5 +1,5 @@
-"""Discriminative evaluation: the build's counterpart of evaluate_disc.evaluate (evaluate_disc.py:27-118) and of the eval
-branch of train_disc.forward (train_disc.py:27-124) for a `VisualDialogEncoder` with model = 'enc_only_a'.
+"""Discriminative evaluation and training step: the build's counterpart of evaluate_disc.evaluate (evaluate_disc.py:27-118) and
+of train_disc.forward, both branches (train_disc.py:27-124), for a `VisualDialogEncoder` with model = 'enc_only_a'.
 
 Same batch contract (per-dialog tensors [B, rounds, options, L] from the disc eval dataloader; image tensors once per dialog)
 and the same metrics.  Two things differ, neither changes a result:
@@ -59,11 +59,58 @@ def _prepare(item, params):
     return tokens, features, spatials, sep_indices, segments, mask, att, image_mask
 
 
+def train_rows(batch, params):
+    """The host index work of train_disc.forward's train branch (train_disc.py:43-85): `batch_size` rows drawn with
+    torch.randperm from the flattened [dialog, round, sample] rows, the text / label tensors of those rows, and the image
+    tensors of each row's dialog.  The image tensors (image_feat, image_loc, image_mask, image_target, image_label) may come
+    in the layout the reference builds (expanded to one copy per row, train_disc.py:266-276) or once per dialog: then row r
+    takes those of dialog r // (rounds * samples) by index -- image_target is [37, 1601] fp32 per dialog, and its copy x rounds
+    x samples per step is the largest host-to-device transfer of the reference's loop.  Also returns the flat indices of the
+    masked tokens (label != -1) and regions (label == 1), computed here on the host: the device step needs no sync for them."""
+    flat = lambda k: batch[k].reshape(-1, batch[k].shape[-1])
+    hist_len = batch["hist_len"].reshape(-1)
+    n = hist_len.shape[0]
+    sample_indices = torch.randperm(n)[:params["batch_size"]]
+    out = dict(sample_indices=sample_indices, hist_len=hist_len[sample_indices])
+    for k in ("tokens", "segments", "sep_indices", "mask", "next_sentence_labels"):
+        out[k] = flat(k)[sample_indices, :]
+    per_dialog = batch["image_feat"].dim() == 3
+    if per_dialog:
+        dialogs = batch["image_feat"].shape[0]
+        if n % dialogs:
+            raise ValueError("%d rows do not divide into %d dialogs" % (n, dialogs))
+        pick = sample_indices // (n // dialogs)
+    out["dialog_of_row"] = pick if per_dialog else None
+    for k, tail in (("image_feat", 2), ("image_loc", 2), ("image_mask", 1), ("image_target", 2), ("image_label", 1)):
+        x = batch[k]
+        out[k] = x[pick] if per_dialog else x.reshape(-1, *x.shape[-tail:])[sample_indices]
+    out["token_rows"] = (out["mask"].reshape(-1) != -1).nonzero().view(-1)
+    out["region_rows"] = (out["image_label"].reshape(-1) == 1).nonzero().view(-1)
+    return out
+
+
+def _forward_train(encoder, batch, params):
+    """Train branch of train_disc.forward: sampled rows -> the encoder's three losses -> means, coefficients, their sum."""
+    dev = params["device"]
+    r = {k: (v.to(dev) if torch.is_tensor(v) else v) for k, v in train_rows(batch, params).items()}
+    att = sequence_mask(sequence_lengths(r["sep_indices"], r["hist_len"]), r["tokens"].shape[1])
+    lm_loss, img_loss, nsp_loss, nsp_scores, lm_scores, _, _ = encoder(
+        r["tokens"], r["image_feat"], r["image_loc"], sep_indices=r["sep_indices"], token_type_ids=r["segments"],
+        masked_lm_labels=r["mask"], attention_mask=att, next_sentence_label=r["next_sentence_labels"],
+        image_attention_mask=r["image_mask"], image_label=r["image_label"], image_target=r["image_target"],
+        token_rows=r["token_rows"], region_rows=r["region_rows"])
+    lm_loss = params["lm_loss_coeff"] * lm_loss.mean()
+    nsp_loss = params["nsp_loss_coeff"] * nsp_loss.mean()
+    img_loss = params["img_loss_coeff"] * img_loss.mean()
+    return lm_loss + nsp_loss + img_loss, lm_loss, nsp_loss, img_loss, nsp_scores, lm_scores
+
+
 def forward_disc(encoder, item, params):
-    """Eval branch of train_disc.forward -> its 6-tuple (loss, lm_loss, nsp_loss, img_loss, nsp_scores, lm_scores): the losses
-    are None as there, and so is lm_scores (the MLM logits are not computed; modules.VisualDialogEncoder)."""
+    """train_disc.forward -> its 6-tuple (loss, lm_loss, nsp_loss, img_loss, nsp_scores, lm_scores).  Eval modes: the losses are
+    None as there.  Train modes: the weighted losses and their sum, differentiable.  lm_scores is None in both (the MLM logits
+    over all tokens are not materialised; modules.VisualDialogEncoder)."""
     if "train" in params["mode"]:
-        raise NotImplementedError("forward_disc is the eval branch of train_disc.forward; train_disc.py is out of scope")
+        return _forward_train(encoder, item, params)
     tokens, features, spatials, sep_indices, segments, mask, att, image_mask = _prepare(item, params)
     _, _, _, nsp_scores, lm_scores, _, _ = encoder(tokens, features, spatials, sep_indices=sep_indices, token_type_ids=segments,
                                                    masked_lm_labels=mask, attention_mask=att, image_attention_mask=image_mask)

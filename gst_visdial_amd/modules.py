@@ -1,4 +1,4 @@
-"""Host-side mirror of the reference's module API for the enc_dec_a path and for inference of the enc_only_a model.
+"""Host-side mirror of the reference's module API for the enc_dec_a path and for the enc_only_a model (ranking and training).
 
 `VisualDialogEncoder`, `VisualDialogDecoder`, `EncoderDecoderModel`, `VLFusion` keep the constructor and
 forward signatures, return conventions and the `state_dict()` key layout of
@@ -277,11 +277,16 @@ class VisualDialogEncoder(nn.Module):
     """models/visual_dialog_encoder.py:7-76.  `params` is held by reference and re-read on every call.
 
     model = 'enc_dec_*': the encoder half of an EncoderDecoderModel (hidden states out).
-    model = 'enc_only_a': the discriminative model of evaluate_disc.py, INFERENCE only.  The module owns an encoder-only engine
-    and `forward` returns the reference's 7-tuple with `seq_relationship_score` [B, 2] fp32 in place 3 and None everywhere
-    else -- including `prediction_scores_t`, the MLM logits over all B*T tokens (6 GB at 200 x 256 x 30522), which the
-    reference computes and its only caller discards (evaluate_disc.py:79): deliberately not computed here.  train_disc.py (the
-    MLM / masked-region / NSP losses, their backward) is out of scope: a train mode or a module in training state raises."""
+    model = 'enc_only_a': the discriminative model of evaluate_disc.py / train_disc.py.  The module owns an encoder-only engine.
+    Under an eval mode `forward` returns the reference's 7-tuple with `seq_relationship_score` [B, 2] fp32 in place 3 and None
+    everywhere else -- including `prediction_scores_t`, the MLM logits over all B*T tokens (6 GB at 200 x 256 x 30522), which
+    the reference computes and its only caller discards (evaluate_disc.py:79): deliberately not computed here.
+    Under a mode containing 'train' (params['mode'] decides the branch, as in the reference; the module's `.training` decides
+    dropout) and with masked_lm_labels, next_sentence_label, image_label and image_target all given, it returns
+    (lm_loss [1], img_loss [1], nsp_loss [1], seq_relationship_score, None, None, None): the three unscaled losses of
+    models/vilbert_dialog.py:1496-1510, differentiable -- `loss.backward()` fills `.grad` of every parameter but
+    sep_embeddings and q_dense* (Engine.disc_step).  A train-mode call without those four labels, and a module left in
+    training state under an eval mode, raise."""
 
     def __init__(self, params):
         super().__init__()
@@ -293,8 +298,8 @@ class VisualDialogEncoder(nn.Module):
         self.config.validate()
         self.model_arch = params["model"]
         if "enc_dec" not in self.model_arch and self.model_arch != "enc_only_a":
-            raise NotImplementedError("gst_visdial_amd implements the enc_dec_* generative path and inference of the "
-                                      "discriminative enc_only_a model only (model=%r)" % self.model_arch)
+            raise NotImplementedError("gst_visdial_amd implements the enc_dec_* generative path and the discriminative "
+                                      "enc_only_a model only (model=%r)" % self.model_arch)
         # the reference calls from_pretrained('bert-base-uncased') (network); here weights come from
         # load_state_dict / a checkpoint, with BERT-style N(0, 0.02) init as the starting point
         self.bert_pretrained = BertForMultiModalPreTraining(self.config)
@@ -320,9 +325,9 @@ class VisualDialogEncoder(nn.Module):
         mode = self.params["mode"]
         if "train" in mode or self.training:
             raise NotImplementedError(
-                "gst_visdial_amd runs the enc_only_a model for inference only (evaluate_disc.py): mode=%r, module.training=%s.  "
-                "train_disc.py -- the MLM, masked-region and NSP losses, their backward and optimizer -- is out of scope; use an "
-                "eval mode and call .eval()" % (mode, self.training))
+                "the ranking branch of the enc_only_a model (evaluate_disc.py) needs an eval mode and .eval(): mode=%r, "
+                "module.training=%s.  The training branch of train_disc.py is forward(...) under a 'train' mode with "
+                "masked_lm_labels, next_sentence_label, image_label and image_target" % (mode, self.training))
 
     def nsp_scores(self, input_ids, image_feat, image_loc, token_type_ids=None, attention_mask=None, image_attention_mask=None):
         """enc_only_a: (seq_relationship_score [B, 2], softmax(score, 1)[:, 0] [B]), both fp32, the second straight from the
@@ -332,7 +337,21 @@ class VisualDialogEncoder(nn.Module):
 
     def forward(self, input_ids, image_feat, image_loc, sep_indices=None, token_type_ids=None, attention_mask=None,
                 masked_lm_labels=None, next_sentence_label=None, image_attention_mask=None, image_label=None,
-                image_target=None):
+                image_target=None, token_rows=None, region_rows=None):
+        """enc_only_a, train mode: `token_rows` / `region_rows` (not in the reference's signature, optional) are the flat indices
+        of the tokens with masked_lm_labels != -1 and of the regions with image_label == 1, which a caller that still has the
+        labels on the host passes along (evaluate_disc.forward_disc does).  Without them the two index lists are taken from
+        the device tensors with `nonzero`: one host synchronisation each per call."""
+        if self.model_arch == "enc_only_a" and "train" in self.params["mode"]:
+            # train branch of models/visual_dialog_encoder.py:51-57
+            if masked_lm_labels is None or next_sentence_label is None or image_label is None or image_target is None:
+                raise NotImplementedError(
+                    "the train branch of the enc_only_a model (train_disc.py) needs masked_lm_labels, next_sentence_label, "
+                    "image_label and image_target; without them there is no loss to return (mode=%r)" % (self.params["mode"],))
+            lm, img, nsp, score = self.engine.disc_step(image_feat, image_loc, image_attention_mask, input_ids, token_type_ids,
+                                                        attention_mask, masked_lm_labels, next_sentence_label, image_label,
+                                                        image_target, token_rows=token_rows, region_rows=region_rows)
+            return (lm, img, nsp, score, None, None, None)
         if self.model_arch == "enc_only_a":
             # eval branch of models/visual_dialog_encoder.py:68-76; sep_indices / masked_lm_labels feed nothing in it
             score, _ = self.nsp_scores(input_ids, image_feat, image_loc, token_type_ids, attention_mask, image_attention_mask)

@@ -838,6 +838,136 @@ def nsp_head(xt, t_rows, xv, v_rows, wt, bt, wv, bv, wn, bn, B, fusion, z, prob0
     return z, prob0
 
 
+def _i64_index(idx, n):
+    if idx.dtype != torch.int64 or idx.dim() != 1 or not idx.is_contiguous() or idx.numel() != n or n <= 0:
+        raise L.GstvdError("row index: a contiguous int64 vector with one entry per compacted row (at least one) is needed")
+
+
+def rows_gather(src, idx, dst, M=None):
+    """dst[i, :] = src[idx[i], :] (gstvd_rows_gather): src [>= M, H] with any row stride, dst [n, H]."""
+    lib = L.load()
+    n, H = dst.shape
+    _i64_index(idx, n)
+    if src.dtype != dst.dtype or src.shape[1] != H or src.stride(1) != 1 or dst.stride(1) != 1:
+        raise L.GstvdError("rows_gather: source and destination must share dtype and width, with dense rows")
+    M = src.shape[0] if M is None else M
+    e0 = _prof_begin()
+    L.check("gstvd_rows_gather", lib.gstvd_rows_gather(_p(src), src.stride(0), M, _p(idx), n, H, dt(src), _p(dst), dst.stride(0), _stream()))
+    _prof_end(e0, "rows_gather", 0.0, 2.0 * n * H * src.element_size(), (n, H))
+    return dst
+
+
+def rows_scatter(src, idx, dst, accumulate, M=None):
+    """dst[idx[i], :] (=|+=) src[i, :] (gstvd_rows_scatter), idx distinct.  accumulate False: the first writer of `dst` -- rows
+    [0, M) that no index names are zero filled."""
+    lib = L.load()
+    n, H = src.shape
+    _i64_index(idx, n)
+    if src.dtype != dst.dtype or dst.shape[1] != H or src.stride(1) != 1 or dst.stride(1) != 1:
+        raise L.GstvdError("rows_scatter: source and destination must share dtype and width, with dense rows")
+    M = dst.shape[0] if M is None else M
+    e0 = _prof_begin()
+    L.check("gstvd_rows_scatter", lib.gstvd_rows_scatter(_p(src), src.stride(0), _p(idx), n, H, dt(src), _p(dst), dst.stride(0), M,
+                                                         int(bool(accumulate)), _stream()))
+    _prof_end(e0, "rows_scatter", 0.0, float((3 * n if accumulate else 2 * n + M) * H * src.element_size()), (n, H))
+    return dst
+
+
+def rows_mul_(x, a, M, N):
+    """x[:M, :N] *= a[:M, :N] in place (gstvd_rows_mul)."""
+    lib = L.load()
+    if x.dtype != a.dtype:
+        raise L.GstvdError("rows_mul_: operands must share one dtype")
+    e0 = _prof_begin()
+    L.check("gstvd_rows_mul", lib.gstvd_rows_mul(_p(x), x.stride(-2), _p(a), a.stride(-2), M, N, dt(x), _stream()))
+    _prof_end(e0, "rows_mul", 0.0, 3.0 * M * N * x.element_size(), (M, N))
+
+
+def kl_fwd(scores, target, rows, C, row_loss, lse, stats, target_row=None, labels=None):
+    """Masked-region loss (gstvd_kl_fwd): scores [rows, >= C] fp32 / bf16, target fp32 [*, >= C] (row i of the scores belongs to
+    target row target_row[i], or i)."""
+    lib = L.load()
+    if target.dtype != torch.float32 or target.stride(-1) != 1 or scores.stride(-1) != 1:
+        raise L.GstvdError("kl_fwd: the target is fp32, rows dense")
+    e0 = _prof_begin()
+    L.check("gstvd_kl_fwd", lib.gstvd_kl_fwd(_p(scores), scores.stride(-2), _p(target), target.stride(-2), _p(target_row), _p(labels),
+                                             rows, C, dt(scores), _p(row_loss), _p(lse), _p(stats), _stream()))
+    _prof_end(e0, "kl_fwd", 0.0, float(rows) * C * (3 * scores.element_size() + 4), (rows, C))
+
+
+def kl_bwd(scores, target, lse, stats, gscale, mean, rows, C, dscores, target_row=None, labels=None):
+    lib = L.load()
+    if dscores.dtype != scores.dtype or dscores.stride(-1) != 1:
+        raise L.GstvdError("kl_bwd: the gradient has the scores' dtype, rows dense")
+    e0 = _prof_begin()
+    L.check("gstvd_kl_bwd", lib.gstvd_kl_bwd(_p(scores), scores.stride(-2), _p(target), target.stride(-2), _p(target_row), _p(labels),
+                                             _p(lse), _p(stats), _p(gscale), int(mean), rows, C, dt(scores), _p(dscores),
+                                             dscores.stride(-2), _stream()))
+    _prof_end(e0, "kl_bwd", 0.0, float(rows) * C * (2 * scores.element_size() + 8), (rows, C))
+
+
+def nsp_train_desc(xt, t_rows, xv, v_rows, wt, bt, wv, bv, wn, bn, labels, B, fusion, z, pt, pv, keep, row_loss, stats, p=0.0,
+                   site=0, rng=None):
+    """Descriptor of the NSP head in training form (gstvd_nsp_train_t), forward half; nsp_train_bwd fills in the rest.  Operands
+    as ops.nsp_head; labels [B, 2] fp32 (soft), pt / pv [B, Hb] fp32 and keep [B, Hb] uint8 are written for backward."""
+    if fusion not in FUSION:
+        raise L.GstvdError("nsp_train: fusion_method must be 'mul' or 'sum', got %r" % (fusion,))
+    Hb = wt.shape[0]
+    if wt.dtype != xt.dtype or wv.dtype != xt.dtype or xv.dtype != xt.dtype:
+        raise L.GstvdError("nsp_train: activations and pooler weights must share one dtype")
+    for t in (bt, bv, wn, bn, z, labels, pt, pv, row_loss, stats):
+        if t.dtype != torch.float32:
+            raise L.GstvdError("nsp_train: biases, the classifier, the labels and the outputs are fp32")
+    if xt.shape[0] < B * t_rows or xv.shape[0] < B * v_rows or z.shape[0] < B or tuple(labels.shape) != (B, 2) or labels.stride(1) != 1 \
+            or z.stride(-1) != 1 or xt.stride(-1) != 1 or xv.stride(-1) != 1 or wt.stride(-1) != 1 or wv.stride(-1) != 1 \
+            or wn.stride(-1) != 1 or bt.numel() != Hb or bv.numel() != Hb or wv.shape[0] != Hb or tuple(wn.shape) != (2, Hb) \
+            or bn.numel() != 2 or keep.dtype != torch.uint8 or row_loss.numel() < B or stats.numel() < 3 \
+            or any(tuple(t.shape) != (B, Hb) or not t.is_contiguous() for t in (pt, pv, keep)):
+        raise L.GstvdError("nsp_train: operand shapes do not match")
+    d = L.NspTrainDesc()
+    d.xt, d.ldt, d.t_rows = _p(xt), xt.stride(0), t_rows
+    d.xv, d.ldv, d.v_rows = _p(xv), xv.stride(0), v_rows
+    d.wt, d.ldwt, d.wv, d.ldwv = _p(wt), wt.stride(0), _p(wv), wv.stride(0)
+    d.bt, d.bv, d.wn, d.ldwn, d.bn = _p(bt), _p(bv), _p(wn), wn.stride(0), _p(bn)
+    d.labels, d.ldl = _p(labels), labels.stride(0)
+    d.z, d.ldz = _p(z), z.stride(0)
+    d.pt, d.pv, d.keep, d.row_loss, d.stats = _p(pt), _p(pv), _p(keep), _p(row_loss), _p(stats)
+    d.p, d.site = float(p), int(site)
+    d.rng = rng.ptr() if (rng is not None and p > 0) else None
+    d.B, d.H, d.Hv, d.Hb = B, wt.shape[1], wv.shape[1], Hb
+    d.dtype, d.fusion = dt(xt), FUSION[fusion]
+    d._keep = (xt, xv, wt, bt, wv, bv, wn, bn, labels, z, pt, pv, keep, row_loss, stats)
+    return d
+
+
+def nsp_train_fwd(d):
+    lib = L.load()
+    e0 = _prof_begin()
+    buf = C.create_string_buffer(256) if e0 is not None else None
+    if buf is not None:
+        d.kernel_name, d.kernel_name_len = C.addressof(buf), 256
+    L.check("gstvd_nsp_train_fwd", lib.gstvd_nsp_train_fwd(C.byref(d), _stream()))
+    d.kernel_name, d.kernel_name_len = None, 0
+    if e0 is not None:
+        _prof_end(e0, "nsp_train_fwd:" + buf.value.decode(), 2.0 * d.B * d.Hb * (d.H + d.Hv + 2), 0.0, (d.B, d.H, d.Hv, d.Hb))
+
+
+def nsp_train_bwd(d, gscale, dwn, dbn, dpt, dpv, acc_w=False, acc_b=False):
+    """Backward of gscale[0] * (mean soft-label loss) of descriptor `d` (after nsp_train_fwd): dwn [2, Hb], dbn [2] fp32 (=|+=),
+    dpt / dpv [B, Hb] in the activations' dtype = the gradients in front of the two pooler ReLUs."""
+    lib = L.load()
+    if dwn.dtype != torch.float32 or dbn.dtype != torch.float32 or tuple(dwn.shape) != (2, d.Hb) or dbn.numel() != 2 \
+            or dwn.stride(1) != 1 or dpt.dtype != dpv.dtype or _DT[dpt.dtype] != d.dtype or tuple(dpt.shape) != (d.B, d.Hb) \
+            or tuple(dpv.shape) != (d.B, d.Hb) or dpt.stride(1) != 1 or dpv.stride(1) != 1 or dpt.stride(0) != dpv.stride(0):
+        raise L.GstvdError("nsp_train_bwd: operand shapes do not match")
+    d.gscale, d.dwn, d.lddwn, d.dbn = _p(gscale), _p(dwn), dwn.stride(0), _p(dbn)
+    d.dpt, d.dpv, d.lddp = _p(dpt), _p(dpv), dpt.stride(0)
+    d.acc_w, d.acc_b = int(bool(acc_w)), int(bool(acc_b))
+    e0 = _prof_begin()
+    L.check("gstvd_nsp_train_bwd", lib.gstvd_nsp_train_bwd(C.byref(d), _stream()))
+    _prof_end(e0, "nsp_train_bwd", 8.0 * d.B * d.Hb, 14.0 * d.B * d.Hb, (d.B, d.Hb))
+
+
 def vl_split(d_enc, B, R, T, H, d_v, d_t, p, site_v, site_t, rng):
     lib = L.load()
     L.check("gstvd_vl_split", lib.gstvd_vl_split(_p(d_enc), B, R, T, H, dt(d_enc), _p(d_v), _p(d_t), p, site_v, site_t,

@@ -99,8 +99,11 @@ class FlatParams(object):
         self.off = 0
         H, Hv, Hb = enc_cfg.hidden_size, enc_cfg.v_hidden_size, enc_cfg.bi_hidden_size
         if self.enc_only:
-            dec_cfg = gen = lm_w = None       # no decoder slots, no LM head: the word table keeps its own row count
-            self.Vp = 0
+            # no decoder slots; the MLM head of train_disc.py is tied to the word table (models/vilbert_dialog.py:991) the way the
+            # enc_dec LM head is after train_gen.py:293, so the table gets the same row padding the head's GEMM needs
+            dec_cfg = gen = None
+            self.Vp = _round_up(enc_cfg.vocab_size, 64)
+            lm_w = encoder.bert_pretrained.cls.predictions.decoder.weight
         else:
             dec_cfg = model.decoder.config
             gen = model.decoder.decoder
@@ -184,13 +187,30 @@ class FlatParams(object):
                 ffn(p, c.v_intermediate, c.v_output, ".vfi", ".vfo", ".vln")
                 ffn(p, c.t_intermediate, c.t_output, ".tfi", ".tfo", ".tln")
         if self.enc_only:
-            # the NSP head (models/vilbert_dialog.py:915-941,1038) is live here; cls.predictions.*, cls.imagePredictions.*,
-            # sep_embeddings and q_dense* stay in the dead buffer, as in the enc_dec form
+            # the three heads of BertPreTrainingHeads (models/vilbert_dialog.py:915-1055) are live here: NSP for ranking and
+            # training, cls.predictions.* / cls.imagePredictions.* for training (Engine.disc_step); sep_embeddings and q_dense*
+            # stay in the dead buffer, as in the enc_dec form
             cls = encoder.bert_pretrained.cls
             self.marks["nsp"] = _round_up(self.off, 64)
             place("pool.t.w", [bert.t_pooler.dense.weight]); place("pool.t.b", [bert.t_pooler.dense.bias])
             place("pool.v.w", [bert.v_pooler.dense.weight]); place("pool.v.b", [bert.v_pooler.dense.bias])
             place("nsp.w", [cls.bi_seq_relationship.weight]); place("nsp.b", [cls.bi_seq_relationship.bias])
+            self.marks["mlm"] = _round_up(self.off, 64)
+            tr = cls.predictions.transform
+            place("mlm.tr.w", [tr.dense.weight]); place("mlm.tr.b", [tr.dense.bias])
+            place("mlm.ln.w", [tr.LayerNorm.weight]); place("mlm.ln.b", [tr.LayerNorm.bias])
+            if id(lm_w) in self.placed:
+                self.slots["mlm.dec.w"] = self.slots["emb.word"]         # the tied decoder: an alias, one gradient slot
+            else:
+                place("mlm.dec.w", [lm_w], shape=(self.Vp, lm_w.shape[1]), pad_rows_to=self.Vp)
+            place("mlm.b", [cls.predictions.bias], shape=(self.Vp,), pad_rows_to=self.Vp)
+            self.marks["imgp"] = _round_up(self.off, 64)
+            ip = cls.imagePredictions
+            self.Cp = _round_up(ip.decoder.weight.shape[0], 64)
+            place("imgp.tr.w", [ip.transform.dense.weight]); place("imgp.tr.b", [ip.transform.dense.bias])
+            place("imgp.ln.w", [ip.transform.LayerNorm.weight]); place("imgp.ln.b", [ip.transform.LayerNorm.bias])
+            place("imgp.dec.w", [ip.decoder.weight], shape=(self.Cp, Hv), pad_rows_to=self.Cp)
+            place("imgp.dec.b", [ip.decoder.bias], shape=(self.Cp,), pad_rows_to=self.Cp)
             self._finish(model, precision)
             return
         self.marks["vlf"] = _round_up(self.off, 64)
@@ -252,13 +272,22 @@ class FlatParams(object):
         for p, off in self.items:
             p.data = P[off:off + p.numel()].view(p.shape)
         self.P, self.D = P, D
-        # (encoder-only form: inference only -- no gradient buffer, no gradient views)
-        self.G = None if self.enc_only else torch.zeros(self.n_live, dtype=torch.float32, device=device)
+        # (encoder-only form: no gradient buffer, no gradient views until the first training call -- `ensure_grads`)
+        self.G, self.grad_views = None, []
+        if not self.enc_only:
+            self.ensure_grads()
         self.S = torch.empty(self.n_live, dtype=torch.bfloat16, device=device) if self.precision == "bf16" else None
-        self.grad_views = [] if self.enc_only else [self.G[off:off + p.numel()].view(p.shape) for p, off in self.items]
         self.ptrs = [(p, P[off:off + p.numel()].data_ptr()) for p, off in self.items]
         self.shadow_version = None
         self.device = device
+
+    def ensure_grads(self):
+        """The flat gradient buffer and the per-parameter views of it; -> True when this call made them."""
+        if self.G is not None:
+            return False
+        self.G = torch.zeros(self.n_live, dtype=torch.float32, device=self.P.device)
+        self.grad_views = [self.G[off:off + p.numel()].view(p.shape) for p, off in self.items]
+        return True
 
     def is_materialized(self):
         if self.P is None:

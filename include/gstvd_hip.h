@@ -385,6 +385,62 @@ typedef struct {
 } gstvd_nsp_head_t;
 int gstvd_nsp_head(const gstvd_nsp_head_t* a, gstvd_stream_t s);
 
+/* ---- training heads of the enc_only model (train_disc.py; entry points added, no signature changed: ABI stays 9) --------------
+ * Row compaction.  The MLM and masked-region losses read only the masked rows; every other row's gradient is exactly zero, so
+ * the heads run on the gathered rows and the [B*T, vocab] logits of the reference never exist.
+ *   gather : dst[i, 0..H) = src[idx[i], 0..H),  i < n            (src [M, lds >= H], dst [n, ldd >= H]; idx outside [0, M): zeros)
+ *   scatter: dst[idx[i], 0..H) (=|+=) src[i, 0..H)               (dst [M, ldd]; idx distinct -- one writer per row, no atomics)
+ *            accumulate = 0: the FIRST writer of dst -- every row of dst[0..M) that no index names is zero filled;
+ *            accumulate = 1: adds to what dst holds (the pooler also sends a gradient to row 0 of every batch row).
+ * H % 4 == 0, strides % 4 == 0, n >= 1 (a zero-row launch is the caller's to skip). */
+int gstvd_rows_gather(const void* src, int64_t lds, int64_t M, const int64_t* idx, int64_t n, int64_t H, int32_t dtype,
+                      void* dst, int64_t ldd, gstvd_stream_t s);
+int gstvd_rows_scatter(const void* src, int64_t lds, const int64_t* idx, int64_t n, int64_t H, int32_t dtype, void* dst,
+                       int64_t ldd, int64_t M, int32_t accumulate, gstvd_stream_t s);
+
+/* x[m, 0..N) *= a[m, 0..N) in place (both dtype, N % 4 == 0): d(GELU output) -> d(pre-activation) with the gelu' that the
+ * GSTVD_EPI_GELU epilogue saved, for the head transforms whose LayerNorm follows the GELU directly (vilbert_dialog.py:955-959). */
+int gstvd_rows_mul(void* x, int64_t ldx, const void* a, int64_t lda, int64_t M, int64_t N, int32_t dtype, gstvd_stream_t s);
+
+/* Masked-region loss (models/vilbert_dialog.py:1496-1501): per row i of scores [rows, lds >= C] (dtype) against the fp32 target
+ * row target[(target_row ? target_row[i] : i) * ldt + 0..C):
+ *   row_loss[i] = sum_c t * (log t - log_softmax(scores[i])[c]), terms with t == 0 exactly 0 (torch.xlogy);  lse[i] saved;
+ *   labels (int64 [rows] or NULL = all rows count): rows whose label != 1 give 0 and are not counted;
+ *   stats[0] = sum_i row_loss[i], stats[1] = counted rows, stats[2] = stats[0] / stats[1]    (one block, fixed order).
+ * Backward: dscores[i, c] = scale * (softmax(scores[i])[c] * sum_c t - t[c]), scale = gscale[0] (NULL: 1), / stats[1] with
+ * `mean`; the row's ACTUAL target sum is used; columns [C, ldd) are zero filled.  Any C (1601: the tail is handled inside). */
+int gstvd_kl_fwd(const void* scores, int64_t lds, const float* target, int64_t ldt, const int64_t* target_row,
+                 const int64_t* labels, int64_t rows, int64_t C, int32_t dtype, float* row_loss, float* lse, float* stats,
+                 gstvd_stream_t s);
+int gstvd_kl_bwd(const void* scores, int64_t lds, const float* target, int64_t ldt, const int64_t* target_row,
+                 const int64_t* labels, const float* lse, const float* stats, const float* gscale, int32_t mean,
+                 int64_t rows, int64_t C, int32_t dtype, void* dscores, int64_t ldd, gstvd_stream_t s);
+
+/* NSP head, training form (models/vilbert_dialog.py:1026-1041,1509-1510).  Forward = gstvd_nsp_head's arithmetic in the same
+ * order (p = 0: the same z bits) with the Dropout(p) of BertPreTrainingHeads on the fused value, drawn at element b * Hb + n of
+ * (rng, site), plus the soft-label loss:
+ *   z = Wn drop(f) + bn;  row_loss[b] = -(l[b,0] * log_softmax(z[b])[0] + l[b,1] * log_softmax(z[b])[1]),  labels [B, ldl >= 2] fp32
+ *   stats = (sum_b row_loss, B, sum / B);  saved for backward: pt, pv [B, Hb] fp32 (dense), keep [B, Hb] uint8 (1 = kept).
+ * Backward of gscale[0] * stats[2] (gscale NULL: 1):
+ *   dwn [2, lddwn], dbn [2] (=|+=, acc_w / acc_b), and the gradients in front of the two ReLUs dpt, dpv [B, lddp] (dtype);
+ *   the labels' row sums are used as they are (soft labels [s, 1 - s], not assumed to add up to 1).
+ * Constraints as gstvd_nsp_head; 0 <= p < 1.  The backward entry reads pt .. labels, wn, gscale and writes dwn .. dpv only. */
+typedef struct {
+  const void* xt; int64_t ldt; int64_t t_rows;
+  const void* xv; int64_t ldv; int64_t v_rows;
+  const void* wt; int64_t ldwt; const void* wv; int64_t ldwv;
+  const float* bt; const float* bv; const float* wn; int64_t ldwn; const float* bn;
+  const float* labels; int64_t ldl;
+  float* z; int64_t ldz;
+  float* pt; float* pv; uint8_t* keep; float* row_loss; float* stats;
+  const float* gscale; float* dwn; int64_t lddwn; float* dbn; void* dpt; void* dpv; int64_t lddp;
+  const uint64_t* rng; float p; uint32_t site;
+  int32_t B, H, Hv, Hb, dtype, fusion, acc_w, acc_b;
+  char* kernel_name; int32_t kernel_name_len; int32_t reserved_;
+} gstvd_nsp_train_t;
+int gstvd_nsp_train_fwd(const gstvd_nsp_train_t* a, gstvd_stream_t s);
+int gstvd_nsp_train_bwd(const gstvd_nsp_train_t* a, gstvd_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
