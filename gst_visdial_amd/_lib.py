@@ -135,6 +135,8 @@ SIGNATURES = {
     "gstvd_attn_kernel_name": (_i32, [C.POINTER(AttnDesc), _i32, C.c_char_p, _i32]),
     "gstvd_ce_fwd": (_i32, [_vp, _i64, _vp, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp]),
     "gstvd_ce_bwd": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i64, _i32, _vp, _i64, _vp]),
+    "gstvd_ce_bwd_rows": (_i32, [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp, _i64, _vp]),
+    "gstvd_fgsm_step": (_i32, [_vp, _vp, _f32, _vp, _i64, _vp]),
     "gstvd_answer_scores": (_i32, [_vp, _i64, _vp, _vp, _i64, _i64, _i32, _vp, _vp]),
     "gstvd_sample_topk": (_i32, [C.POINTER(SampleDesc), _vp]),
     "gstvd_vl_split": (_i32, [_vp, _i64, _i64, _i64, _i64, _i32, _vp, _vp, _f32, _u32, _u32, _vp, _vp]),

@@ -1,0 +1,203 @@
+"""FGSM attack evaluation: the build's counterpart of evaluate_gen_attack.py with `-attack fgsm`.
+
+The attack (evaluate_gen_attack.py:92-165) perturbs the image features of ONE dialog round per dialog -- the round whose 100
+answer options carry human relevance scores -- by epsilon * sign(d loss / d features), where the loss is the relevance-weighted
+sum over the options of each option's mean per-token loss, and then scores the options on the perturbed features.
+
+What differs from the script, none of it in the numbers it defines:
+  * an option with relevance 0 contributes 0 * loss: its gradient is exactly zero and its features come back unchanged.  The
+    gradient pass therefore runs on the options with a non-zero relevance only (typically a third of the 100), found on the host
+    before anything is copied to the device;
+  * that pass replays the backward for the image-feature gradient alone (Engine.inputs_only): the attack discards every
+    parameter gradient, so none is computed;
+  * the rounds that are not attacked are scored with one encoder pass per round (EncoderDecoderModel.score_candidates), as
+    evaluate.py does; the attacked round cannot be -- its 100 contexts differ after the perturbation.
+
+The text attacks (`coreference`, `random_token`) need a pretrained BertForMaskedLM and counter-fitted word vectors
+(utils/text_attack.py); neither is part of this package, and asking for them raises.
+"""
+import contextlib
+
+import torch
+
+from . import ops
+from .metrics import SparseGTMetrics, NDCG, scores_to_ranks
+
+ROWS_PER_CALL = 100         # evaluate_gen_attack.py:241
+
+_MODEL_KEYS = ("enc_image_features", "enc_image_spatials", "enc_image_mask", "enc_image_target", "enc_image_label",
+               "enc_next_sentence_labels", "enc_input_ids", "enc_segments", "enc_sep_indices", "enc_mlm_labels",
+               "enc_attention_mask", "dec_input_ids", "dec_attention_mask", "dec_labels")
+
+
+def _core(model):
+    return getattr(model, "module", model)          # nn.DataParallel(model, [gpu]) as the reference's scripts wrap it
+
+
+def relevant_rows(gt_relevance):
+    """Host indices (ascending, int64) of the options whose relevance is not zero -- the only rows whose loss reaches the
+    attack's gradient."""
+    rel = gt_relevance.detach().reshape(-1).cpu()
+    return (rel != 0).nonzero().view(-1)
+
+
+def _feature_grad(model, kw, weights, inputs_only):
+    """evaluate_gen_attack.py:101-130 on the rows of `kw`: -> (x, d loss / d x), loss = sum_b weights[b] * mean_u lm_loss[b, u]."""
+    x = kw["enc_image_features"].detach().clone().requires_grad_(True)
+    core = _core(model)
+    mode = core.inputs_only() if inputs_only else contextlib.nullcontext()
+    with torch.enable_grad(), mode:
+        lm_loss, _ = model(**dict(kw, enc_image_features=x), loss_reduction=False)
+        n, U = kw["dec_input_ids"].shape
+        lm_loss = lm_loss.view(n, U).mean(dim=1)
+        lm_loss = torch.sum(lm_loss * weights)
+        lm_loss.backward()
+    return x.detach(), x.grad
+
+
+def fgsm_features(model, kw, gt_relevance, epsilon, inputs_only=True, grad_fn=None):
+    """evaluate_gen_attack.py:101-131 -> adv_feats = features + epsilon * sign(d loss / d features), fp32, same shape.
+
+    `kw`: the 14 keyword tensors of EncoderDecoderModel.forward on the device, dec_labels None; `gt_relevance` [B] (host or
+    device; on the host nothing waits for the device).  Rows with relevance 0 are returned bit for bit and take no part in the
+    gradient pass.  As in the reference, whose first forward replaces [SEP] by [PAD] in the caller's `dec_input_ids` in place
+    (visual_dialog_decoder.py:57), kw["dec_input_ids"] leaves this function with that replacement made on EVERY row, so the
+    forward that follows sees what the reference's second forward sees.  `inputs_only` False: the full backward, parameter
+    gradients included, as the reference runs it.  `grad_fn(model, sub_kw, weights, inputs_only) -> (x, grad)` replaces the
+    gradient pass (host-logic tests)."""
+    if kw.get("dec_labels") is not None:
+        raise ValueError("fgsm_features: dec_labels must be None (the attack's labels are the shifted dec_input_ids)")
+    feats, dec_ids = kw["enc_image_features"], kw["dec_input_ids"]
+    B = feats.shape[0]
+    rel = gt_relevance.detach().reshape(-1)
+    if rel.numel() != B:
+        raise ValueError("fgsm_features: %d relevance scores for %d rows" % (rel.numel(), B))
+    rows = relevant_rows(rel)
+    adv = feats.detach().to(torch.float32, copy=True)
+    if rows.numel():
+        dev_rows = rows.to(feats.device)
+        full = rows.numel() == B
+        sub = {k: (v if (full or v is None) else v.index_select(0, dev_rows)) for k, v in kw.items()}
+        if full:
+            sub["dec_input_ids"] = dec_ids.clone()          # (the replacement below is made once, on the caller's tensor)
+        weights = rel.to(feats.device, torch.float32)
+        x, g = (grad_fn or _feature_grad)(model, sub, weights if full else weights.index_select(0, dev_rows), inputs_only)
+        x, g = x.to(torch.float32).contiguous(), g.to(torch.float32).contiguous()
+        if x.is_cuda:
+            stepped = ops.fgsm_step(x, g, epsilon, out=x)
+        else:                                                # host-logic tests only: the product path is on the device
+            stepped = x + epsilon * torch.sign(g)
+        if full:
+            adv = stepped.view_as(adv)
+        else:
+            adv.index_copy_(0, dev_rows, stepped.view(rows.numel(), *adv.shape[1:]))
+    dc = _core(model).decoder.config
+    dec_ids.masked_fill_(dec_ids == dc.eos_token_id, dc.pad_token_id)
+    return adv
+
+
+def _flat(t, last):
+    return t.reshape((-1,) + tuple(t.shape[-last:]))
+
+
+def attacked_round(batch):
+    """evaluate_gen_attack.py:94-100: the dialog round of the chunk (half the number of non-zero separator positions of its
+    first row) is the one that carries the relevance scores."""
+    sep = _flat(batch["enc_sep_indices"], 1)
+    return int(int((sep[0] != 0).sum()) / 2) == int(batch["round_id"].reshape(-1)[0])
+
+
+def forward_attack(model, batch, params, epsilon=1.0, inputs_only=True):
+    """The `fgsm` branch of evaluate_gen_attack.forward (evaluate_gen_attack.py:28-165) -> lm_scores [rows, U, vocab].
+    `batch`: one chunk of the eval loader's rows (host tensors) with its dialog's `round_id` and `gt_relevance`."""
+    attack = params.get("attack")
+    if attack in ("coreference", "random_token"):
+        raise NotImplementedError(
+            "attack=%r is a text attack (utils/text_attack.py): it needs a pretrained BertForMaskedLM, the counter-fitted word "
+            "vectors (cos_sim_counter_fitting, cos_sim_idx2word, cos_sim_word2idx)%s, none of which this package carries.  "
+            "Only attack='fgsm' is implemented" % (attack, " and the coreference dependencies" if attack == "coreference" else ""))
+    if attack != "fgsm":
+        raise NotImplementedError("attack=%r: no such attack (the reference has 'fgsm', 'coreference', 'random_token'; only "
+                                  "'fgsm' is implemented)" % (attack,))
+    dev = params["device"]
+    hit = attacked_round(batch)                                  # on the host tensors: no device round trip
+    kw = dict.fromkeys(_MODEL_KEYS)
+    kw.update(enc_input_ids=_flat(batch["enc_input_ids"], 1).to(dev), enc_segments=_flat(batch["enc_segments"], 1).to(dev),
+              enc_sep_indices=_flat(batch["enc_sep_indices"], 1).to(dev), enc_mlm_labels=_flat(batch["enc_mlm_labels"], 1).to(dev),
+              enc_attention_mask=_flat(batch["enc_att_mask"], 1).to(dev),
+              dec_input_ids=_flat(batch["dec_input_ids"], 1).to(dev, copy=True),     # (mutated below: never the loader's tensor)
+              dec_attention_mask=_flat(batch["dec_att_mask"], 1).to(dev),
+              enc_image_features=_flat(batch["enc_image_feat"], 2).to(dev), enc_image_spatials=_flat(batch["enc_image_loc"], 2).to(dev),
+              enc_image_mask=_flat(batch["enc_image_mask"], 1).to(dev))
+    if hit:
+        kw["enc_image_features"] = fgsm_features(model, kw, batch["gt_relevance"], epsilon, inputs_only=inputs_only)
+    _, lm_scores = model(**kw)
+    return lm_scores
+
+
+def _same_context(batch, keys=("enc_input_ids", "enc_segments", "enc_att_mask")):
+    return all(bool((batch[k] == batch[k][:1]).all()) for k in keys)
+
+
+def score_chunk(model, item, params, epsilon):
+    """Scores [rows] of one chunk: the script's lines 321-333 for the attacked round, one encoder pass for any other."""
+    dev = params["device"]
+    core = _core(model)
+    ids = item["dec_input_ids"]
+    if attacked_round(item) or not _same_context(item):
+        forward_attack(model, item, params, epsilon)
+        last = core.engine.last          # the second forward's logits and their log-sum-exp, still in the arena
+        scores = torch.empty(ids.shape[0], dtype=torch.float32, device=dev)
+        ops.answer_scores(last["logits"].t, last["lse"], ids.to(dev).contiguous(), ids.shape[0], ids.shape[1], scores)
+        return scores
+    return core.score_candidates(item["enc_image_feat"][:1].to(dev), item["enc_image_loc"][:1].to(dev),
+                                 item["enc_image_mask"][:1].to(dev), item["enc_input_ids"][:1].to(dev),
+                                 item["enc_segments"][:1].to(dev), item["enc_att_mask"][:1].to(dev), ids.to(dev),
+                                 item["dec_att_mask"].to(dev), ids.shape[0])
+
+
+@torch.no_grad()
+def evaluate_attack(model, dataloader, params, epsilon=1.0, mode="vd_eval_val"):
+    """The loop of evaluate_gen_attack.evaluate (evaluate_gen_attack.py:233-369) for attack='fgsm': chunks of 100 option rows,
+    the metrics of metrics.py; -> (ranks_json, metrics) as evaluate.evaluate returns them."""
+    if params.get("attack") != "fgsm":
+        forward_attack(model, {}, params)           # raises, naming what is missing
+    sparse, ndcg, ranks_json = SparseGTMetrics(), NDCG(), []
+    model.eval()
+    for batch in dataloader:
+        ids = batch["enc_input_ids"]
+        Bd, rounds, options = ids.shape[0], ids.shape[1], ids.shape[2]
+        per_dialog = rounds * options
+        if per_dialog % ROWS_PER_CALL:
+            raise ValueError("evaluate_attack: %d rows per dialog are not a multiple of %d" % (per_dialog, ROWS_PER_CALL))
+        text = {k: _flat(batch[k], 1) for k in ("enc_input_ids", "enc_segments", "enc_sep_indices", "enc_mlm_labels", "enc_att_mask",
+                                                "dec_input_ids", "dec_att_mask")}
+        out = []
+        for d in range(Bd):
+            for j in range(per_dialog // ROWS_PER_CALL):
+                rows = slice(d * per_dialog + j * ROWS_PER_CALL, d * per_dialog + (j + 1) * ROWS_PER_CALL)
+                item = {k: v[rows] for k, v in text.items()}
+                # the loader holds the image tensors once per dialog; the chunk's rows all belong to dialog d
+                item["enc_image_feat"] = batch["enc_image_feat"][d:d + 1].expand(ROWS_PER_CALL, -1, -1)
+                item["enc_image_loc"] = batch["enc_image_loc"][d:d + 1].expand(ROWS_PER_CALL, -1, -1)
+                item["enc_image_mask"] = batch["enc_image_mask"][d:d + 1].expand(ROWS_PER_CALL, -1)
+                item["round_id"] = batch["round_id"][d:d + 1]
+                item["gt_relevance"] = batch["gt_relevance"][d]
+                out.append(score_chunk(model, item, params, epsilon))
+        scores = torch.cat(out, 0).view(Bd, rounds, options)
+        if mode == "vd_eval_val":
+            sparse.observe(scores, batch["gt_option_inds"])
+            if params.get("vd_version", "1.0") == "1.0":
+                rid = batch["round_id"].reshape(Bd)
+                ndcg.observe(scores[torch.arange(Bd), rid - 1, :], batch["gt_relevance"])
+        else:
+            ranks = scores_to_ranks(scores).squeeze(1)
+            for i in range(Bd):
+                ranks_json.append({"image_id": batch["image_id"][i].item(), "round_id": int(batch["round_id"][i].item()),
+                                   "ranks": [r.item() for r in ranks[i][:]]})
+    metrics = {}
+    if mode == "vd_eval_val":
+        metrics.update(sparse.retrieve(reset=True))
+        if params.get("vd_version", "1.0") == "1.0":
+            metrics.update(ndcg.retrieve(reset=True))
+    return ranks_json, metrics

@@ -58,18 +58,10 @@ __global__ __launch_bounds__(256) void ce_reduce_kernel(const float* row_loss, c
   if (threadIdx.x == 0) { stats[0] = s; stats[1] = n; stats[2] = s / n; }
 }
 
+// One row of dlogits = (softmax - onehot) * gs, columns V..ldd zero; `keep` false: the whole row zero.  Shared by the mean form
+// and the per-row form below, so the two agree to the last bit wherever their scales do.
 template <typename T>
-__global__ __launch_bounds__(256) void ce_bwd_kernel(const T* logits, int64_t ldl, const int64_t* labels, const float* lse,
-                                                     const float* stats, const float* gscale, int mean, int64_t V,
-                                                     int64_t ignore, T* dl, int64_t ldd) {
-  const int64_t m = blockIdx.x;
-  const T* x = logits + m * ldl;
-  T* d = dl + m * ldd;
-  const int64_t lab = labels[m];
-  const bool keep = !(lab == ignore || lab < 0 || lab >= V);
-  float gs = gscale ? gscale[0] : 1.f;
-  if (mean) gs /= stats[1];
-  const float l = lse[m];
+DEVFN void ce_bwd_row(const T* x, T* d, int64_t lab, bool keep, float l, float gs, int64_t V, int64_t ldd) {
   for (int64_t c = threadIdx.x * 4; c < ldd; c += 1024) {
     f32x4 o = {0.f, 0.f, 0.f, 0.f};
     if (keep) {
@@ -84,6 +76,52 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const T* logits, int64_t ld
       }
     }
     st4(d + c, o);
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void ce_bwd_kernel(const T* logits, int64_t ldl, const int64_t* labels, const float* lse,
+                                                     const float* stats, const float* gscale, int mean, int64_t V,
+                                                     int64_t ignore, T* dl, int64_t ldd) {
+  const int64_t m = blockIdx.x;
+  const int64_t lab = labels[m];
+  const bool keep = !(lab == ignore || lab < 0 || lab >= V);
+  float gs = gscale ? gscale[0] : 1.f;
+  if (mean) gs /= stats[1];
+  ce_bwd_row(logits + m * ldl, dl + m * ldd, lab, keep, lse[m], gs, V, ldd);
+}
+
+// Backward of CrossEntropyLoss(reduction='none') (visual_dialog_decoder.py:76) under a per-token upstream gradient g[m]
+// (evaluate_gen_attack.py:126-130: mean over the sequence, times the candidate's relevance).  A row whose g is zero is STORED as
+// zeros, never multiplied: 0 * exp(...) of a logit that overflowed would be NaN.
+template <typename T>
+__global__ __launch_bounds__(256) void ce_bwd_rows_kernel(const T* logits, int64_t ldl, const int64_t* labels, const float* lse,
+                                                          const float* g, int64_t V, int64_t ignore, T* dl, int64_t ldd) {
+  const int64_t m = blockIdx.x;
+  const int64_t lab = labels[m];
+  const float gs = g[m];
+  const bool keep = !(lab == ignore || lab < 0 || lab >= V) && gs != 0.f;
+  ce_bwd_row(logits + m * ldl, dl + m * ldd, lab, keep, lse[m], gs, V, ldd);
+}
+
+// out = x + eps * sign(g) (evaluate_gen_attack.py:131), sign(+-0) = 0 as torch.sign has it; sign(NaN) = NaN.  The sign is read off
+// the bits, so a denormal g counts whatever the denormal mode.  out may be x: every element is read and written by one thread.
+DEVFN float fgsm_one(float x, float g, float eps) {
+#pragma clang fp contract(off)
+  const uint32_t b = __builtin_bit_cast(uint32_t, g), mag = b & 0x7fffffffu;
+  const float s = mag == 0u ? 0.f : (mag > 0x7f800000u ? g : ((b >> 31) ? -1.f : 1.f));
+  return x + eps * s;
+}
+__global__ __launch_bounds__(256) void fgsm_step_kernel(const float* x, const float* g, float eps, float* out, int64_t n) {
+  const int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
+  if (i + 3 < n) {
+    const f32x4 xv = ld4(x + i), gv = ld4(g + i);
+    f32x4 o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = fgsm_one(xv[e], gv[e], eps);
+    st4(out + i, o);
+  } else {
+    for (int64_t j = i; j < n; ++j) out[j] = fgsm_one(x[j], g[j], eps);
   }
 }
 
@@ -240,6 +278,27 @@ extern "C" int gstvd_ce_bwd(const void* logits, int64_t ldl, const int64_t* labe
   if (dtype == GSTVD_BF16) hipLaunchKernelGGL(ce_bwd_kernel<bf16>, dim3((unsigned)M), dim3(256), 0, s, (const bf16*)logits, ldl, labels, lse, stats, gscale, mean, V, ignore_index, (bf16*)dlogits, ldd);
   else if (dtype == GSTVD_F32) hipLaunchKernelGGL(ce_bwd_kernel<float>, dim3((unsigned)M), dim3(256), 0, s, (const float*)logits, ldl, labels, lse, stats, gscale, mean, V, ignore_index, (float*)dlogits, ldd);
   else return GSTVD_E_DTYPE;
+  GSTVD_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int gstvd_ce_bwd_rows(const void* logits, int64_t ldl, const int64_t* labels, const float* lse, const float* g, int64_t M,
+                                 int64_t V, int64_t ignore_index, int32_t dtype, void* dlogits, int64_t ldd, gstvd_stream_t stream) {
+  if (!logits || !labels || !lse || !g || !dlogits) return GSTVD_E_NULL;
+  if (M <= 0 || V <= 0 || (ldl % 4) || (ldd % 4) || ldd < V) return GSTVD_E_SHAPE;
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == GSTVD_BF16) hipLaunchKernelGGL(ce_bwd_rows_kernel<bf16>, dim3((unsigned)M), dim3(256), 0, s, (const bf16*)logits, ldl, labels, lse, g, V, ignore_index, (bf16*)dlogits, ldd);
+  else if (dtype == GSTVD_F32) hipLaunchKernelGGL(ce_bwd_rows_kernel<float>, dim3((unsigned)M), dim3(256), 0, s, (const float*)logits, ldl, labels, lse, g, V, ignore_index, (float*)dlogits, ldd);
+  else return GSTVD_E_DTYPE;
+  GSTVD_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int gstvd_fgsm_step(const float* x, const float* g, float eps, float* out, int64_t n, gstvd_stream_t stream) {
+  if (!x || !g || !out) return GSTVD_E_NULL;
+  if (n <= 0 || n > ((int64_t)1 << 40)) return GSTVD_E_SHAPE;
+  if (((uintptr_t)x | (uintptr_t)g | (uintptr_t)out) & 15) return GSTVD_E_ALIGN;
+  hipLaunchKernelGGL(fgsm_step_kernel, dim3((unsigned)((n + 1023) / 1024)), dim3(256), 0, (hipStream_t)stream, x, g, eps, out, n);
   GSTVD_LAUNCH_CHECK();
   return 0;
 }

@@ -20,6 +20,7 @@ Numerics: precision 'fp32' runs every GEMM on the exact-fp32 MFMA (parity gate: 
 oracle); 'bf16' stores activations/weights in bf16 with fp32 accumulation and fp32 LN/softmax/CE statistics.
 The sampling decode (`sample`, `rescore_sampled`) is engine_decode.py.
 """
+import contextlib
 import os
 import weakref
 
@@ -81,6 +82,7 @@ class Engine(DecodeMixin):
         self.pipe = None               # BackwardPipeline (pipeline.py): slice-wise wgrad / all-reduce / AdamW on the aux stream
         self.tape, self.rec = [], False
         self.accumulate, self.written = False, set()
+        self._inputs_only, self._io = False, False     # inputs_only(): asked for by the caller / in force during the running replay
         self.stats = {}
         self._validate = True
         self.use_streams = bool(params.get("amd_streams", True))
@@ -224,6 +226,8 @@ class Engine(DecodeMixin):
 
     def _hook(self, off):
         """Backward reached flat offset `off`: every gradient at offset >= off has been produced or queued."""
+        if self._io:
+            return
         if self.pipe is not None and self.pipe.ready(off):
             self._emit(off)
 
@@ -234,7 +238,7 @@ class Engine(DecodeMixin):
         launch.  So the grouped launch starts here on the auxiliary stream and those two run beside it instead of in front of it
         (engine.EARLY_WGRAD = 0: the launch waits for them, as in rounds 4-5a; profiles/r05_early_wgrad_ab.txt)."""
         p = self.pipe
-        if not self.use_streams or p is None or p.hi is None or p.slices or p.hi != self.flat.n_live or p.fuse_handle() is None:
+        if self._io or not self.use_streams or p is None or p.hi is None or p.slices or p.hi != self.flat.n_live or p.fuse_handle() is None:
             return
         if any(self.wgrads.pending_into(self.Gv[n]) for n in ("emb.word", "emb.pos", "emb.tt", "emb.tte") if n in self.Gv):
             return      # a queued GEMM writes a table the embedding's backward is about to add into (tied LM head): keep the order
@@ -323,6 +327,8 @@ class Engine(DecodeMixin):
     def _flush_aux(self):
         """Run the queued (decoder + LM head) weight-gradient group and column reductions on a third stream so they
         overlap the encoder's backward chain; joined back before the final flush."""
+        if self._io:
+            return
         self._wait_for(self.aux, self.main)
         with torch.cuda.stream(self.aux):
             self.wgrads.flush()
@@ -362,6 +368,7 @@ class Engine(DecodeMixin):
         else:
             ops.gemm(x.t, self.W[w], y.t, x.M, N, K, bias=self.Pv[b])
         y.prod = (x, w, K, need_dx)
+        y.req = x.req
         self.push(lambda: self._lin_bwd(x, y, w, b, N, K, need_dx))
         return y
 
@@ -384,6 +391,7 @@ class Engine(DecodeMixin):
         ops.gemm_ln_fwd(kw, self.W[w], out.t, N, bias=self.Pv[wb], aux=aux, epi=EPI_GELU if gelu else 0)
         out.gelu_aux = aux
         out.prod = (y, w, H, True)
+        y.req = out.req = x.req or res.req
         self.push(lambda: self._ln_bwd(kw, x, res, y, g, b, H, bias_name))
         if mark is not None:
             self.mark(mark)
@@ -392,6 +400,18 @@ class Engine(DecodeMixin):
 
     def _lin_bwd(self, x, y, w, b, N, K, need_dx):
         dy, M = y.g, x.M      # for a GELU output y.g already holds d(pre-activation): its producer applied gelu'
+        if not self._io:
+            self._lin_param_grads(x, y, w, b, N, K, dy, M)
+        elif not x.req:
+            return                # inputs-only replay: the weight- and bias-gradient siblings of the dgrad are dropped, and so is a dgrad nothing needs
+        if need_dx and not y.dgrad_done:          # (dgrad_done: the LayerNorm behind y ran it with its own backward, _ln_bwd)
+            add = x.g
+            if x.g is None:
+                x.g = self.buf(M, K)
+            ops.gemm(dy, self.W[w], x.g, M, K, N, b_km=True, addend=add, aux=x.gelu_aux,
+                     epi=EPI_DGELU if x.gelu_aux is not None else 0)
+
+    def _lin_param_grads(self, x, y, w, b, N, K, dy, M):
         gw, acc = self.grad_slot(w)
         if not y.bias_done and self.wgrads.colsum_capable(dy):
             # the bias gradient (column sums of dY) comes out of the weight-gradient launch itself: its producer waves sum the
@@ -404,12 +424,6 @@ class Engine(DecodeMixin):
                 gb, accb = self.grad_slot(b)
                 scratch = self.vec(((M + 63) // 64) * N)
                 self.colsums.add_slabs(dy, M, N, scratch, gb, accb)
-        if need_dx and not y.dgrad_done:          # (dgrad_done: the LayerNorm behind y ran it with its own backward, _ln_bwd)
-            add = x.g
-            if x.g is None:
-                x.g = self.buf(M, K)
-            ops.gemm(dy, self.W[w], x.g, M, K, N, b_km=True, addend=add, aux=x.gelu_aux,
-                     epi=EPI_DGELU if x.gelu_aux is not None else 0)
 
     def ln(self, x, res, g, b, H, p_pre, bias_name, eps=1e-12):
         M = x.M
@@ -418,6 +432,7 @@ class Engine(DecodeMixin):
                   mean=self.vec(M), rstd=self.vec(M), eps=eps, x=x.t, res=res.t if res is not None else None, y=y.t,
                   p_pre=p_pre if self.train else 0.0, site_pre=self.site(g[:-2], p_pre, "rows", (M, H)), rng=self.rng)
         ops.ln_fwd(**kw)
+        y.req = x.req or (res is not None and res.req)
         self.push(lambda: self._ln_bwd(kw, x, res, y, g, b, H, bias_name))
         return y
 
@@ -434,6 +449,8 @@ class Engine(DecodeMixin):
 
     def _ln_bwd(self, kw, x, res, y, g, b, H, bias_name):
         M = x.M
+        if self._io and not (x.req or (res is not None and res.req)):
+            return              # nothing below it depends on the image features
         prod = x.prod
         # (prod[0] must be a third tensor: for LN(Linear(r) + r) the input gradient of the Linear and the residual gradient are the
         # SAME tensor's gradient -- the fused launch would hand one uninitialised buffer to both its `dres` column tile and its
@@ -456,7 +473,8 @@ class Engine(DecodeMixin):
             ops.gemm_ln_bwd(kw, y.g, partial, nblk, self.W[w], xin.g, Kin, dres=res.g, dx=x.g, addend=add, aux=xin.gelu_aux,
                             epi=EPI_DGELU if xin.gelu_aux is not None else 0)
             x.dgrad_done = True
-            self._colsums(partial, nblk, H, [g, b, bias_name])
+            if not self._io:        # (inputs-only: the launch is kept for its dx / dres / dgrad, its parameter partials are dropped)
+                self._colsums(partial, nblk, H, [g, b, bias_name])
             x.bias_done = bias_name is not None
             return
         nblk = ops.ln_bwd_blocks(M, H, LN_RESID)
@@ -467,7 +485,8 @@ class Engine(DecodeMixin):
             res.g = self.buf(M, H)
         x.g = self.buf(M, H)
         ops.ln_bwd(kw, y.g, partial, dres=res.g if res is not None else None, dx=x.g, nblk=nblk)
-        self._colsums(partial, nblk, H, [g, b, bias_name])
+        if not self._io:
+            self._colsums(partial, nblk, H, [g, b, bias_name])
         x.bias_done = bias_name is not None
 
     def embed(self, prefix, ids, segs, Bn, T, cfg, pos_offset=0, label=None, p_drop=None):
@@ -482,10 +501,13 @@ class Engine(DecodeMixin):
                   p_post=p_drop if self.train else 0.0, site_post=self.site(label, p_drop, "rows", (M, H)), rng=self.rng,
                   pos_offset=pos_offset)
         ops.ln_fwd(**kw)
+        y.req = False           # token ids and tables only
         self.push(lambda: self._embed_bwd(kw, prefix, y, M, H))
         return y
 
     def _embed_bwd(self, kw, prefix, y, M, H):
+        if self._io:
+            return              # table and LayerNorm gradients only
         tabs, fresh = [], []
         for n in (".word", ".pos", ".tt", ".tte"):
             gv, acc = self.grad_slot(prefix + n)
@@ -535,6 +557,7 @@ class Engine(DecodeMixin):
                   b_loc=self.Pv["vemb.loc.b"], p_post=cfg.hidden_dropout_prob if self.train else 0.0,
                   site_post=self.site("vemb", cfg.hidden_dropout_prob, "rows", (M, H)), rng=self.rng)
         ops.ln_fwd(**kw)
+        y.req = x.req
         self.push(lambda: self._img_embed_bwd(kw, x, y, loc, M, H))
         return y
 
@@ -543,6 +566,8 @@ class Engine(DecodeMixin):
         partial = self.arena.alloc(nblk * 3 * H, torch.float32)
         x.g = self.buf(M, H)
         ops.ln_bwd(kw, y.g, partial, dres=x.g)
+        if self._io:
+            return
         self._colsums(partial, nblk, H, ["vemb.ln.w", "vemb.ln.b", "vemb.loc.b"])
         self._colsums(partial, nblk, H, [None, None, "vemb.img.b"])
         x.bias_done = True
@@ -563,10 +588,13 @@ class Engine(DecodeMixin):
                           site=self.site(label, p, "attn", (Bn, nh, Lq, (Lk + 3) // 4 * 4), Lk=Lk), rng=self.rng,
                           kv_group=kv_group, kv_bstride=kv_bstride, drop_bits=bits)
         ops.attn_fwd(a)
+        o.req = qa.req or ka.req or va.req
         self.push(lambda: self._attn_bwd(a, q, k, v, o, Bn, nh, Lq, Hh))
         return o
 
     def _attn_bwd(self, a, q, k, v, o, Bn, nh, Lq, Hh):
+        if self._io and not o.req:
+            return
         gs = []
         for (act, c) in (q, k, v):
             if act.g is None:
@@ -827,28 +855,58 @@ class Engine(DecodeMixin):
         if labels is None:
             labels = self._shift_labels(dec_ids)
         I = self._inputs(feats, loc, img_mask, ids, segs, att_mask, dec_ids, dec_mask)
+        if self._inputs_only and not (record and I["feats_grad"]):
+            raise GstvdError("inputs_only(): the call needs enabled gradients and enc_image_features that require grad -- "
+                             "d loss / d enc_image_features is all such a backward returns")
         xt, xv = self.encoder(I)
         enc = self.fusion(xt, xv, I)
         y, logits = self.decoder(enc, I)
         loss_raw, lv, ce = self._ce(logits, labels, I["B"], I["U"], loss_reduction)
-        st = dict(ce, I=I, logits=logits, mean=bool(loss_reduction), tape=self.tape)
+        st = dict(ce, I=I, logits=logits, mean=bool(loss_reduction), tape=self.tape, inputs_only=self._inputs_only)
         self.last = dict(enc_t=xt, enc_v=xv, enc=enc, dec_hidden=y, logits=logits, lse=ce["lse"], row_loss=ce["row_loss"])
         if record:
             loss = _StepFn.apply(self.anchor, feats if I["feats_grad"] else None, self, st, loss_raw)
             return loss, lv
         return loss_raw.clone(), lv.to(torch.float32, copy=True)      # copies: the arena is rewound by the next engine call
 
+    @contextlib.contextmanager
+    def inputs_only(self):
+        """For one forward / backward pair of `step`: the backward returns d loss / d enc_image_features and NOTHING else.  The
+        tape keeps every launch that gradient depends on -- the same dgrad GEMMs, LayerNorm and attention backwards with the same
+        operands, so the result is bit-identical to the full replay's -- and drops their siblings: weight gradients, bias and
+        LayerNorm column sums, the embedding scatters, the location-projection gradient, and the backward of every activation
+        that does not depend on the image features (Act.req: the text stream below the first connection layer, the decoder's
+        embedding and its first self-attention sub-layer).  `p.grad`, the flat gradient buffer, `written` / `accumulate` and an
+        attached BackwardPipeline are not touched.  What it is for: the FGSM attack of evaluate_gen_attack.py:101-131
+        (attack.fgsm_features), which discards every parameter gradient."""
+        prev, self._inputs_only = self._inputs_only, True
+        try:
+            yield self
+        finally:
+            self._inputs_only = prev
+
     def backward(self, st, gloss):
-        """Replay the tape: fills the flat gradient buffer, assigns `.grad` views, returns d loss / d image features."""
+        """Replay the tape: fills the flat gradient buffer, assigns `.grad` views, returns d loss / d image features.
+        `gloss`: the upstream gradient of the mean loss ([] / [1]) or, after loss_reduction=False, of the per-token losses
+        ([B * U] or [B, U]; evaluate_gen_attack.py:126-130 arrives here as relevance[b] / U on every token of row b)."""
         flat = self.flat
-        if not st["mean"]:
-            raise GstvdError("backward through loss_reduction=False is not supported (the reference never does it)")
-        self._backward_begin()
-        logits = st["logits"]
-        logits.g = self.buf(st["Md"], flat.Vp)
-        gs = gloss.reshape(1).float().contiguous() if gloss is not None else None
-        ops.ce_bwd(logits.t, st["lab"], st["lse"], st["stats"], gs, True, st["Md"], st["V"], logits.g, ignore_index=st["pad"])
-        return self._replay(st)
+        self._io = bool(st.get("inputs_only", False))       # as recorded by the forward, wherever backward() is called from
+        try:
+            if not self._io:
+                self._backward_begin()
+            logits = st["logits"]
+            logits.g = self.buf(st["Md"], flat.Vp)
+            if st["mean"]:
+                gs = gloss.reshape(1).float().contiguous() if gloss is not None else None
+                ops.ce_bwd(logits.t, st["lab"], st["lse"], st["stats"], gs, True, st["Md"], st["V"], logits.g, ignore_index=st["pad"])
+            else:
+                if gloss is None or gloss.numel() != st["Md"]:
+                    raise GstvdError("backward of the per-token losses needs an upstream gradient of %d elements" % st["Md"])
+                g = gloss.reshape(-1).to(device=logits.t.device, dtype=torch.float32).contiguous()
+                ops.ce_bwd_rows(logits.t, st["lab"], st["lse"], g, st["Md"], st["V"], logits.g, ignore_index=st["pad"])
+            return self._replay(st)
+        finally:
+            self._io = False
 
     def _backward_begin(self):
         """Start of every backward: gradient accumulation state (an optimizer that kept `.grad`), the deferred launches."""
@@ -870,8 +928,9 @@ class Engine(DecodeMixin):
         """The tape in reverse on the two streams, the deferred weight-gradient / column-sum launches, the `.grad` views;
         -> d loss / d image features (or None).  Shared by the enc_dec step and the discriminative step."""
         flat = self.flat
+        io = self._io
         self.main, self.tag = torch.cuda.current_stream(), "t"
-        if self.pipe is not None:
+        if self.pipe is not None and not io:
             self.pipe.begin()
         for tag, fn in reversed(st["tape"]):
             if tag == "sync":
@@ -883,6 +942,8 @@ class Engine(DecodeMixin):
                 fn()
         if self.use_streams:
             self._wait("t", "v")
+        if io:
+            return self._feats_grad(st)         # no parameter gradient was queued or written: nothing to flush, `.grad` stays
         if self.pipe is not None:
             if self.pipe.hi > 0:
                 self._emit(0)
@@ -904,9 +965,15 @@ class Engine(DecodeMixin):
         else:
             for p, gv in zip(flat.live, flat.grad_views):
                 p.grad = gv
+        return self._feats_grad(st)
+
+    @staticmethod
+    def _feats_grad(st):
+        """d loss / d image features as an fp32 tensor of its own (not a view of the arena, which the next engine call rewinds:
+        autograd keeps what it is handed as the leaf's `.grad`), or None."""
         fa = st["I"].get("feats_act")
         if st["I"]["feats_grad"] and fa is not None and fa.g is not None:
-            return fa.g.float()
+            return fa.g.to(torch.float32, copy=True)
         return None
 
     # ------------------------------------------------------------------------------------------ candidate scoring

@@ -427,6 +427,11 @@ class EncoderDecoderModel(nn.Module):
             "(torchrun --nproc-per-node N train script) with gst_visdial_amd.pipeline.BackwardPipeline doing the gradient "
             "all-reduce over RCCL (INTEGRATION.md, 'Multi-GPU').")
 
+    def inputs_only(self):
+        """Context manager: the backward of a forward made inside it returns d loss / d enc_image_features only and leaves
+        every parameter's `.grad` alone (Engine.inputs_only; the FGSM attack, attack.fgsm_features)."""
+        return self.engine.inputs_only()
+
     def score_candidates(self, enc_image_features, enc_image_spatials, enc_image_mask, enc_input_ids, enc_segments,
                          enc_attention_mask, dec_input_ids, dec_attention_mask, num_options):
         """Generative ranking scores of evaluate_gen.py:45-106 with one encoder pass per dialog round (see

@@ -749,7 +749,34 @@ def ce_bwd(logits, labels, lse, stats, gscale, mean, M, V, dlogits, ignore_index
     _prof_end(e0, "ce_bwd", 0.0, float(M) * V * (logits.element_size() + dlogits.element_size()), (M, V))
 
 
-SAMPLE_MAX_TOP_K = 1 << 30  # (ABI 6: no limit any more -- k <= 16 walks the distinct values from the top, larger k bisects; top-p is in the kernel too)
+def ce_bwd_rows(logits, labels, lse, g, M, V, dlogits, ignore_index=0):
+    """dlogits = g[row] * (softmax - onehot): the backward of the per-token losses (gstvd_ce_bwd_rows); g fp32 [M] on the device."""
+    lib = L.load()
+    if g.dtype != torch.float32 or not g.is_contiguous() or g.numel() != M:
+        raise L.GstvdError("ce_bwd_rows: g must be a contiguous fp32 tensor of %d elements" % M)
+    if dlogits.dtype != logits.dtype:
+        raise L.GstvdError("ce_bwd_rows: logits and dlogits must share one dtype")
+    e0 = _prof_begin()
+    L.check("gstvd_ce_bwd_rows", lib.gstvd_ce_bwd_rows(_p(logits), logits.stride(-2), _p(labels), _p(lse), _p(g), M, V, ignore_index,
+                                                       dt(logits), _p(dlogits), dlogits.stride(-2), _stream()))
+    _prof_end(e0, "ce_bwd_rows", 0.0, float(M) * V * (logits.element_size() + dlogits.element_size()), (M, V))
+
+
+def fgsm_step(x, g, eps, out=None):
+    """out = x + eps * sign(g) over contiguous fp32 tensors of one size (gstvd_fgsm_step); `out` None: a new tensor, `out` may be x."""
+    lib = L.load()
+    if out is None:
+        out = torch.empty_like(x)
+    for t in (x, g, out):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != x.numel():
+            raise L.GstvdError("fgsm_step: x, g and out must be contiguous fp32 tensors of one size")
+    e0 = _prof_begin()
+    L.check("gstvd_fgsm_step", lib.gstvd_fgsm_step(_p(x), _p(g), float(eps), _p(out), x.numel(), _stream()))
+    _prof_end(e0, "fgsm_step", 0.0, 12.0 * x.numel(), (x.numel(),))
+    return out
+
+
+SAMPLE_MAX_TOP_K = 1 << 30 # (ABI 6: no limit any more -- k <= 16 walks the distinct values from the top, larger k bisects; top-p is in the kernel too)
 SAMPLE_MAX_VOCAB = 31 * 1024   # a row of scaled logits lives in one CU's LDS (and 31 registers per thread)
 
 

@@ -29,12 +29,15 @@ def _numel(shape):
 
 class Act(object):
     """An activation [M, N] in the arena plus (during backward) its gradient."""
-    __slots__ = ("t", "g", "M", "N", "gelu_aux", "bias_done", "prod", "dgrad_done")
+    __slots__ = ("t", "g", "M", "N", "gelu_aux", "bias_done", "prod", "dgrad_done", "req")
 
     def __init__(self, t, M, N):
         self.t, self.g, self.M, self.N = t, None, M, N
         self.gelu_aux, self.bias_done = None, False
         self.prod, self.dgrad_done = None, False      # the Linear that produced it (input, weight, K_in, need_dx); see _ln_bwd
+        # False: the activation does not depend on the image features (it comes from token ids and parameters alone), so the
+        # inputs-only replay (Engine.inputs_only) needs no gradient for it.  Forward ops pass it on like autograd's requires_grad.
+        self.req = True
 
 
 class Arena(object):

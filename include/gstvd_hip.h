@@ -250,6 +250,16 @@ int gstvd_ce_fwd(const void* logits, int64_t ldl, const int64_t* labels, int64_t
 int gstvd_ce_bwd(const void* logits, int64_t ldl, const int64_t* labels, const float* lse,
                  const float* stats, const float* gscale, int32_t mean, int64_t M, int64_t V,
                  int64_t ignore_index, int32_t dtype, void* dlogits, int64_t ldd, gstvd_stream_t s);
+/* (entry points added for the FGSM attack evaluation, no signature changed: ABI stays 9)
+ * The same under a PER-ROW upstream gradient, the backward of CrossEntropyLoss(reduction='none') (evaluate_gen_attack.py:121-130):
+ * dlogits[m, v] = g[m] * (softmax - onehot) for kept rows with g[m] != 0 (g: device fp32 [M]); a row with g[m] == 0 or an
+ * ignored label is stored as exact zeros (never 0 * inf); columns V..ldd-1 zero filled.  With g[m] = gscale / stats[1] on the
+ * kept rows the result is gstvd_ce_bwd's mean form to the last bit (one row routine serves both). */
+int gstvd_ce_bwd_rows(const void* logits, int64_t ldl, const int64_t* labels, const float* lse, const float* g, int64_t M,
+                      int64_t V, int64_t ignore_index, int32_t dtype, void* dlogits, int64_t ldd, gstvd_stream_t s);
+/* evaluate_gen_attack.py:131: out[i] = x[i] + eps * sign(g[i]) over fp32 [n], sign(+0) = sign(-0) = 0 (torch.sign), denormal g
+ * counted by its sign bit; out may alias x; 16-byte aligned pointers. */
+int gstvd_fgsm_step(const float* x, const float* g, float eps, float* out, int64_t n, gstvd_stream_t s);
 /* evaluate_gen.py:94-106: score[m] = sum_u [tgt != 0] * (logits[m,u,tgt] - lse[m,u]) with tgt = ids shifted left */
 int gstvd_answer_scores(const void* logits, int64_t ldl, const float* lse, const int64_t* dec_ids,
                         int64_t rows, int64_t U, int32_t dtype, float* scores, gstvd_stream_t s);
