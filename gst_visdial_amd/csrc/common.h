@@ -117,6 +117,20 @@ DEVFN float wave_max(float v) {
   return v;
 }
 
+// Sum / max over the blockDim.x / 64 waves of a workgroup, result in every thread: the wave's reduction, then the waves through
+// `red` (one float per wave) in wave order red[0], red[1], ... -- a fixed order, bit-reproducible.  The leading barrier lets
+// consecutive calls share `red`.  (sample.hip keeps its own block_sum: it starts from 0.f over a compile-time wave count.)
+DEVFN float block_reduce(float v, float* red, bool is_max) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  v = is_max ? wave_max(v) : wave_sum(v);
+  __syncthreads();
+  if (lane == 0) red[wave] = v;
+  __syncthreads();
+  float r = red[0];
+  for (int w = 1; w < (int)(blockDim.x >> 6); ++w) r = is_max ? fmaxf(r, red[w]) : r + red[w];
+  return r;
+}
+
 // ---- counter-based dropout ----------------------------------------------------------------------
 // lowbias32 integer hash (full avalanche); one 32-bit draw serves two elements (16 bits each).
 // Counter hash of the dropout draws: xorshift folds around two 24-bit multiplies (v_mul_u32_u24: full rate; a 32-bit
@@ -217,3 +231,12 @@ DEVFN s16x4 pack_bf16x4(float a, float b, float c, float d) {
 }
 
 #define GSTVD_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return (int)e_; } while (0)
+
+// Runs the statement(s) `...` with `T` naming the element type of `dtype` (GSTVD_BF16 -> bf16, GSTVD_F32 -> float); any other
+// dtype returns GSTVD_E_DTYPE from the calling function.  A launch spells its argument list once, with T in it.
+#define GSTVD_FOR_DTYPE(dtype, T, ...)                           \
+  do {                                                           \
+    if ((dtype) == GSTVD_BF16) { using T = bf16; __VA_ARGS__; }  \
+    else if ((dtype) == GSTVD_F32) { using T = float; __VA_ARGS__; } \
+    else return GSTVD_E_DTYPE;                                   \
+  } while (0)

@@ -6,29 +6,8 @@
 //     over the regions with image_label == 1 and divided by their number (models/vilbert_dialog.py:1496-1501).
 // One workgroup per row, sums in a fixed order (lane -> wave -> waves in wave order; one block for the sum over rows): no atomics,
 // bit-reproducible.
-#include "common.h"
+#include "loss_reduce.h"
 #include <math.h>
-
-DEVFN float dt_block_sum(float v, float* red) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  v = wave_sum(v);
-  __syncthreads();
-  if (lane == 0) red[wave] = v;
-  __syncthreads();
-  float r = red[0];
-  for (int w = 1; w < (int)(blockDim.x >> 6); ++w) r += red[w];
-  return r;
-}
-DEVFN float dt_block_max(float v, float* red) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  v = wave_max(v);
-  __syncthreads();
-  if (lane == 0) red[wave] = v;
-  __syncthreads();
-  float r = red[0];
-  for (int w = 1; w < (int)(blockDim.x >> 6); ++w) r = fmaxf(r, red[w]);
-  return r;
-}
 
 // ---- row gather / scatter ----------------------------------------------------------------------------------------------------
 // dst[i, :] = src[idx[i], :]; an index outside [0, M) gives a zero row (never an out-of-bounds read)
@@ -87,10 +66,10 @@ __global__ __launch_bounds__(256) void kl_fwd_kernel(const T* scores, int64_t ld
   const float* t = target + (trow ? trow[m] : m) * ldt;
   float mx = -INFINITY;
   for (int64_t c = threadIdx.x; c < C; c += 256) mx = fmaxf(mx, to_f(x[c]));
-  mx = dt_block_max(mx, red);
+  mx = block_reduce(mx, red, true);
   float s = 0.f;
   for (int64_t c = threadIdx.x; c < C; c += 256) s += expf(to_f(x[c]) - mx);
-  s = dt_block_sum(s, red);
+  s = block_reduce(s, red, false);
   const float lse = mx + logf(s);
   float a = 0.f;
   for (int64_t c = threadIdx.x; c < C; c += 256) {
@@ -98,24 +77,11 @@ __global__ __launch_bounds__(256) void kl_fwd_kernel(const T* scores, int64_t ld
     // torch's xlogy convention: the t == 0 terms are exactly 0 whatever the score
     if (tv != 0.f) a += tv * (logf(tv) - (to_f(x[c]) - lse));
   }
-  a = dt_block_sum(a, red);
+  a = block_reduce(a, red, false);
   if (threadIdx.x == 0) {
     lse_out[m] = lse;
     row_loss[m] = (labels && labels[m] != 1) ? 0.f : a;
   }
-}
-
-// stats[0] = sum(row_loss), stats[1] = number of counted rows, stats[2] = their quotient; one block, fixed order
-__global__ __launch_bounds__(256) void kl_reduce_kernel(const float* row_loss, const int64_t* labels, int64_t M, float* stats) {
-  __shared__ float red[4];
-  float s = 0.f, n = 0.f;
-  for (int64_t i = threadIdx.x; i < M; i += 256) {
-    s += row_loss[i];
-    n += (!labels || labels[i] == 1) ? 1.f : 0.f;
-  }
-  s = dt_block_sum(s, red);
-  n = dt_block_sum(n, red);
-  if (threadIdx.x == 0) { stats[0] = s; stats[1] = n; stats[2] = s / n; }
 }
 
 // d scores = scale * (softmax * sum_c t - t), scale = gscale[0] (/ stats[1] with `mean`); columns [C, ldd) are zero filled
@@ -131,7 +97,7 @@ __global__ __launch_bounds__(256) void kl_bwd_kernel(const T* scores, int64_t ld
   const bool keep = !labels || labels[m] == 1;
   float ts = 0.f;
   for (int64_t c = threadIdx.x; c < C; c += 256) ts += t[c];
-  ts = dt_block_sum(ts, red);            // the row's ACTUAL target sum (not assumed to be 1)
+  ts = block_reduce(ts, red, false);            // the row's ACTUAL target sum (not assumed to be 1)
   float gs = gscale ? gscale[0] : 1.f;
   if (mean) gs /= stats[1];
   const float l = lse[m];
@@ -159,8 +125,7 @@ extern "C" int gstvd_rows_gather(const void* src, int64_t lds, int64_t M, const 
   const int rc = rows_args(src, dst, idx, n, H, lds, ldd, M, dtype);
   if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == GSTVD_BF16) hipLaunchKernelGGL(rows_gather_kernel<bf16>, dim3((unsigned)n), dim3(256), 0, s, (const bf16*)src, lds, M, idx, H, (bf16*)dst, ldd);
-  else hipLaunchKernelGGL(rows_gather_kernel<float>, dim3((unsigned)n), dim3(256), 0, s, (const float*)src, lds, M, idx, H, (float*)dst, ldd);
+  GSTVD_FOR_DTYPE(dtype, T, hipLaunchKernelGGL(rows_gather_kernel<T>, dim3((unsigned)n), dim3(256), 0, s, (const T*)src, lds, M, idx, H, (T*)dst, ldd));
   GSTVD_LAUNCH_CHECK();
   return 0;
 }
@@ -172,19 +137,11 @@ extern "C" int gstvd_rows_scatter(const void* src, int64_t lds, const int64_t* i
   if (M > 0x7fffffffLL) return GSTVD_E_SHAPE;
   hipStream_t s = (hipStream_t)stream;
   const int acc = accumulate ? 1 : 0;
-  if (dtype == GSTVD_BF16) {
-    if (!acc) {       // first writer: the rows no index names are zero, written here (same stream: ordered before the scatter)
-      hipLaunchKernelGGL(rows_zero_kernel<bf16>, dim3((unsigned)M), dim3(256), 0, s, (bf16*)dst, ldd, H);
-      GSTVD_LAUNCH_CHECK();
-    }
-    hipLaunchKernelGGL(rows_scatter_kernel<bf16>, dim3((unsigned)n), dim3(256), 0, s, (const bf16*)src, lds, idx, H, (bf16*)dst, ldd, M, acc);
-  } else {
-    if (!acc) {
-      hipLaunchKernelGGL(rows_zero_kernel<float>, dim3((unsigned)M), dim3(256), 0, s, (float*)dst, ldd, H);
-      GSTVD_LAUNCH_CHECK();
-    }
-    hipLaunchKernelGGL(rows_scatter_kernel<float>, dim3((unsigned)n), dim3(256), 0, s, (const float*)src, lds, idx, H, (float*)dst, ldd, M, acc);
+  if (!acc) {       // first writer: the rows no index names are zero, written here (same stream: ordered before the scatter)
+    GSTVD_FOR_DTYPE(dtype, T, hipLaunchKernelGGL(rows_zero_kernel<T>, dim3((unsigned)M), dim3(256), 0, s, (T*)dst, ldd, H));
+    GSTVD_LAUNCH_CHECK();
   }
+  GSTVD_FOR_DTYPE(dtype, T, hipLaunchKernelGGL(rows_scatter_kernel<T>, dim3((unsigned)n), dim3(256), 0, s, (const T*)src, lds, idx, H, (T*)dst, ldd, M, acc));
   GSTVD_LAUNCH_CHECK();
   return 0;
 }
@@ -195,8 +152,7 @@ extern "C" int gstvd_rows_mul(void* x, int64_t ldx, const void* a, int64_t lda, 
   if (M <= 0 || M > 0x7fffffffLL || N <= 0 || (N % 4) || ldx < N || lda < N || (ldx % 4) || (lda % 4)) return GSTVD_E_SHAPE;
   if (((uintptr_t)x | (uintptr_t)a) & (dtype == GSTVD_BF16 ? 7 : 15)) return GSTVD_E_ALIGN;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == GSTVD_BF16) hipLaunchKernelGGL(rows_mul_kernel<bf16>, dim3((unsigned)M), dim3(256), 0, s, (bf16*)x, ldx, (const bf16*)a, lda, N);
-  else hipLaunchKernelGGL(rows_mul_kernel<float>, dim3((unsigned)M), dim3(256), 0, s, (float*)x, ldx, (const float*)a, lda, N);
+  GSTVD_FOR_DTYPE(dtype, T, hipLaunchKernelGGL(rows_mul_kernel<T>, dim3((unsigned)M), dim3(256), 0, s, (T*)x, ldx, (const T*)a, lda, N));
   GSTVD_LAUNCH_CHECK();
   return 0;
 }
@@ -207,11 +163,9 @@ extern "C" int gstvd_kl_fwd(const void* scores, int64_t lds, const float* target
   if (!scores || !target || !row_loss || !lse || !stats) return GSTVD_E_NULL;
   if (rows <= 0 || rows > 0x7fffffffLL || C <= 0 || lds < C || ldt < C) return GSTVD_E_SHAPE;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == GSTVD_BF16) hipLaunchKernelGGL(kl_fwd_kernel<bf16>, dim3((unsigned)rows), dim3(256), 0, s, (const bf16*)scores, lds, target, ldt, target_row, labels, C, row_loss, lse);
-  else if (dtype == GSTVD_F32) hipLaunchKernelGGL(kl_fwd_kernel<float>, dim3((unsigned)rows), dim3(256), 0, s, (const float*)scores, lds, target, ldt, target_row, labels, C, row_loss, lse);
-  else return GSTVD_E_DTYPE;
+  GSTVD_FOR_DTYPE(dtype, T, hipLaunchKernelGGL(kl_fwd_kernel<T>, dim3((unsigned)rows), dim3(256), 0, s, (const T*)scores, lds, target, ldt, target_row, labels, C, row_loss, lse));
   GSTVD_LAUNCH_CHECK();
-  hipLaunchKernelGGL(kl_reduce_kernel, dim3(1), dim3(256), 0, s, row_loss, labels, rows, stats);
+  hipLaunchKernelGGL(row_loss_reduce_kernel, dim3(1), dim3(256), 0, s, (const float*)row_loss, labels, (int64_t)1, 1, rows, stats);   // rows with label == 1 (no labels: all) count
   GSTVD_LAUNCH_CHECK();
   return 0;
 }
@@ -222,9 +176,7 @@ extern "C" int gstvd_kl_bwd(const void* scores, int64_t lds, const float* target
   if (!scores || !target || !lse || !stats || !dscores) return GSTVD_E_NULL;
   if (rows <= 0 || rows > 0x7fffffffLL || C <= 0 || lds < C || ldt < C || ldd < C) return GSTVD_E_SHAPE;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == GSTVD_BF16) hipLaunchKernelGGL(kl_bwd_kernel<bf16>, dim3((unsigned)rows), dim3(256), 0, s, (const bf16*)scores, lds, target, ldt, target_row, labels, lse, stats, gscale, mean, C, (bf16*)dscores, ldd);
-  else if (dtype == GSTVD_F32) hipLaunchKernelGGL(kl_bwd_kernel<float>, dim3((unsigned)rows), dim3(256), 0, s, (const float*)scores, lds, target, ldt, target_row, labels, lse, stats, gscale, mean, C, (float*)dscores, ldd);
-  else return GSTVD_E_DTYPE;
+  GSTVD_FOR_DTYPE(dtype, T, hipLaunchKernelGGL(kl_bwd_kernel<T>, dim3((unsigned)rows), dim3(256), 0, s, (const T*)scores, lds, target, ldt, target_row, labels, lse, stats, gscale, mean, C, (T*)dscores, ldd));
   GSTVD_LAUNCH_CHECK();
   return 0;
 }

@@ -1,19 +1,8 @@
 // LM-head cross entropy (visual_dialog_decoder.py:70-77), candidate scoring (evaluate_gen.py:94-106),
 // casts, the dropout-mask probe used by tests, and the fused AdamW (pytorch_transformers 1.2.0 semantics).
 // All HBM-bound: 16-byte vector accesses, one workgroup per logits row, deterministic reductions.
-#include "common.h"
+#include "loss_reduce.h"
 #include <math.h>
-
-DEVFN float block_reduce(float v, float* red, bool is_max) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  v = is_max ? wave_max(v) : wave_sum(v);
-  __syncthreads();
-  if (lane == 0) red[wave] = v;
-  __syncthreads();
-  float r = red[0];
-  for (int w = 1; w < (int)(blockDim.x >> 6); ++w) r = is_max ? fmaxf(r, red[w]) : r + red[w];
-  return r;
-}
 
 template <typename T>
 __global__ __launch_bounds__(256) void ce_fwd_kernel(const T* logits, int64_t ldl, const int64_t* labels, int64_t V,
@@ -42,20 +31,6 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const T* logits, int64_t ld
     const int64_t lab = labels[m];
     row_loss[m] = (lab == ignore || lab < 0 || lab >= V) ? 0.f : lse - to_f(x[lab]);
   }
-}
-
-// stats[0] = sum(row_loss), stats[1] = #(label != ignore), stats[2] = mean; single block, fixed order => deterministic
-__global__ __launch_bounds__(256) void ce_reduce_kernel(const float* row_loss, const int64_t* labels, int64_t M,
-                                                        int64_t ignore, float* stats) {
-  __shared__ float red[4];
-  float s = 0.f, n = 0.f;
-  for (int64_t i = threadIdx.x; i < M; i += 256) {
-    s += row_loss[i];
-    n += (labels[i] != ignore) ? 1.f : 0.f;
-  }
-  s = block_reduce(s, red, false);
-  n = block_reduce(n, red, false);
-  if (threadIdx.x == 0) { stats[0] = s; stats[1] = n; stats[2] = s / n; }
 }
 
 // One row of dlogits = (softmax - onehot) * gs, columns V..ldd zero; `keep` false: the whole row zero.  Shared by the mean form
@@ -243,9 +218,7 @@ extern "C" int gstvd_vl_split(const void* d_enc, int64_t B, int64_t R, int64_t T
   if (B <= 0 || R <= 0 || T <= 0 || H <= 0 || (H % 4)) return GSTVD_E_SHAPE;
   hipStream_t s = (hipStream_t)stream;
   dim3 grid((unsigned)((B * (R + T) * (H / 4) + 255) / 256));
-  if (dtype == GSTVD_BF16) hipLaunchKernelGGL(vl_split_kernel<bf16>, grid, dim3(256), 0, s, (const bf16*)d_enc, B, R, T, H, (bf16*)d_v, (bf16*)d_t, p, site_v, site_t, rng);
-  else if (dtype == GSTVD_F32) hipLaunchKernelGGL(vl_split_kernel<float>, grid, dim3(256), 0, s, (const float*)d_enc, B, R, T, H, (float*)d_v, (float*)d_t, p, site_v, site_t, rng);
-  else return GSTVD_E_DTYPE;
+  GSTVD_FOR_DTYPE(dtype, E, hipLaunchKernelGGL(vl_split_kernel<E>, grid, dim3(256), 0, s, (const E*)d_enc, B, R, T, H, (E*)d_v, (E*)d_t, p, site_v, site_t, rng));
   GSTVD_LAUNCH_CHECK();
   return 0;
 }
@@ -260,11 +233,9 @@ extern "C" int gstvd_ce_fwd(const void* logits, int64_t ldl, const int64_t* labe
   if (!logits || !labels || !row_loss || !lse || !stats) return GSTVD_E_NULL;
   if (M <= 0 || V <= 0 || (ldl % 4)) return GSTVD_E_SHAPE;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == GSTVD_BF16) hipLaunchKernelGGL(ce_fwd_kernel<bf16>, dim3((unsigned)M), dim3(256), 0, s, (const bf16*)logits, ldl, labels, V, ignore_index, row_loss, lse);
-  else if (dtype == GSTVD_F32) hipLaunchKernelGGL(ce_fwd_kernel<float>, dim3((unsigned)M), dim3(256), 0, s, (const float*)logits, ldl, labels, V, ignore_index, row_loss, lse);
-  else return GSTVD_E_DTYPE;
+  GSTVD_FOR_DTYPE(dtype, T, hipLaunchKernelGGL(ce_fwd_kernel<T>, dim3((unsigned)M), dim3(256), 0, s, (const T*)logits, ldl, labels, V, ignore_index, row_loss, lse));
   GSTVD_LAUNCH_CHECK();
-  hipLaunchKernelGGL(ce_reduce_kernel, dim3(1), dim3(256), 0, s, row_loss, labels, M, ignore_index, stats);
+  hipLaunchKernelGGL(row_loss_reduce_kernel, dim3(1), dim3(256), 0, s, (const float*)row_loss, labels, ignore_index, 0, M, stats);   // rows with label != ignore count
   GSTVD_LAUNCH_CHECK();
   return 0;
 }
@@ -275,9 +246,7 @@ extern "C" int gstvd_ce_bwd(const void* logits, int64_t ldl, const int64_t* labe
   if (!logits || !labels || !lse || !stats || !dlogits) return GSTVD_E_NULL;
   if (M <= 0 || V <= 0 || (ldl % 4) || (ldd % 4) || ldd < V) return GSTVD_E_SHAPE;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == GSTVD_BF16) hipLaunchKernelGGL(ce_bwd_kernel<bf16>, dim3((unsigned)M), dim3(256), 0, s, (const bf16*)logits, ldl, labels, lse, stats, gscale, mean, V, ignore_index, (bf16*)dlogits, ldd);
-  else if (dtype == GSTVD_F32) hipLaunchKernelGGL(ce_bwd_kernel<float>, dim3((unsigned)M), dim3(256), 0, s, (const float*)logits, ldl, labels, lse, stats, gscale, mean, V, ignore_index, (float*)dlogits, ldd);
-  else return GSTVD_E_DTYPE;
+  GSTVD_FOR_DTYPE(dtype, T, hipLaunchKernelGGL(ce_bwd_kernel<T>, dim3((unsigned)M), dim3(256), 0, s, (const T*)logits, ldl, labels, lse, stats, gscale, mean, V, ignore_index, (T*)dlogits, ldd));
   GSTVD_LAUNCH_CHECK();
   return 0;
 }
@@ -287,9 +256,7 @@ extern "C" int gstvd_ce_bwd_rows(const void* logits, int64_t ldl, const int64_t*
   if (!logits || !labels || !lse || !g || !dlogits) return GSTVD_E_NULL;
   if (M <= 0 || V <= 0 || (ldl % 4) || (ldd % 4) || ldd < V) return GSTVD_E_SHAPE;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == GSTVD_BF16) hipLaunchKernelGGL(ce_bwd_rows_kernel<bf16>, dim3((unsigned)M), dim3(256), 0, s, (const bf16*)logits, ldl, labels, lse, g, V, ignore_index, (bf16*)dlogits, ldd);
-  else if (dtype == GSTVD_F32) hipLaunchKernelGGL(ce_bwd_rows_kernel<float>, dim3((unsigned)M), dim3(256), 0, s, (const float*)logits, ldl, labels, lse, g, V, ignore_index, (float*)dlogits, ldd);
-  else return GSTVD_E_DTYPE;
+  GSTVD_FOR_DTYPE(dtype, T, hipLaunchKernelGGL(ce_bwd_rows_kernel<T>, dim3((unsigned)M), dim3(256), 0, s, (const T*)logits, ldl, labels, lse, g, V, ignore_index, (T*)dlogits, ldd));
   GSTVD_LAUNCH_CHECK();
   return 0;
 }
@@ -308,9 +275,7 @@ extern "C" int gstvd_answer_scores(const void* logits, int64_t ldl, const float*
   if (!logits || !lse || !dec_ids || !scores) return GSTVD_E_NULL;
   if (rows <= 0 || U <= 0) return GSTVD_E_SHAPE;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == GSTVD_BF16) hipLaunchKernelGGL(answer_scores_kernel<bf16>, dim3((unsigned)rows), dim3(64), 0, s, (const bf16*)logits, ldl, lse, dec_ids, U, scores);
-  else if (dtype == GSTVD_F32) hipLaunchKernelGGL(answer_scores_kernel<float>, dim3((unsigned)rows), dim3(64), 0, s, (const float*)logits, ldl, lse, dec_ids, U, scores);
-  else return GSTVD_E_DTYPE;
+  GSTVD_FOR_DTYPE(dtype, T, hipLaunchKernelGGL(answer_scores_kernel<T>, dim3((unsigned)rows), dim3(64), 0, s, (const T*)logits, ldl, lse, dec_ids, U, scores));
   GSTVD_LAUNCH_CHECK();
   return 0;
 }

@@ -10,6 +10,7 @@
 //  * the classifier's sum over the Hb columns: in the lane over its column tiles, then over the four 16-lane rows of the wave,
 //    then over the waves through LDS in wave order -- fixed order, no atomics, no cross-workgroup reduction: bit-reproducible.
 #include "gemm_common.h"
+#include "loss_reduce.h"
 
 struct NspP {
   const char* xt; const char* xv; const char* wt; const char* wv;
@@ -82,8 +83,23 @@ DEVFN void nsp_stage(T* img, const char* x, int64_t sb, int K, int64_t m0, int B
   }
 }
 
-template <typename T>
-__global__ __launch_bounds__(NSP_WAVES * 64) void nsp_head_kernel(NspP p) {
+// Training form (gstvd_nsp_train_fwd; train_disc.py, models/vilbert_dialog.py:1026-1041,1509-1510): the same launch plus what
+// backward needs -- pt, pv [B, Hb] fp32, the keep flags of the Dropout(0.1) in front of the classifier (drawn from the engine's
+// counter stream at element b * Hb + n) -- and, in place of prob0, the soft-label loss
+//   row_loss[b] = -(l[b, 0] * log_softmax(z[b])[0] + l[b, 1] * log_softmax(z[b])[1]),   stats = (sum_b, B, sum_b / B).
+struct NspTrainP : NspP {
+  const float* labels; int64_t ldl;
+  float* pt; float* pv; uint8_t* keep; float* row_loss;
+  float p; uint32_t site; const uint64_t* rng;
+};
+template <bool TRAIN> struct NspArgs { typedef NspP type; };
+template <> struct NspArgs<true> { typedef NspTrainP type; };
+
+// ONE body for both forms: what TRAIN adds sits under `if constexpr`, so the inference instantiation neither carries nor reads a
+// training field, and z is accumulated by the same instructions in the same order in both -- with p = 0 the same bits.
+template <typename T, bool TRAIN>
+__global__ __launch_bounds__(NSP_WAVES * 64) void nsp_head_kernel(typename NspArgs<TRAIN>::type q) {
+  const NspP& p = q;
   constexpr int PAD = NspCfg<T>::PAD;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   T* xs_t = (T*)smem;
@@ -91,6 +107,8 @@ __global__ __launch_bounds__(NSP_WAVES * 64) void nsp_head_kernel(NspP p) {
   float* zpart = (float*)(xs_v + NSP_ROWS * (p.Hv + PAD));        // [wave][row][2]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, li = lane & 15;
   const int64_t m0 = (int64_t)blockIdx.x * NSP_ROWS;
+  DropKey dk;
+  if constexpr (TRAIN) dk = make_drop(q.p, q.site, q.rng);
 
   nsp_stage<T>(xs_t, p.xt, p.sbt, p.H, m0, p.B, tid);
   nsp_stage<T>(xs_v, p.xv, p.sbv, p.Hv, m0, p.B, tid);
@@ -105,12 +123,28 @@ __global__ __launch_bounds__(NSP_WAVES * 64) void nsp_head_kernel(NspP p) {
     const int n = n0 + 4 * g;
     const f32x4 b1 = *(const f32x4*)(p.bt + n), b2 = *(const f32x4*)(p.bv + n);
     const f32x4 w0 = *(const f32x4*)(p.wn + n), w1 = *(const f32x4*)(p.wn + p.ldwn + n);
+    const int64_t m = m0 + li;
+    f32x4 fac, pt4, pv4;
+    uint32_t kb = 0;
+    if constexpr (TRAIN) fac = drop_factor4(dk, (uint64_t)(m * p.Hb + n));
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const float pt = fmaxf(at[r] + b1[r], 0.f), pv = fmaxf(av[r] + b2[r], 0.f);
-      const float f = p.sum ? pt + pv : pt * pv;
+      float f = p.sum ? pt + pv : pt * pv;
+      if constexpr (TRAIN) {
+        pt4[r] = pt; pv4[r] = pv;
+        if (dk.on) f *= fac[r];
+        kb |= (fac[r] != 0.f ? 1u : 0u) << (8 * r);
+      }
       z0 += f * w0[r];
       z1 += f * w1[r];
+    }
+    if constexpr (TRAIN) {
+      if (m < p.B) {
+        *(f32x4*)(q.pt + m * p.Hb + n) = pt4;
+        *(f32x4*)(q.pv + m * p.Hb + n) = pv4;
+        *(uint32_t*)(q.keep + m * p.Hb + n) = kb;
+      }
     }
   }
   z0 = rows_sum(z0);
@@ -129,28 +163,38 @@ __global__ __launch_bounds__(NSP_WAVES * 64) void nsp_head_kernel(NspP p) {
     // one value per batch row: evaluated in double, so the fp32 result is the correctly rounded one (denormal tail included)
     const double mx = (double)fmaxf(s0, s1);
     const double e0 = exp((double)s0 - mx), e1 = exp((double)s1 - mx);
-    p.prob0[m] = (float)(e0 / (e0 + e1));
+    if constexpr (TRAIN) {
+      const double lse = mx + log(e0 + e1);
+      const double l0 = (double)q.labels[m * q.ldl], l1 = (double)q.labels[m * q.ldl + 1];
+      q.row_loss[m] = (float)(-(l0 * ((double)s0 - lse) + l1 * ((double)s1 - lse)));
+    } else {
+      p.prob0[m] = (float)(e0 / (e0 + e1));
+    }
   }
 }
 
-template <typename T>
-static int nsp_launch(const NspP& p, char* name, int32_t name_len, hipStream_t s) {
+template <typename T, bool TRAIN>
+static int nsp_launch(const typename NspArgs<TRAIN>::type& q, char* name, int32_t name_len, hipStream_t s) {
   constexpr int PAD = NspCfg<T>::PAD;
-  const int lds = NSP_ROWS * (p.H + PAD + p.Hv + PAD) * (int)sizeof(T) + NSP_WAVES * NSP_ROWS * 2 * 4;
-  auto k = nsp_head_kernel<T>;
+  const int lds = NSP_ROWS * (q.H + PAD + q.Hv + PAD) * (int)sizeof(T) + NSP_WAVES * NSP_ROWS * 2 * 4;
+  auto k = nsp_head_kernel<T, TRAIN>;
   static int attr_rc = ensure_lds(k, NSP_ROWS * (1024 + PAD) * 2 * (int)sizeof(T) + NSP_WAVES * NSP_ROWS * 2 * 4);
   if (attr_rc) return attr_rc;
   if (name) {
     const int rc = copy_kernel_name((const void*)k, name, name_len);
     if (rc) return rc;
   }
-  hipLaunchKernelGGL(k, dim3((unsigned)((p.B + NSP_ROWS - 1) / NSP_ROWS)), dim3(NSP_WAVES * 64), lds, s, p);
+  hipLaunchKernelGGL(k, dim3((unsigned)((q.B + NSP_ROWS - 1) / NSP_ROWS)), dim3(NSP_WAVES * 64), lds, s, q);
   GSTVD_LAUNCH_CHECK();
   return 0;
 }
 
-extern "C" int gstvd_nsp_head(const gstvd_nsp_head_t* a, gstvd_stream_t stream) {
-  if (!a || !a->xt || !a->xv || !a->wt || !a->wv || !a->bt || !a->bv || !a->wn || !a->bn || !a->z || !a->prob0) return GSTVD_E_NULL;
+// The conditions both entry points share, as four steps in the order the return codes are tested; an entry point puts its own
+// conditions into the step they belong to (`null_own`: one of its own pointers is NULL; `shape_own`; `own16` / `own4`: its own
+// pointers that must be 16- / 4-byte aligned, or-ed together).  gstvd_nsp_head_t and gstvd_nsp_train_t name the shared fields alike.
+template <typename A>
+static int nsp_fwd_check(const A* a, bool null_own, bool shape_own, uintptr_t own16, uintptr_t own4) {
+  if (!a->xt || !a->xv || !a->wt || !a->wv || !a->bt || !a->bv || !a->wn || !a->bn || !a->z || null_own) return GSTVD_E_NULL;
   if (a->dtype != GSTVD_BF16 && a->dtype != GSTVD_F32) return GSTVD_E_DTYPE;
   if (a->fusion != 0 && a->fusion != 1) return GSTVD_E_UNSUPPORTED;
   if (a->kernel_name && a->kernel_name_len <= 1) return GSTVD_E_SHAPE;
@@ -158,107 +202,53 @@ extern "C" int gstvd_nsp_head(const gstvd_nsp_head_t* a, gstvd_stream_t stream) 
   for (int d : dims)
     if (d <= 0 || d % 16 || d > 1024) return GSTVD_E_SHAPE;
   if (a->B <= 0 || a->t_rows <= 0 || a->v_rows <= 0) return GSTVD_E_SHAPE;
-  if (a->ldt < a->H || a->ldv < a->Hv || a->ldwt < a->H || a->ldwv < a->Hv || a->ldwn < a->Hb || a->ldz < 2) return GSTVD_E_SHAPE;
+  if (a->ldt < a->H || a->ldv < a->Hv || a->ldwt < a->H || a->ldwv < a->Hv || a->ldwn < a->Hb || a->ldz < 2 || shape_own) return GSTVD_E_SHAPE;
   const int ve = a->dtype == GSTVD_BF16 ? 8 : 4;
   if ((a->ldt % ve) || (a->ldv % ve) || (a->ldwt % ve) || (a->ldwv % ve) || (a->ldwn % 4)) return GSTVD_E_ALIGN;
   if (((uintptr_t)a->xt | (uintptr_t)a->xv | (uintptr_t)a->wt | (uintptr_t)a->wv | (uintptr_t)a->bt | (uintptr_t)a->bv |
-       (uintptr_t)a->wn) & 15)
+       (uintptr_t)a->wn | own16) & 15)
     return GSTVD_E_ALIGN;
-  if (((uintptr_t)a->bn | (uintptr_t)a->z | (uintptr_t)a->prob0) & 3) return GSTVD_E_ALIGN;
-  NspP p;
+  if (((uintptr_t)a->bn | (uintptr_t)a->z | own4) & 3) return GSTVD_E_ALIGN;
+  return 0;
+}
+
+template <typename A>
+static void nsp_pack(NspP& p, const A* a, float* prob0) {
   p.xt = (const char*)a->xt; p.xv = (const char*)a->xv; p.wt = (const char*)a->wt; p.wv = (const char*)a->wv;
-  p.bt = a->bt; p.bv = a->bv; p.wn = a->wn; p.bn = a->bn; p.z = a->z; p.prob0 = a->prob0;
+  p.bt = a->bt; p.bv = a->bv; p.wn = a->wn; p.bn = a->bn; p.z = a->z; p.prob0 = prob0;
   p.ldt = a->ldt; p.ldv = a->ldv; p.sbt = a->t_rows * a->ldt; p.sbv = a->v_rows * a->ldv;
   p.ldwt = a->ldwt; p.ldwv = a->ldwv; p.ldwn = a->ldwn; p.ldz = a->ldz;
   p.B = a->B; p.H = a->H; p.Hv = a->Hv; p.Hb = a->Hb; p.sum = a->fusion;
+}
+
+extern "C" int gstvd_nsp_head(const gstvd_nsp_head_t* a, gstvd_stream_t stream) {
+  if (!a) return GSTVD_E_NULL;
+  const int rc = nsp_fwd_check(a, !a->prob0, false, 0, (uintptr_t)a->prob0);
+  if (rc) return rc;
+  NspP p;
+  nsp_pack(p, a, a->prob0);
+  GSTVD_FOR_DTYPE(a->dtype, T, return (nsp_launch<T, false>(p, a->kernel_name, a->kernel_name_len, (hipStream_t)stream)));
+}
+
+extern "C" int gstvd_nsp_train_fwd(const gstvd_nsp_train_t* a, gstvd_stream_t stream) {
+  if (!a) return GSTVD_E_NULL;
+  const int rc = nsp_fwd_check(a, !a->labels || !a->pt || !a->pv || !a->keep || !a->row_loss || !a->stats,
+                               a->ldl < 2 || !(a->p >= 0.f && a->p < 1.f) || (a->p > 0.f && !a->rng), (uintptr_t)a->pt | (uintptr_t)a->pv,
+                               (uintptr_t)a->labels | (uintptr_t)a->row_loss | (uintptr_t)a->stats | (uintptr_t)a->keep);
+  if (rc) return rc;
+  NspTrainP q;
+  nsp_pack(q, a, nullptr);
+  q.labels = a->labels; q.ldl = a->ldl; q.pt = a->pt; q.pv = a->pv; q.keep = a->keep; q.row_loss = a->row_loss;
+  q.p = a->p; q.site = a->site; q.rng = a->rng;
   hipStream_t s = (hipStream_t)stream;
-  return a->dtype == GSTVD_BF16 ? nsp_launch<bf16>(p, a->kernel_name, a->kernel_name_len, s)
-                                : nsp_launch<float>(p, a->kernel_name, a->kernel_name_len, s);
-}
-
-// ---- training form (gstvd_nsp_train_fwd / gstvd_nsp_train_bwd; train_disc.py, models/vilbert_dialog.py:1026-1041,1509-1510) ----
-// Forward: the launch above plus what backward needs -- pt, pv [B, Hb] fp32, the keep flags of the Dropout(0.1) in front of the
-// classifier (drawn from the engine's counter stream at element b * Hb + n) -- and the soft-label loss
-//   row_loss[b] = -(l[b, 0] * log_softmax(z[b])[0] + l[b, 1] * log_softmax(z[b])[1]),   stats = (sum_b, B, sum_b / B).
-// Same accumulation order as nsp_head_kernel: with p = 0 the scores are the same bits.
-struct NspTrainP {
-  NspP h;
-  const float* labels; int64_t ldl;
-  float* pt; float* pv; uint8_t* keep; float* row_loss;
-  float p; uint32_t site; const uint64_t* rng;
-};
-
-template <typename T>
-__global__ __launch_bounds__(NSP_WAVES * 64) void nsp_train_fwd_kernel(NspTrainP q) {
-  const NspP& p = q.h;
-  constexpr int PAD = NspCfg<T>::PAD;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  T* xs_t = (T*)smem;
-  T* xs_v = xs_t + NSP_ROWS * (p.H + PAD);
-  float* zpart = (float*)(xs_v + NSP_ROWS * (p.Hv + PAD));        // [wave][row][2]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, li = lane & 15;
-  const int64_t m0 = (int64_t)blockIdx.x * NSP_ROWS;
-  const DropKey dk = make_drop(q.p, q.site, q.rng);
-
-  nsp_stage<T>(xs_t, p.xt, p.sbt, p.H, m0, p.B, tid);
-  nsp_stage<T>(xs_v, p.xv, p.sbv, p.Hv, m0, p.B, tid);
-  __syncthreads();
-
-  const int64_t m = m0 + li;
-  float z0 = 0.f, z1 = 0.f;
-  for (int n0 = wave * 16; n0 < p.Hb; n0 += NSP_WAVES * 16) {
-    f32x4 at = {0.f, 0.f, 0.f, 0.f}, av = at;
-    nsp_dot(at, (const T*)p.wt + (int64_t)(n0 + li) * p.ldwt, xs_t + li * (p.H + PAD), p.H, g);
-    nsp_dot(av, (const T*)p.wv + (int64_t)(n0 + li) * p.ldwv, xs_v + li * (p.Hv + PAD), p.Hv, g);
-    const int n = n0 + 4 * g;
-    const f32x4 b1 = *(const f32x4*)(p.bt + n), b2 = *(const f32x4*)(p.bv + n);
-    const f32x4 w0 = *(const f32x4*)(p.wn + n), w1 = *(const f32x4*)(p.wn + p.ldwn + n);
-    const f32x4 fac = drop_factor4(dk, (uint64_t)(m * p.Hb + n));
-    f32x4 pt4, pv4;
-    uint32_t kb = 0;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const float pt = fmaxf(at[r] + b1[r], 0.f), pv = fmaxf(av[r] + b2[r], 0.f);
-      pt4[r] = pt; pv4[r] = pv;
-      float f = p.sum ? pt + pv : pt * pv;
-      if (dk.on) f *= fac[r];
-      kb |= (fac[r] != 0.f ? 1u : 0u) << (8 * r);
-      z0 += f * w0[r];
-      z1 += f * w1[r];
-    }
-    if (m < p.B) {
-      *(f32x4*)(q.pt + m * p.Hb + n) = pt4;
-      *(f32x4*)(q.pv + m * p.Hb + n) = pv4;
-      *(uint32_t*)(q.keep + m * p.Hb + n) = kb;
-    }
-  }
-  z0 = rows_sum(z0);
-  z1 = rows_sum(z1);
-  if (g == 0) { zpart[(wave * NSP_ROWS + li) * 2] = z0; zpart[(wave * NSP_ROWS + li) * 2 + 1] = z1; }
-  __syncthreads();
-  if (tid < NSP_ROWS && m0 + tid < p.B) {
-    float s0 = 0.f, s1 = 0.f;
-#pragma unroll
-    for (int w = 0; w < NSP_WAVES; ++w) { s0 += zpart[(w * NSP_ROWS + tid) * 2]; s1 += zpart[(w * NSP_ROWS + tid) * 2 + 1]; }
-    s0 += p.bn[0];
-    s1 += p.bn[1];
-    const int64_t r = m0 + tid;
-    p.z[r * p.ldz] = s0;
-    p.z[r * p.ldz + 1] = s1;
-    // one value per batch row: log-softmax in double, rounded once
-    const double mx = (double)fmaxf(s0, s1);
-    const double lse = mx + log(exp((double)s0 - mx) + exp((double)s1 - mx));
-    const double l0 = (double)q.labels[r * q.ldl], l1 = (double)q.labels[r * q.ldl + 1];
-    q.row_loss[r] = (float)(-(l0 * ((double)s0 - lse) + l1 * ((double)s1 - lse)));
-  }
-}
-
-// stats[0] = sum_b row_loss[b] (fixed order, one block), stats[1] = B, stats[2] = their quotient
-__global__ __launch_bounds__(64) void nsp_loss_reduce_kernel(const float* row_loss, int B, float* stats) {
-  float s = 0.f;
-  for (int i = threadIdx.x; i < B; i += 64) s += row_loss[i];
-  s = wave_sum(s);
-  if (threadIdx.x == 0) { stats[0] = s; stats[1] = (float)B; stats[2] = s / (float)B; }
+  GSTVD_FOR_DTYPE(a->dtype, T, {
+    const int lrc = nsp_launch<T, true>(q, a->kernel_name, a->kernel_name_len, s);
+    if (lrc) return lrc;
+  });
+  hipLaunchKernelGGL(row_loss_reduce_kernel, dim3(1), dim3(64), 0, s, (const float*)a->row_loss, (const int64_t*)nullptr, (int64_t)0, 0,
+                     (int64_t)a->B, a->stats);      // every row counts
+  GSTVD_LAUNCH_CHECK();
+  return 0;
 }
 
 // Backward of loss = gscale * sum_b row_loss[b] / B down to the gradients in front of the two ReLUs:
@@ -329,59 +319,6 @@ __global__ __launch_bounds__(256) void nsp_train_bwd_kernel(NspBwdP q) {
   }
 }
 
-template <typename T>
-static int nsp_train_launch(const NspTrainP& q, float* stats, char* name, int32_t name_len, hipStream_t s) {
-  constexpr int PAD = NspCfg<T>::PAD;
-  const NspP& p = q.h;
-  const int lds = NSP_ROWS * (p.H + PAD + p.Hv + PAD) * (int)sizeof(T) + NSP_WAVES * NSP_ROWS * 2 * 4;
-  auto k = nsp_train_fwd_kernel<T>;
-  static int attr_rc = ensure_lds(k, NSP_ROWS * (1024 + PAD) * 2 * (int)sizeof(T) + NSP_WAVES * NSP_ROWS * 2 * 4);
-  if (attr_rc) return attr_rc;
-  if (name) {
-    const int rc = copy_kernel_name((const void*)k, name, name_len);
-    if (rc) return rc;
-  }
-  hipLaunchKernelGGL(k, dim3((unsigned)((p.B + NSP_ROWS - 1) / NSP_ROWS)), dim3(NSP_WAVES * 64), lds, s, q);
-  GSTVD_LAUNCH_CHECK();
-  hipLaunchKernelGGL(nsp_loss_reduce_kernel, dim3(1), dim3(64), 0, s, (const float*)q.row_loss, p.B, stats);
-  GSTVD_LAUNCH_CHECK();
-  return 0;
-}
-
-extern "C" int gstvd_nsp_train_fwd(const gstvd_nsp_train_t* a, gstvd_stream_t stream) {
-  if (!a || !a->xt || !a->xv || !a->wt || !a->wv || !a->bt || !a->bv || !a->wn || !a->bn || !a->z || !a->labels || !a->pt || !a->pv ||
-      !a->keep || !a->row_loss || !a->stats)
-    return GSTVD_E_NULL;
-  if (a->dtype != GSTVD_BF16 && a->dtype != GSTVD_F32) return GSTVD_E_DTYPE;
-  if (a->fusion != 0 && a->fusion != 1) return GSTVD_E_UNSUPPORTED;
-  if (a->kernel_name && a->kernel_name_len <= 1) return GSTVD_E_SHAPE;
-  const int dims[3] = {a->H, a->Hv, a->Hb};
-  for (int d : dims)
-    if (d <= 0 || d % 16 || d > 1024) return GSTVD_E_SHAPE;
-  if (a->B <= 0 || a->t_rows <= 0 || a->v_rows <= 0) return GSTVD_E_SHAPE;
-  if (a->ldt < a->H || a->ldv < a->Hv || a->ldwt < a->H || a->ldwv < a->Hv || a->ldwn < a->Hb || a->ldz < 2 || a->ldl < 2) return GSTVD_E_SHAPE;
-  if (!(a->p >= 0.f && a->p < 1.f) || (a->p > 0.f && !a->rng)) return GSTVD_E_SHAPE;
-  const int ve = a->dtype == GSTVD_BF16 ? 8 : 4;
-  if ((a->ldt % ve) || (a->ldv % ve) || (a->ldwt % ve) || (a->ldwv % ve) || (a->ldwn % 4)) return GSTVD_E_ALIGN;
-  if (((uintptr_t)a->xt | (uintptr_t)a->xv | (uintptr_t)a->wt | (uintptr_t)a->wv | (uintptr_t)a->bt | (uintptr_t)a->bv |
-       (uintptr_t)a->wn | (uintptr_t)a->pt | (uintptr_t)a->pv) & 15)
-    return GSTVD_E_ALIGN;
-  if (((uintptr_t)a->bn | (uintptr_t)a->z | (uintptr_t)a->labels | (uintptr_t)a->row_loss | (uintptr_t)a->stats | (uintptr_t)a->keep) & 3)
-    return GSTVD_E_ALIGN;
-  NspTrainP q;
-  NspP& p = q.h;
-  p.xt = (const char*)a->xt; p.xv = (const char*)a->xv; p.wt = (const char*)a->wt; p.wv = (const char*)a->wv;
-  p.bt = a->bt; p.bv = a->bv; p.wn = a->wn; p.bn = a->bn; p.z = a->z; p.prob0 = nullptr;
-  p.ldt = a->ldt; p.ldv = a->ldv; p.sbt = a->t_rows * a->ldt; p.sbv = a->v_rows * a->ldv;
-  p.ldwt = a->ldwt; p.ldwv = a->ldwv; p.ldwn = a->ldwn; p.ldz = a->ldz;
-  p.B = a->B; p.H = a->H; p.Hv = a->Hv; p.Hb = a->Hb; p.sum = a->fusion;
-  q.labels = a->labels; q.ldl = a->ldl; q.pt = a->pt; q.pv = a->pv; q.keep = a->keep; q.row_loss = a->row_loss;
-  q.p = a->p; q.site = a->site; q.rng = a->rng;
-  hipStream_t s = (hipStream_t)stream;
-  return a->dtype == GSTVD_BF16 ? nsp_train_launch<bf16>(q, a->stats, a->kernel_name, a->kernel_name_len, s)
-                                : nsp_train_launch<float>(q, a->stats, a->kernel_name, a->kernel_name_len, s);
-}
-
 extern "C" int gstvd_nsp_train_bwd(const gstvd_nsp_train_t* a, gstvd_stream_t stream) {
   if (!a || !a->pt || !a->pv || !a->keep || !a->z || !a->labels || !a->wn || !a->dwn || !a->dbn || !a->dpt || !a->dpv) return GSTVD_E_NULL;
   if (a->dtype != GSTVD_BF16 && a->dtype != GSTVD_F32) return GSTVD_E_DTYPE;
@@ -397,8 +334,7 @@ extern "C" int gstvd_nsp_train_bwd(const gstvd_nsp_train_t* a, gstvd_stream_t st
   q.B = a->B; q.Hb = a->Hb; q.sum = a->fusion; q.acc_w = a->acc_w; q.acc_b = a->acc_b; q.p = a->p;
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid((unsigned)((a->Hb + 63) / 64));
-  if (a->dtype == GSTVD_BF16) hipLaunchKernelGGL(nsp_train_bwd_kernel<bf16>, grid, dim3(256), 0, s, q);
-  else hipLaunchKernelGGL(nsp_train_bwd_kernel<float>, grid, dim3(256), 0, s, q);
+  GSTVD_FOR_DTYPE(a->dtype, T, hipLaunchKernelGGL(nsp_train_bwd_kernel<T>, grid, dim3(256), 0, s, q));
   GSTVD_LAUNCH_CHECK();
   return 0;
 }

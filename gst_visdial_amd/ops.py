@@ -827,32 +827,43 @@ def answer_scores(logits, lse, dec_ids, rows, U, scores):
 FUSION = {"mul": 0, "sum": 1}
 
 
+def _nsp_fwd_desc(who, d, xt, t_rows, xv, v_rows, wt, bt, wv, bv, wn, bn, B, fusion, z, own_fp32, own_names=""):
+    """Validates the operands the NSP head's two forms share and fills the leading fields gstvd_nsp_head_t and gstvd_nsp_train_t
+    have in common into descriptor `d`.  `who` prefixes the error messages; `own_fp32`: the caller's further fp32 operands,
+    `own_names` what the message calls them."""
+    if fusion not in FUSION:
+        raise L.GstvdError("%s: fusion_method must be 'mul' or 'sum', got %r" % (who, fusion))
+    Hb = wt.shape[0]
+    if wt.dtype != xt.dtype or wv.dtype != xt.dtype or xv.dtype != xt.dtype:
+        raise L.GstvdError("%s: activations and pooler weights must share one dtype" % who)
+    for t in (bt, bv, wn, bn, z) + tuple(own_fp32):
+        if t.dtype != torch.float32:
+            raise L.GstvdError("%s: biases, the classifier%s and the outputs are fp32" % (who, own_names))
+    if xt.shape[0] < B * t_rows or xv.shape[0] < B * v_rows or z.shape[0] < B \
+            or z.stride(-1) != 1 or xt.stride(-1) != 1 or xv.stride(-1) != 1 or wt.stride(-1) != 1 or wv.stride(-1) != 1 \
+            or wn.stride(-1) != 1 or bt.numel() != Hb or bv.numel() != Hb or wv.shape[0] != Hb or tuple(wn.shape) != (2, Hb) \
+            or bn.numel() != 2:
+        raise L.GstvdError("%s: operand shapes do not match" % who)
+    d.xt, d.ldt, d.t_rows = _p(xt), xt.stride(0), t_rows
+    d.xv, d.ldv, d.v_rows = _p(xv), xv.stride(0), v_rows
+    d.wt, d.ldwt, d.wv, d.ldwv = _p(wt), wt.stride(0), _p(wv), wv.stride(0)
+    d.bt, d.bv, d.wn, d.ldwn, d.bn = _p(bt), _p(bv), _p(wn), wn.stride(0), _p(bn)
+    d.z, d.ldz = _p(z), z.stride(0)
+    d.B, d.H, d.Hv, d.Hb = B, wt.shape[1], wv.shape[1], Hb
+    d.dtype, d.fusion = dt(xt), FUSION[fusion]
+    return d
+
+
 def nsp_head(xt, t_rows, xv, v_rows, wt, bt, wv, bv, wn, bn, B, fusion, z, prob0):
     """NSP scores of the enc_only model in one launch (gstvd_nsp_head): row 0 of every batch row of the encoder's final
     activations xt [B * t_rows, H] / xv [B * v_rows, Hv] (read in place, row strides taken from the tensors) -> poolers
     wt [Hb, H], wv [Hb, Hv] (dtype of the activations) with fp32 biases -> `fusion` ('mul' | 'sum') -> wn [2, Hb], bn [2] in
     fp32 -> z [B, 2] fp32 and prob0 [B] fp32 = softmax(z, 1)[:, 0]."""
     lib = L.load()
-    if fusion not in FUSION:
-        raise L.GstvdError("nsp_head: fusion_method must be 'mul' or 'sum', got %r" % (fusion,))
-    if wt.dtype != xt.dtype or wv.dtype != xt.dtype or xv.dtype != xt.dtype:
-        raise L.GstvdError("nsp_head: activations and pooler weights must share one dtype")
-    for t in (bt, bv, wn, bn, z, prob0):
-        if t.dtype != torch.float32:
-            raise L.GstvdError("nsp_head: biases, the classifier and the outputs are fp32")
-    if xt.shape[0] < B * t_rows or xv.shape[0] < B * v_rows or z.shape[0] < B or prob0.shape[0] < B or prob0.stride(0) != 1 \
-            or z.stride(-1) != 1 or xt.stride(-1) != 1 or xv.stride(-1) != 1 or wt.stride(-1) != 1 or wv.stride(-1) != 1 \
-            or wn.stride(-1) != 1 or bt.numel() != wt.shape[0] or bv.numel() != wt.shape[0] or wv.shape[0] != wt.shape[0] \
-            or tuple(wn.shape) != (2, wt.shape[0]) or bn.numel() != 2:
+    d = _nsp_fwd_desc("nsp_head", L.NspHeadDesc(), xt, t_rows, xv, v_rows, wt, bt, wv, bv, wn, bn, B, fusion, z, (prob0,))
+    if prob0.shape[0] < B or prob0.stride(0) != 1:
         raise L.GstvdError("nsp_head: operand shapes do not match")
-    d = L.NspHeadDesc()
-    d.xt, d.ldt, d.t_rows = _p(xt), xt.stride(0), t_rows
-    d.xv, d.ldv, d.v_rows = _p(xv), xv.stride(0), v_rows
-    d.wt, d.ldwt, d.wv, d.ldwv = _p(wt), wt.stride(0), _p(wv), wv.stride(0)
-    d.bt, d.bv, d.wn, d.ldwn, d.bn = _p(bt), _p(bv), _p(wn), wn.stride(0), _p(bn)
-    d.z, d.ldz, d.prob0 = _p(z), z.stride(0), _p(prob0)
-    d.B, d.H, d.Hv, d.Hb = B, wt.shape[1], wv.shape[1], wt.shape[0]
-    d.dtype, d.fusion = dt(xt), FUSION[fusion]
+    d.prob0 = _p(prob0)
     e0 = _prof_begin()
     buf = C.create_string_buffer(256) if e0 is not None else None
     if buf is not None:
@@ -937,32 +948,15 @@ def nsp_train_desc(xt, t_rows, xv, v_rows, wt, bt, wv, bv, wn, bn, labels, B, fu
                    site=0, rng=None):
     """Descriptor of the NSP head in training form (gstvd_nsp_train_t), forward half; nsp_train_bwd fills in the rest.  Operands
     as ops.nsp_head; labels [B, 2] fp32 (soft), pt / pv [B, Hb] fp32 and keep [B, Hb] uint8 are written for backward."""
-    if fusion not in FUSION:
-        raise L.GstvdError("nsp_train: fusion_method must be 'mul' or 'sum', got %r" % (fusion,))
-    Hb = wt.shape[0]
-    if wt.dtype != xt.dtype or wv.dtype != xt.dtype or xv.dtype != xt.dtype:
-        raise L.GstvdError("nsp_train: activations and pooler weights must share one dtype")
-    for t in (bt, bv, wn, bn, z, labels, pt, pv, row_loss, stats):
-        if t.dtype != torch.float32:
-            raise L.GstvdError("nsp_train: biases, the classifier, the labels and the outputs are fp32")
-    if xt.shape[0] < B * t_rows or xv.shape[0] < B * v_rows or z.shape[0] < B or tuple(labels.shape) != (B, 2) or labels.stride(1) != 1 \
-            or z.stride(-1) != 1 or xt.stride(-1) != 1 or xv.stride(-1) != 1 or wt.stride(-1) != 1 or wv.stride(-1) != 1 \
-            or wn.stride(-1) != 1 or bt.numel() != Hb or bv.numel() != Hb or wv.shape[0] != Hb or tuple(wn.shape) != (2, Hb) \
-            or bn.numel() != 2 or keep.dtype != torch.uint8 or row_loss.numel() < B or stats.numel() < 3 \
-            or any(tuple(t.shape) != (B, Hb) or not t.is_contiguous() for t in (pt, pv, keep)):
+    d = _nsp_fwd_desc("nsp_train", L.NspTrainDesc(), xt, t_rows, xv, v_rows, wt, bt, wv, bv, wn, bn, B, fusion, z,
+                      (labels, pt, pv, row_loss, stats), ", the labels")
+    if tuple(labels.shape) != (B, 2) or labels.stride(1) != 1 or keep.dtype != torch.uint8 or row_loss.numel() < B or stats.numel() < 3 \
+            or any(tuple(t.shape) != (B, d.Hb) or not t.is_contiguous() for t in (pt, pv, keep)):
         raise L.GstvdError("nsp_train: operand shapes do not match")
-    d = L.NspTrainDesc()
-    d.xt, d.ldt, d.t_rows = _p(xt), xt.stride(0), t_rows
-    d.xv, d.ldv, d.v_rows = _p(xv), xv.stride(0), v_rows
-    d.wt, d.ldwt, d.wv, d.ldwv = _p(wt), wt.stride(0), _p(wv), wv.stride(0)
-    d.bt, d.bv, d.wn, d.ldwn, d.bn = _p(bt), _p(bv), _p(wn), wn.stride(0), _p(bn)
     d.labels, d.ldl = _p(labels), labels.stride(0)
-    d.z, d.ldz = _p(z), z.stride(0)
     d.pt, d.pv, d.keep, d.row_loss, d.stats = _p(pt), _p(pv), _p(keep), _p(row_loss), _p(stats)
     d.p, d.site = float(p), int(site)
     d.rng = rng.ptr() if (rng is not None and p > 0) else None
-    d.B, d.H, d.Hv, d.Hb = B, wt.shape[1], wv.shape[1], Hb
-    d.dtype, d.fusion = dt(xt), FUSION[fusion]
     d._keep = (xt, xv, wt, bt, wv, bv, wn, bn, labels, z, pt, pv, keep, row_loss, stats)
     return d
 

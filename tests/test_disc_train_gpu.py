@@ -431,6 +431,84 @@ def test_nsp_train_head_with_dropout_matches_float64_under_its_own_keep_flags(fu
     assert all(torch.equal(_bits(out[k]), _bits(out2[k])) for k in out)
 
 
+def _random_problem(Bn, H, Hv, Hb, seed):
+    """Non-integer operands: every partial sum is rounded, so z depends on the order of the additions."""
+    g = torch.Generator().manual_seed(seed)
+    rn = lambda *s: torch.randn(*s, generator=g)
+    return dict(xt=rn(Bn, H), xv=rn(Bn, Hv), wt=rn(Hb, H) * 0.1, wv=rn(Hb, Hv) * 0.1, bt=rn(Hb) * 0.1, bv=rn(Hb) * 0.1,
+                wn=rn(2, Hb) * 0.1, bn=rn(2) * 0.1, labels=torch.rand(Bn, 2, generator=g))
+
+
+# H = 272: one full 256-wide bf16 k step plus a 16-element tail; Hb = 144: wave 0 owns two column tiles, the other waves one;
+# Bn = 17, 33: a partly filled last workgroup
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
+@pytest.mark.parametrize("fusion", ["mul", "sum"])
+@pytest.mark.parametrize("shape", [(64, 96, 128), (272, 48, 144)], ids=lambda s: "x".join(map(str, s)))
+@pytest.mark.parametrize("Bn", [1, 17, 33])
+def test_nsp_head_and_the_training_forward_with_p_0_give_the_same_z_bits_on_random_operands(Bn, shape, fusion, dtype):
+    from gst_visdial_amd import ops
+    H, Hv, Hb = shape
+    Pm = _random_problem(Bn, H, Hv, Hb, seed=31 * Bn + Hb + (fusion == "sum"))
+    out, (xt, xv, wt, wv) = _run_train_head(Pm, fusion, dtype)      # p = 0; padded row strides, canaried write windows
+    f32 = lambda v: v.to(DEV, torch.float32).contiguous()
+    zbuf = _canary((Bn + 2) * 4, torch.float32).view(Bn + 2, 4)
+    pbuf = _canary(Bn + 8, torch.float32)
+    zh, ph = zbuf[1:Bn + 1, :2], pbuf[4:Bn + 4]
+    ops.nsp_head(xt, 3, xv, 2, wt, f32(Pm["bt"]), wv, f32(Pm["bv"]), f32(Pm["wn"]), f32(Pm["bn"]), Bn, fusion, zh, ph)
+    torch.cuda.synchronize()
+    zi, pi = _bits(zbuf), _bits(pbuf)
+    assert bool((zi[0] == POISON).all()) and bool((zi[Bn + 1] == POISON).all()) and bool((zi[:, 2:] == POISON).all())
+    assert bool((pi[:4] == POISON).all()) and bool((pi[Bn + 4:] == POISON).all())
+    z = zh.clone().cpu()
+    assert torch.isfinite(z).all() and bool((z != z.round()).all()) and bool((out["keep"] == 1).all())
+    assert torch.equal(_bits(out["z"]), _bits(z))
+
+
+@pytest.mark.parametrize("rows", [1, 64, 65, 257])
+def test_the_shared_row_loss_reduction_counts_exactly_and_sums_within_the_fp32_worst_case(rows):
+    """stats = (sum, count, quotient) of the one reduction kernel behind gstvd_ce_fwd (rows whose label is not ignore_index
+    count), gstvd_kl_fwd (rows with label 1; no labels: all) and gstvd_nsp_train_fwd (all).  The sum's bound is the worst case
+    of ANY order of rows - 1 fp32 additions, (rows - 1) * 2^-24 * sum |row_loss|; 257 is more than one stride of a 256-thread
+    block.  (rows = 1: the one row counts -- an all-ignored call has the quotient 0 / 0.)"""
+    from gst_visdial_amd import ops
+    ops.set_device(torch.device(DEV))
+    g = torch.Generator().manual_seed(500 + rows)
+    idx = torch.arange(rows)
+    skip = (idx % 3 == 0) & (idx < rows - 1)                        # some rows out; the last row always counts
+    cases = []
+
+    V, ignore = 37, -1
+    lab = torch.randint(0, V, (rows,), generator=g)
+    lab[skip] = ignore
+    logits = torch.zeros(rows, 40, device=DEV)
+    logits[:, :V] = (torch.randn(rows, V, generator=g) * 2.0).to(DEV)
+    row_loss, lse, stats = (torch.zeros(n, device=DEV) for n in (rows, rows, 4))
+    ops.ce_fwd(logits[:, :V], lab.to(DEV), rows, V, row_loss, lse, stats, ignore_index=ignore)
+    cases.append(("ce", row_loss, stats, int((~skip).sum())))
+
+    C = 11
+    target = torch.rand(rows, C, generator=g).to(DEV)
+    scores = (torch.randn(rows, C, generator=g) * 2.0).to(DEV)
+    for name, labels in (("kl, no labels", None), ("kl, 0/1 labels", (~skip).to(torch.int64).to(DEV))):
+        row_loss, lse, stats = (torch.zeros(n, device=DEV) for n in (rows, rows, 4))
+        ops.kl_fwd(scores, target, rows, C, row_loss, lse, stats, labels=labels)
+        cases.append((name, row_loss, stats, rows if labels is None else int((~skip).sum())))
+
+    out, _ = _run_train_head(_random_problem(rows, 64, 96, 128, seed=900 + rows), "mul", torch.float32)
+    cases.append(("nsp", out["row"], out["stats"], rows))
+    torch.cuda.synchronize()
+
+    for name, row_loss, stats, count in cases:
+        row_loss, stats = row_loss.cpu(), stats.cpu()
+        s64, a64 = row_loss.double().sum().item(), row_loss.double().abs().sum().item()
+        err, bound = abs(stats[0].double().item() - s64), (rows - 1) * 2.0 ** -24 * a64
+        print("\n%-15s rows %3d: count %3d, sum %.9g, |sum - sum64| %.3e (bound %.3e)" % (name, rows, stats[1].item(), stats[0].item(), err, bound))
+        assert a64 > 0 and torch.isfinite(row_loss).all(), name
+        assert stats[1].item() == count, (name, stats[1].item(), count)
+        assert torch.equal(_bits(stats[2:3]), _bits(stats[0:1] / stats[1:2])), (name, stats)
+        assert err <= bound, (name, err, bound)
+
+
 # ---------------------------------------------------------------------------------------------- engine level
 def _profiled(enc, r, backward=True):
     from gst_visdial_amd import ops
