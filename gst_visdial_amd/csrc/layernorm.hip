@@ -3,6 +3,8 @@
 // vector accesses, row statistics by wave shuffles, dropout masks regenerated from the counter hash.
 // Reference arithmetic: models/vilbert_dialog.py:283-296 (TF-style LN), :324-352 (BertEmbeddingsDialog),
 // :1420-1427 (BertImageEmbeddings), :416-420 / :458-462 / :735-742 (dense -> dropout -> LN(x + residual)).
+#include <stdio.h>
+
 #include "common.h"
 
 struct LnP {
@@ -10,7 +12,6 @@ struct LnP {
   // backward extras
   const void* dy; int64_t lddy; void* dres; int64_t lddres; void* dx; int64_t lddx; float* partial;
   float *dword, *dpos, *dtt, *dtt_ext;
-  int64_t nblk_wide;       // > 0: the caller sized `partial` for the 16-wave geometry
 };
 
 // rows per wave in backward: 2 (both rows' loads in flight before any reduction) for large M; 1 for small M, where the
@@ -413,28 +414,13 @@ static int ln_check(const gstvd_ln_t* p) {
   return 0;
 }
 
-template <typename T, int MODE>
-static int ln_fwd_nv(const gstvd_ln_t& f, hipStream_t s) {
-  dim3 grid((unsigned)((f.M + 3) / 4)), block(256);
-  if (f.H <= 256) hipLaunchKernelGGL((ln_fwd_kernel<T, MODE, 1>), grid, block, 0, s, f);
-  else if (f.H <= 768) hipLaunchKernelGGL((ln_fwd_kernel<T, MODE, 3>), grid, block, 0, s, f);
-  else if (f.H <= 1024) hipLaunchKernelGGL((ln_fwd_kernel<T, MODE, 4>), grid, block, 0, s, f);
-  else hipLaunchKernelGGL((ln_fwd_kernel<T, MODE, 8>), grid, block, 0, s, f);
-  GSTVD_LAUNCH_CHECK();
-  return 0;
-}
-template <typename T>
-static int ln_fwd_mode(const gstvd_ln_t& f, hipStream_t s) {
-  if (f.mode == GSTVD_LN_RESID) return ln_fwd_nv<T, GSTVD_LN_RESID>(f, s);
-  if (f.mode == GSTVD_LN_EMBED) return ln_fwd_nv<T, GSTVD_LN_EMBED>(f, s);
-  return ln_fwd_nv<T, GSTVD_LN_IMAGE>(f, s);
-}
-extern "C" int gstvd_ln_fwd(const gstvd_ln_t* p, gstvd_stream_t stream) {
-  int rc = ln_check(p);
-  if (rc) return rc;
-  if (!p->y) return GSTVD_E_NULL;
-  hipStream_t s = (hipStream_t)stream;
-  return p->dtype == GSTVD_BF16 ? ln_fwd_mode<bf16>(*p, s) : ln_fwd_mode<float>(*p, s);
+// The route of a launch: ONE decision -- mode, type, NV (256-column vectors per lane), RW (rows per wave), NW (waves per block) and
+// the grid -- taken here; the launchers below act on it and gstvd_ln_kernel_name reports it.
+struct LnRoute { int mode, bf, nv, rw, nw; int64_t nblk; };
+static inline int ln_nv(int64_t H) { return H <= 256 ? 1 : (H <= 768 ? 3 : (H <= 1024 ? 4 : 8)); }
+
+static LnRoute ln_fwd_route(const gstvd_ln_t& f) {
+  return {f.mode, f.dtype == GSTVD_BF16, ln_nv(f.H), 1, 4, (f.M + 3) / 4};
 }
 
 extern "C" int64_t gstvd_ln_bwd_blocks(int64_t M) { const int rpb = 4 * ln_bwd_rw(M); return (M + rpb - 1) / rpb; }
@@ -443,67 +429,116 @@ extern "C" int64_t gstvd_ln_bwd_blocks_for(int64_t M, int64_t H, int32_t mode) {
   return gstvd_ln_bwd_blocks(M);
 }
 
-template <typename T, int MODE>
-static int ln_bwd_wide(const LnP& p, hipStream_t s) {       // 16 one-row waves per block, H <= 768
-  constexpr int NW = 16;
-  const size_t lds = (size_t)NW * 3 * p.f.H * sizeof(float);
-  static int rc1 = (int)hipFuncSetAttribute((const void*)ln_bwd_kernel<T, MODE, 1, 1, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, NW * 3 * 256 * 4);
-  static int rc3 = (int)hipFuncSetAttribute((const void*)ln_bwd_kernel<T, MODE, 3, 1, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, NW * 3 * 768 * 4);
-  if (rc1 | rc3) return rc1 | rc3;
-  dim3 grid((unsigned)((p.f.M + NW - 1) / NW)), block(NW * 64);
-  if (p.f.H <= 256) hipLaunchKernelGGL((ln_bwd_kernel<T, MODE, 1, 1, NW>), grid, block, lds, s, p);
-  else hipLaunchKernelGGL((ln_bwd_kernel<T, MODE, 3, 1, NW>), grid, block, lds, s, p);
-  GSTVD_LAUNCH_CHECK();
+// nblk = 0 or gstvd_ln_bwd_blocks(M): 4 waves per block; nblk = gstvd_ln_bwd_blocks_for(M, H, mode) where that differs: the
+// caller sized `partial` for the 16-wave geometry; any other count is refused
+static int ln_bwd_route(const gstvd_ln_bwd_t& b, LnRoute* r) {
+  const gstvd_ln_t& f = b.f;
+  const int64_t narrow = gstvd_ln_bwd_blocks(f.M), wide = gstvd_ln_bwd_blocks_for(f.M, f.H, f.mode);
+  if (b.nblk > 0 && b.nblk != wide && b.nblk != narrow) return GSTVD_E_SHAPE;
+  const bool w = b.nblk > 0 && b.nblk == wide && wide != narrow;
+  *r = {f.mode, f.dtype == GSTVD_BF16, ln_nv(f.H), w ? 1 : ln_bwd_rw(f.M), w ? 16 : 4, w ? wide : narrow};
   return 0;
 }
 
-template <typename T, int MODE, int RW>
-static int ln_bwd_nv(const LnP& p, hipStream_t s) {
-  dim3 grid((unsigned)gstvd_ln_bwd_blocks(p.f.M)), block(256);
-  // embedding mode: 4 slabs, or (H <= 1024) 5 slabs + the word strip per wave
-  size_t lds = (size_t)4 * (MODE == GSTVD_LN_EMBED ? (p.f.H <= 1024 ? 6 : 4) : 3) * p.f.H * sizeof(float);
-  if (lds > 48 * 1024) {
-    static int rc8 = (int)hipFuncSetAttribute((const void*)ln_bwd_kernel<T, MODE, 8, RW>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 4 * 2048 * 4)
-                   | (int)hipFuncSetAttribute((const void*)ln_bwd_kernel<T, MODE, 4, RW>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 6 * 1024 * 4)
-                   | (int)hipFuncSetAttribute((const void*)ln_bwd_kernel<T, MODE, 3, RW>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 6 * 768 * 4);
-    if (rc8) return rc8;
-  }
-  if (p.f.H <= 256) hipLaunchKernelGGL((ln_bwd_kernel<T, MODE, 1, RW>), grid, block, lds, s, p);
-  else if (p.f.H <= 768) hipLaunchKernelGGL((ln_bwd_kernel<T, MODE, 3, RW>), grid, block, lds, s, p);
-  else if (p.f.H <= 1024) hipLaunchKernelGGL((ln_bwd_kernel<T, MODE, 4, RW>), grid, block, lds, s, p);
-  else hipLaunchKernelGGL((ln_bwd_kernel<T, MODE, 8, RW>), grid, block, lds, s, p);
+// plan-only mode (gstvd_ln_kernel_name): the launch site records the kernel handle it WOULD have launched and launches nothing
+template <typename T, int MODE, int NV>
+static int ln_fwd_go(const gstvd_ln_t& f, const LnRoute& r, hipStream_t s, const void** plan) {
+  if (plan) { *plan = (const void*)ln_fwd_kernel<T, MODE, NV>; return 0; }
+  hipLaunchKernelGGL((ln_fwd_kernel<T, MODE, NV>), dim3((unsigned)r.nblk), dim3(256), 0, s, f);
   GSTVD_LAUNCH_CHECK();
   return 0;
 }
 template <typename T, int MODE>
-static int ln_bwd_rows(const LnP& p, hipStream_t s) {
-  if constexpr (MODE != GSTVD_LN_EMBED) {
-    if (p.nblk_wide > 0) return ln_bwd_wide<T, MODE>(p, s);
-  }
-  return ln_bwd_rw(p.f.M) == 1 ? ln_bwd_nv<T, MODE, 1>(p, s) : ln_bwd_nv<T, MODE, 2>(p, s);
+static int ln_fwd_nv(const gstvd_ln_t& f, const LnRoute& r, hipStream_t s, const void** plan) {
+  if (r.nv == 1) return ln_fwd_go<T, MODE, 1>(f, r, s, plan);
+  if (r.nv == 3) return ln_fwd_go<T, MODE, 3>(f, r, s, plan);
+  if (r.nv == 4) return ln_fwd_go<T, MODE, 4>(f, r, s, plan);
+  return ln_fwd_go<T, MODE, 8>(f, r, s, plan);
 }
 template <typename T>
-static int ln_bwd_mode(const LnP& p, hipStream_t s) {
-  if (p.f.mode == GSTVD_LN_RESID) return ln_bwd_rows<T, GSTVD_LN_RESID>(p, s);
-  if (p.f.mode == GSTVD_LN_EMBED) return ln_bwd_rows<T, GSTVD_LN_EMBED>(p, s);
-  return ln_bwd_rows<T, GSTVD_LN_IMAGE>(p, s);
+static int ln_fwd_mode(const gstvd_ln_t& f, const LnRoute& r, hipStream_t s, const void** plan) {
+  if (r.mode == GSTVD_LN_RESID) return ln_fwd_nv<T, GSTVD_LN_RESID>(f, r, s, plan);
+  if (r.mode == GSTVD_LN_EMBED) return ln_fwd_nv<T, GSTVD_LN_EMBED>(f, r, s, plan);
+  return ln_fwd_nv<T, GSTVD_LN_IMAGE>(f, r, s, plan);
 }
-extern "C" int gstvd_ln_bwd(const gstvd_ln_bwd_t* b, gstvd_stream_t stream) {
+static int ln_fwd_entry(const gstvd_ln_t* p, hipStream_t s, const void** plan) {
+  int rc = ln_check(p);
+  if (rc) return rc;
+  if (!p->y) return GSTVD_E_NULL;
+  const LnRoute r = ln_fwd_route(*p);
+  return r.bf ? ln_fwd_mode<bf16>(*p, r, s, plan) : ln_fwd_mode<float>(*p, r, s, plan);
+}
+extern "C" int gstvd_ln_fwd(const gstvd_ln_t* p, gstvd_stream_t stream) { return ln_fwd_entry(p, (hipStream_t)stream, nullptr); }
+
+template <typename T, int MODE, int NV, int RW, int NW>
+static int ln_bwd_go(const LnP& p, const LnRoute& r, hipStream_t s, const void** plan) {
+  if (plan) { *plan = (const void*)ln_bwd_kernel<T, MODE, NV, RW, NW>; return 0; }
+  // per wave: 3 slabs; embedding mode 4, or (H <= 1024) 5 slabs + the word strip
+  constexpr int NVL = MODE == GSTVD_LN_EMBED ? (NV <= 4 ? 6 : 4) : 3;
+  constexpr int HMAX = NV == 1 ? 256 : (NV == 3 ? 768 : (NV == 4 ? 1024 : 2048));
+  const size_t lds = (size_t)NW * NVL * p.f.H * sizeof(float);
+  if (lds > 48 * 1024) {
+    static int rc = (int)hipFuncSetAttribute((const void*)ln_bwd_kernel<T, MODE, NV, RW, NW>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             NW * NVL * HMAX * 4);
+    if (rc) return rc;
+  }
+  hipLaunchKernelGGL((ln_bwd_kernel<T, MODE, NV, RW, NW>), dim3((unsigned)r.nblk), dim3(NW * 64), lds, s, p);
+  GSTVD_LAUNCH_CHECK();
+  return 0;
+}
+template <typename T, int MODE, int NV>
+static int ln_bwd_geo(const LnP& p, const LnRoute& r, hipStream_t s, const void** plan) {
+  // the 16-wave block exists for one-row waves, H <= 768, outside embedding mode: what ln_bwd_nw / gstvd_ln_bwd_blocks_for name;
+  // should the two ever drift apart, the launch fails here instead of taking another kernel than the one reported
+  if constexpr (MODE != GSTVD_LN_EMBED && NV <= 3) {
+    if (r.nw == 16 && r.rw == 1) return ln_bwd_go<T, MODE, NV, 1, 16>(p, r, s, plan);
+  }
+  if (r.nw != 4) return GSTVD_E_UNSUPPORTED;
+  return r.rw == 1 ? ln_bwd_go<T, MODE, NV, 1, 4>(p, r, s, plan) : ln_bwd_go<T, MODE, NV, 2, 4>(p, r, s, plan);
+}
+template <typename T, int MODE>
+static int ln_bwd_nv(const LnP& p, const LnRoute& r, hipStream_t s, const void** plan) {
+  if (r.nv == 1) return ln_bwd_geo<T, MODE, 1>(p, r, s, plan);
+  if (r.nv == 3) return ln_bwd_geo<T, MODE, 3>(p, r, s, plan);
+  if (r.nv == 4) return ln_bwd_geo<T, MODE, 4>(p, r, s, plan);
+  return ln_bwd_geo<T, MODE, 8>(p, r, s, plan);
+}
+template <typename T>
+static int ln_bwd_mode(const LnP& p, const LnRoute& r, hipStream_t s, const void** plan) {
+  if (r.mode == GSTVD_LN_RESID) return ln_bwd_nv<T, GSTVD_LN_RESID>(p, r, s, plan);
+  if (r.mode == GSTVD_LN_EMBED) return ln_bwd_nv<T, GSTVD_LN_EMBED>(p, r, s, plan);
+  return ln_bwd_nv<T, GSTVD_LN_IMAGE>(p, r, s, plan);
+}
+static int ln_bwd_entry(const gstvd_ln_bwd_t* b, hipStream_t s, const void** plan) {
   if (!b) return GSTVD_E_NULL;
   int rc = ln_check(&b->f);
   if (rc) return rc;
   if (!b->dy || !b->partial) return GSTVD_E_NULL;
   if (b->f.mode == GSTVD_LN_EMBED && (!b->dword || !b->dpos || !b->dtt || !b->dtt_ext)) return GSTVD_E_NULL;
   if (b->f.mode == GSTVD_LN_IMAGE && !b->dres) return GSTVD_E_NULL;
+  LnRoute r;
+  rc = ln_bwd_route(*b, &r);
+  if (rc) return rc;
   LnP p;
   p.f = b->f; p.dy = b->dy; p.lddy = b->lddy; p.dres = b->dres; p.lddres = b->lddres;
   p.dx = b->dx; p.lddx = b->lddx; p.partial = b->partial;
   p.dword = b->dword; p.dpos = b->dpos; p.dtt = b->dtt; p.dtt_ext = b->dtt_ext;
-  const int64_t wide = gstvd_ln_bwd_blocks_for(b->f.M, b->f.H, b->f.mode);
-  p.nblk_wide = (b->nblk > 0 && b->nblk == wide && wide != gstvd_ln_bwd_blocks(b->f.M)) ? wide : 0;
-  if (b->nblk > 0 && b->nblk != wide && b->nblk != gstvd_ln_bwd_blocks(b->f.M)) return GSTVD_E_SHAPE;
-  hipStream_t s = (hipStream_t)stream;
-  return b->f.dtype == GSTVD_BF16 ? ln_bwd_mode<bf16>(p, s) : ln_bwd_mode<float>(p, s);
+  return r.bf ? ln_bwd_mode<bf16>(p, r, s, plan) : ln_bwd_mode<float>(p, r, s, plan);
+}
+extern "C" int gstvd_ln_bwd(const gstvd_ln_bwd_t* b, gstvd_stream_t stream) { return ln_bwd_entry(b, (hipStream_t)stream, nullptr); }
+
+// Which kernel would gstvd_ln_fwd (bwd == 0: desc is a gstvd_ln_t) / gstvd_ln_bwd (bwd != 0: desc is a gstvd_ln_bwd_t) launch?  The
+// entry point runs exactly as for a launch -- same checks, same route -- in plan-only mode: nothing is launched, no memory is
+// touched.  Writes the device function's (mangled) symbol into buf; a buffer too small for it is GSTVD_E_SHAPE.
+extern "C" int gstvd_ln_kernel_name(const void* desc, int32_t bwd, char* buf, int32_t buf_len) {
+  if (!desc || !buf || buf_len <= 1) return GSTVD_E_NULL;
+  const void* fn = nullptr;
+  const int rc = bwd ? ln_bwd_entry((const gstvd_ln_bwd_t*)desc, nullptr, &fn) : ln_fwd_entry((const gstvd_ln_t*)desc, nullptr, &fn);
+  if (rc) return rc;
+  const char* name = fn ? hipKernelNameRefByPtr(fn, nullptr) : nullptr;
+  if (!name) return GSTVD_E_UNSUPPORTED;
+  const int n = snprintf(buf, (size_t)buf_len, "%s", name);
+  return n >= 0 && n < buf_len ? 0 : GSTVD_E_SHAPE;
 }
 
 extern "C" int gstvd_colsum_partials(const float* partial, int64_t nblk, int64_t nvec, int64_t H,

@@ -224,7 +224,8 @@ extern "C" int gstvd_vl_split(const void* d_enc, int64_t B, int64_t R, int64_t T
 }
 
 // 2: gstvd_ln_bwd_t.nblk (round 2); 3: gstvd_gemm_ln_fwd / _bwd, debug entry gone (round 3); 4: gstvd_gemm_grouped_adamw,
-// gstvd_adamw_blocks (round 4); 5: block_map_dev / nblocks of the grouped launches (round 5)
+// gstvd_adamw_blocks (round 4); 5: block_map_dev / nblocks of the grouped launches (round 5); 6-9: DESIGN.md
+// (entry points added without a signature change do not bump it: gstvd_rows_* / gstvd_kl_*, gstvd_ln_kernel_name)
 extern "C" int gstvd_abi_version(void) { return 9; }
 extern "C" const char* gstvd_build_arch(void) { return "gfx950"; }
 

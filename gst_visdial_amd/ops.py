@@ -547,8 +547,7 @@ def ln_bwd_blocks(M, H=None, mode=None):
     return int(L.load().gstvd_ln_bwd_blocks_for(M, H, mode))
 
 
-def ln_bwd(fwd_kw, dy, partial, dres=None, dx=None, dword=None, dpos=None, dtt=None, dtt_ext=None, nblk=0):
-    lib = L.load()
+def _ln_bwd_desc(fwd_kw, dy, partial, dres=None, dx=None, dword=None, dpos=None, dtt=None, dtt_ext=None, nblk=0):
     b = L.LnBwdDesc()
     b.f = _ln_desc(**fwd_kw)
     b.nblk = nblk
@@ -557,9 +556,24 @@ def ln_bwd(fwd_kw, dy, partial, dres=None, dx=None, dword=None, dpos=None, dtt=N
     b.dx, b.lddx = _p(dx), (dx.stride(-2) if dx is not None else 0)
     b.partial = _p(partial)
     b.dword, b.dpos, b.dtt, b.dtt_ext = _p(dword), _p(dpos), _p(dtt), _p(dtt_ext)
+    return b
+
+
+def ln_bwd(fwd_kw, dy, partial, dres=None, dx=None, dword=None, dpos=None, dtt=None, dtt_ext=None, nblk=0):
+    lib = L.load()
+    b = _ln_bwd_desc(fwd_kw, dy, partial, dres, dx, dword, dpos, dtt, dtt_ext, nblk)
     e0 = _prof_begin()
     L.check("gstvd_ln_bwd", lib.gstvd_ln_bwd(C.byref(b), _stream()))
     _prof_end(e0, "ln_bwd", 0.0, 5.0 * b.f.M * b.f.H * (2 if b.f.dtype == BF16 else 4), (b.f.M, b.f.H, b.f.mode))
+
+
+def ln_kernel_symbol(fwd_kw, bwd=None):
+    """(Mangled) symbol of the device kernel ln_fwd(**fwd_kw) launches, or -- bwd: the dict of ln_bwd's other arguments -- the one
+    ln_bwd(fwd_kw, **bwd) launches: asked of the library's own route decision (gstvd_ln_kernel_name), nothing is launched."""
+    d = _ln_desc(**fwd_kw) if bwd is None else _ln_bwd_desc(fwd_kw, **bwd)
+    buf = C.create_string_buffer(512)
+    L.check("gstvd_ln_kernel_name", L.load().gstvd_ln_kernel_name(C.byref(d), int(bwd is not None), buf, 512))
+    return buf.value.decode()
 
 
 def colsum_partials(partial, nblk, nvec, H, out0, out1, out2, accumulate):

@@ -150,6 +150,11 @@ typedef struct {
 int64_t gstvd_ln_bwd_blocks(int64_t M);                                    /* upper bound for every (H, mode) */
 int64_t gstvd_ln_bwd_blocks_for(int64_t M, int64_t H, int32_t mode);       /* the geometry gstvd_ln_bwd uses when told so via nblk */
 int gstvd_ln_bwd(const gstvd_ln_bwd_t* p, gstvd_stream_t s);
+/* Measurement support: the (mangled) symbol of the device kernel that gstvd_ln_fwd (bwd == 0, desc: a gstvd_ln_t) or gstvd_ln_bwd
+ * (bwd != 0, desc: a gstvd_ln_bwd_t) launches for this descriptor -- the launchers' own route decision (mode, type, 256-column
+ * vectors per lane, rows per wave, waves per block), same checks and return codes as the launch; nothing is launched.
+ * GSTVD_E_SHAPE when buf_len is too small for the name. */
+int gstvd_ln_kernel_name(const void* desc, int32_t bwd, char* buf, int32_t buf_len);
 
 /* LayerNorm folded into the Linear next to it, for latency-bound row counts (the decoder's M = rows x 25; csrc/gemm_rows.hip).
  * Both take a gstvd_gemm_t whose A operand is NOT read (A is produced in the kernel; M, K = the LayerNorm's M, H; bf16 operands,

@@ -17,7 +17,7 @@ def declared_symbols():
 def test_header_declares_expected_entry_points():
     syms = declared_symbols()
     for must in ("gstvd_gemm", "gstvd_ln_fwd", "gstvd_ln_bwd", "gstvd_attn_fwd", "gstvd_attn_bwd", "gstvd_ce_fwd",
-                 "gstvd_ce_bwd", "gstvd_adamw"):
+                 "gstvd_ce_bwd", "gstvd_adamw", "gstvd_ln_kernel_name"):
         assert must in syms
 
 
