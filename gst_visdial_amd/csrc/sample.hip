@@ -3,7 +3,8 @@
 //   top-k: z < (k-th largest z) -> -inf   (ties with the k-th value stay, like the reference's `logits < topk(...)[..., -1]`)
 //   top-p (utils/decoding_utils.py:22-34): a token stays when the probability mass of the tokens sorted in FRONT of it is <= top_p
 //          (the reference removes `cumsum(softmax(sorted)) > top_p` shifted right by one, so the token that crosses top_p stays)
-//   p = softmax(z);  id = first index whose cumulative probability reaches u * sum(p)   (inverse CDF, decoding.draw_from_uniform)
+//   p = softmax(z);  id = first index of non-zero probability whose cumulative probability reaches u * sum(p)   (inverse CDF,
+//          decoding.draw_from_uniform; the last such index when rounding leaves every sum below it, 0 when nothing has weight)
 // One workgroup per dialog row, the row's V scaled logits live in LDS (V = 30522: 119 KB of the CU's 160 KB).  It replaces
 // ~25 small library kernels per step (topk's multi-block radix passes, softmax, cumsum scans, compares, copies) by one launch,
 // and keeps library kernels with their own temporary storage / memset nodes out of the captured token graph.
@@ -61,6 +62,7 @@ __global__ __launch_bounds__(NT) void sample_topk_kernel(gstvd_sample_t a) {
   __shared__ __attribute__((aligned(16))) float smf[NWV];
   __shared__ __attribute__((aligned(16))) float smc[NWV];
   __shared__ int smi[NWV];
+  __shared__ int smj[NWV];
   __shared__ float swave[NWV];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.x, V = a.V;
   const T* row = (const T*)a.logits + (int64_t)b * a.ld;
@@ -221,24 +223,37 @@ __global__ __launch_bounds__(NT) void sample_topk_kernel(gstvd_sample_t a) {
     if (w < wave) pre += t;
     total += t;
   }
+  // The draw: the FIRST position of non-zero weight whose inclusive running sum reaches x = u * total, or the last position of
+  // non-zero weight when none does (0 when the row has no weight at all).  Two threads form their running sums in different
+  // orders (a sequential sum inside the segment, the scan's tree in front of it), so the sums need not be monotone across a
+  // thread border: a block minimum over per-thread candidates that carry weight does not depend on that, a count of run < x would.
   const float x = a.u[b] * total;
-  int cnt = 0;
+  int cand = V, lastk = -1;
   float run = pre;
 #pragma unroll
   for (int j = 0; j < SEGMAX; ++j) {
     run += e[j];
-    cnt += (j < seg && i0 + j < i1 && run < x) ? 1 : 0;
+    const bool kept = e[j] > 0.f;                            // (0 past the end of the segment and of the row)
+    cand = (kept && run >= x && i0 + j < cand) ? i0 + j : cand;
+    lastk = kept ? i0 + j : lastk;
   }
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+  for (int o = 32; o > 0; o >>= 1) {
+    const int c2 = __shfl_xor(cand, o, 64), l2 = __shfl_xor(lastk, o, 64);
+    cand = c2 < cand ? c2 : cand;
+    lastk = l2 > lastk ? l2 : lastk;
+  }
   __syncthreads();
-  if (lane == 0) smi[wave] = cnt;
+  if (lane == 0) { smi[wave] = cand; smj[wave] = lastk; }
   __syncthreads();
   if (tid == 0) {
-    int idx = 0;
+    int idx = V, last = -1;
 #pragma unroll
-    for (int i = 0; i < NWV; ++i) idx += smi[i];
-    if (idx > V - 1) idx = V - 1;
+    for (int i = 0; i < NWV; ++i) {
+      idx = smi[i] < idx ? smi[i] : idx;
+      last = smj[i] > last ? smj[i] : last;
+    }
+    if (idx >= V) idx = last >= 0 ? last : 0;                  // (a row with no weight at all -- everything banned: id 0)
     a.out[(int64_t)b * a.out_stride] = idx;
   }
 }

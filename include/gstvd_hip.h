@@ -273,7 +273,10 @@ int gstvd_answer_scores(const void* logits, int64_t ldl, const float* lse, const
  * utils/decoding_utils.py:4-35 for the top-k rule): z = logits / temperature (banned -> -inf); top_k > 0: z below the k-th
  * largest z -> -inf (ties with it stay); out[b * out_stride] = first index whose cumulative softmax probability reaches
  * u[b] * total (inverse CDF -- the draw the oracle substitutes for the reference's torch.multinomial, whose stream is device
- * specific).  logits [B, ld >= V] fp32 or bf16; banned: NULL or uint8 [B, banned_ld >= V]; u [B] in (0, 1).
+ * specific).  The id carries a non-zero weight whenever a token of the row does: it is the first position of non-zero weight
+ * whose running sum reaches u * total, the LAST such position when rounding leaves every sum below it (never the clamp V - 1,
+ * never a filtered or banned token next to a CDF step), and 0 for a row in which everything is banned.
+ * logits [B, ld >= V] fp32 or bf16; banned: NULL or uint8 [B, banned_ld >= V]; u [B] in (0, 1).
  * ngram > 0 (ABI 5): the n-gram filter itself, utils/decoding_utils.py:38-77 (batch_ngram_blocking + _get_generated_ngrams), runs
  * in the same launch -- a token is banned when it would complete an n-gram that occurs in the row's history hist[b, 0..hist_T)
  * (int64 ids, row stride hist_ld; n-grams that contain one of the n_special ids in `special` are ignored) and whose first n-1
