@@ -95,6 +95,21 @@ class NspTrainDesc(C.Structure):
                 ("kernel_name", _vp), ("kernel_name_len", _i32), ("reserved_", _i32)]
 
 
+class BeamStepDesc(C.Structure):
+    """gstvd_beam_step_t: one beam-search step -- the K best of the K x V continuations of every dialog row."""
+    _fields_ = [("logits", _vp), ("ld", _i64), ("dtype", _i32), ("B", _i32), ("K", _i32), ("V", _i32),
+                ("score_in", _vp), ("done_in", _vp), ("score_out", _vp), ("done_out", _vp), ("parent", _vp),
+                ("ids_tm", _vp), ("ids_stride", _i64), ("positions", _i32), ("pos", _i32),
+                ("workspace", _vp), ("eos", _i32), ("pad", _i32)]
+
+
+class BeamReorderDesc(C.Structure):
+    """gstvd_beam_reorder_t: the K | V columns of the surviving beams' self-attention caches, every decoder layer in one launch."""
+    _fields_ = [("src", _vp * 16), ("dst", _vp * 16), ("parent", _vp), ("row_stride", _i64), ("ld", _i64),
+                ("n_layers", _i32), ("B", _i32), ("K", _i32), ("H", _i32), ("Umax", _i32), ("t", _i32), ("dtype", _i32),
+                ("reserved_", _i32)]
+
+
 class ColsumEntry(C.Structure):
     _fields_ = [("partial", _vp), ("out", _vp * 3), ("nblk", _i64), ("stride", _i64), ("H", _i64),
                 ("nvec", _i32), ("accumulate", _i32 * 3), ("blk0", _i32)]
@@ -159,6 +174,8 @@ SIGNATURES = {
     "gstvd_kl_bwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _vp, _i64, _vp]),
     "gstvd_nsp_train_fwd": (_i32, [C.POINTER(NspTrainDesc), _vp]),
     "gstvd_nsp_train_bwd": (_i32, [C.POINTER(NspTrainDesc), _vp]),
+    "gstvd_beam_step": (_i32, [C.POINTER(BeamStepDesc), _vp]),
+    "gstvd_beam_reorder": (_i32, [C.POINTER(BeamReorderDesc), _vp]),
 }
 
 _STATUS = {-1: "GSTVD_E_DTYPE", -2: "GSTVD_E_SHAPE", -3: "GSTVD_E_ALIGN", -4: "GSTVD_E_NULL", -5: "GSTVD_E_UNSUPPORTED"}

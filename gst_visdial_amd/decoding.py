@@ -105,3 +105,29 @@ def draw_from_uniform(prob, u):
     x = u.to(c.device, torch.float32).reshape(-1, 1) * c[:, -1:]
     idx = (c < x).sum(-1, keepdim=True)
     return idx.clamp_(max=prob.shape[-1] - 1)
+
+
+def beam_backtrace(tok, parent):
+    """Sequences of the final beams of a beam search: tok, parent [steps, B, K] (token and parent beam that new beam i of step s
+    recorded) -> [B, K, steps] int64, by walking the parents back from the last step.  Gathers only: no host round trip."""
+    steps = tok.shape[0]
+    idx = torch.arange(tok.shape[2], device=tok.device).expand(tok.shape[1], -1)          # [B, K] beam index at the current step
+    out = []
+    for s in range(steps - 1, -1, -1):
+        out.append(tok[s].gather(1, idx))
+        idx = parent[s].long().gather(1, idx)
+    return torch.stack(out[::-1], dim=2).long()
+
+
+def beam_finalize(sequences, scores, eos_token_id, pad_token_id, length_penalty=1.0):
+    """End of a beam search: sequences [B, K, steps], scores [B, K] (summed token log-probabilities) -> (sequences with PAD after
+    the first EOS, scores / len ** length_penalty, order), each row's hypotheses best first and ties to the smaller beam index;
+    len = tokens up to and including the first EOS, or `steps` without one; order [B, K] = the beam index each place came from."""
+    B, K, steps = sequences.shape
+    eq = (sequences == eos_token_id).long()
+    seen = torch.cumsum(eq, dim=2)
+    length = ((seen - eq) == 0).long().sum(2)                 # positions with no EOS in front of them: up to and incl. the first
+    final = scores.float() / length.float().pow(float(length_penalty))
+    final, order = torch.sort(final, dim=1, descending=True, stable=True)
+    seqs = pad_after_eos(sequences.reshape(B * K, steps), eos_token_id, pad_token_id).view(B, K, steps)
+    return seqs.gather(1, order[:, :, None].expand(B, K, steps)), final, order

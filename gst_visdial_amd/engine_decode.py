@@ -10,11 +10,13 @@ from ._lib import GstvdError, EPI_GELU
 
 
 class DecodeMixin(object):
-    def _decode_plan(self, ins, L0, max_seq_len):
+    def _decode_plan(self, ins, L0, max_seq_len, beams=1):
         """Builds the two device programs of a decode call on the engine's arena: `encode()` (encoder, VLFusion, the
         cross-attention K/V of all decoder layers -- once per call) and `one_token(tok, t)` (ONE token per row through
         the decoder stack at position t, its self-attention K/V appended to the per-layer caches) -> fp32 logits [B, V].
-        `ins` = (feats, loc, img_mask, ids, segs, att_mask, dec_ids) are the tensors the kernels read."""
+        `ins` = (feats, loc, img_mask, ids, segs, att_mask, dec_ids) are the tensors the kernels read.
+        beams = K > 1 (beam_search): B * K decoder rows over the B encoder rows -- cross-attention with kv_group = K -- and a
+        SECOND set of self-attention caches; `one_token(tok, t, cset)` appends to and reads set `cset` (st["QKVc"][cset])."""
         feats, loc, img_mask, ids, segs, att_mask, dec_ids = ins
         dc = self.dec_cfg
         st = {}
@@ -32,11 +34,17 @@ class DecodeMixin(object):
             st["Umax"] = Umax
             # per-layer cache of the fused Q|K|V rows, [B, Umax, 3H]: the QKV GEMM of position t writes its output rows straight
             # into cache[:, t] (row stride Umax*3H), attention reads K / V from the same rows -- no append copies
-            st["QKVc"] = [Act(self.buf(Bn * Umax, 3 * H), Bn * Umax, 3 * H) for _ in range(L)]
+            if beams > 1:
+                Dn = Bn * beams
+                st["QKVc"] = [[Act(self.buf(Dn * Umax, 3 * H), Dn * Umax, 3 * H) for _ in range(L)] for _ in range(2)]
+            else:
+                st["QKVc"] = [Act(self.buf(Bn * Umax, 3 * H), Bn * Umax, 3 * H) for _ in range(L)]
             st["mark"] = self.arena.mark()
 
-        def one_token(tok, t):
-            I, Bn, S, kv, QKVc, Umax = st["I"], st["Bn"], st["S"], st["kv"], st["QKVc"], st["Umax"]
+        def one_token(tok, t, cset=0):
+            I, Bn, S, kv, QKVc, Umax = st["I"], st["Bn"] * beams, st["S"], st["kv"], st["QKVc"], st["Umax"]
+            if beams > 1:
+                QKVc = QKVc[cset]
             V, Vp = dc.vocab_size, self.flat.Vp
             L, H, nh, eps = dc.num_hidden_layers, dc.hidden_size, dc.num_attention_heads, dc.layer_norm_eps
             d = H // nh
@@ -67,7 +75,8 @@ class DecodeMixin(object):
                     ops.gemm(ctx.t, self.W[p + ".ao.w"], pre1.t, Bn, H, H, bias=self.Pv[p + ".ao.b"], addend=y.t)
                     ops.gemv_ln(pre1.t, self.W[p + ".cq.w"], q.t, Bn, H, H, self.Pv[p + ".ln1.w"], self.Pv[p + ".ln1.b"], eps,
                                 y_out=y1.t, bias=self.Pv[p + ".cq.b"])
-                    ctx = self.attn((q, 0), (kv, 2 * i * H), (kv, (2 * i + 1) * H), Bn, nh, 1, S, d, I["emask"], False, -1e9, 0.0)
+                    ctx = self.attn((q, 0), (kv, 2 * i * H), (kv, (2 * i + 1) * H), Bn, nh, 1, S, d, I["emask"], False, -1e9, 0.0,
+                                    kv_group=beams)
                     pre2, y2, a, aux = self.act(Bn, H), self.act(Bn, H), self.act(Bn, I_), self.buf(Bn, I_)
                     ops.gemm(ctx.t, self.W[p + ".co.w"], pre2.t, Bn, H, H, bias=self.Pv[p + ".co.b"], addend=y1.t)
                     ops.gemv_ln(pre2.t, self.W[p + ".fi.w"], a.t, Bn, I_, H, self.Pv[p + ".ln2.w"], self.Pv[p + ".ln2.b"], eps,
@@ -79,7 +88,8 @@ class DecodeMixin(object):
                 ao = self.lin(ctx, p + ".ao.w", p + ".ao.b", H, H)
                 y1 = self.ln(ao, y, p + ".ln1.w", p + ".ln1.b", H, 0.0, None, eps)
                 q = self.lin(y1, p + ".cq.w", p + ".cq.b", H, H)
-                ctx = self.attn((q, 0), (kv, 2 * i * H), (kv, (2 * i + 1) * H), Bn, nh, 1, S, d, I["emask"], False, -1e9, 0.0)
+                ctx = self.attn((q, 0), (kv, 2 * i * H), (kv, (2 * i + 1) * H), Bn, nh, 1, S, d, I["emask"], False, -1e9, 0.0,
+                                kv_group=beams)
                 co = self.lin(ctx, p + ".co.w", p + ".co.b", H, H)
                 y2 = self.ln(co, y1, p + ".ln2.w", p + ".ln2.b", H, 0.0, None, eps)
                 a = self.lin(y2, p + ".fi.w", p + ".fi.b", dc.intermediate_size, H, gelu=True)
@@ -164,6 +174,9 @@ class DecodeMixin(object):
         the caller passes none) instead of torch.multinomial (whose stream is device specific) -- the same rule the oracle
         applies to the reference, so sampled ids can be compared under real sampling."""
         from . import decoding
+        if _.get("num_beams") is not None and int(_["num_beams"]) > 1:
+            raise GstvdError("sample() draws one answer per row; num_beams = %d is beam search: call beam_search(...) or "
+                             "model(..., num_beams=K)" % int(_["num_beams"]))
         dc = self.dec_cfg
         if segs is None:
             segs = torch.zeros_like(ids)
@@ -219,6 +232,135 @@ class DecodeMixin(object):
         # this marker -- but executes nothing, so the eager call's encoder states are still what the arena holds)
         self._last_decode = (dst, ids.shape[0], self.arena)
         return out
+
+    # ------------------------------------------------------------------------------------------ beam search
+    def _beam_buffers(self, Bn, K, L0, max_seq_len, dev):
+        """Static state of a beam call: the time-major id buffer, the ping-pong (score, done) pairs, one parent row per generated
+        position, the step kernel's workspace and the state in front of the first step (s[b,0] = 0, s[b,j>0] = -inf)."""
+        init = torch.full((Bn, K), -float("inf"), dtype=torch.float32, device=dev)
+        init[:, 0] = 0.0
+        return dict(cur=torch.zeros(L0 + max_seq_len, Bn * K, dtype=torch.long, device=dev),
+                    score=[torch.zeros(Bn, K, dtype=torch.float32, device=dev) for _ in range(2)],
+                    done=[torch.zeros(Bn, K, dtype=torch.int32, device=dev) for _ in range(2)],
+                    parent=torch.zeros(max_seq_len, Bn, K, dtype=torch.int32, device=dev),
+                    ws=ops.beam_workspace(Bn, K, dev), init=init)
+
+    def _beam_loop(self, one_token, st, bufs, dec_ids, L0, max_seq_len, K):
+        """The whole beam loop on static buffers, free of host synchronisation (eager issue and graph capture run this same
+        code): the prefix positions feed all K rows of a dialog alike; from position L0 - 1 on every token step is followed by
+        the beam step (gstvd_beam_step: token row t + 1 of the id buffer, parents, the other (score, done) pair) and, while
+        another token step follows, by the reorder of the self-attention caches into the OTHER cache set, which the next token
+        step then appends to and reads.  K = 1 keeps one cache set (its only parent is itself).  Returns the index of the final
+        (score, done) pair."""
+        dc = self.dec_cfg
+        cur, score, done = bufs["cur"], bufs["score"], bufs["done"]
+        Bn = dec_ids.shape[0]
+        cur[:L0] = dec_ids.t()[:, :, None].expand(L0, Bn, K).reshape(L0, Bn * K)
+        score[0].copy_(bufs["init"])
+        done[0].zero_()
+        steps, cset = L0 + max_seq_len - 1, 0
+        H, Umax = dc.hidden_size, st["Umax"]
+        for t in range(steps):
+            logits = one_token(cur[t], t, cset)
+            if t < L0 - 1:
+                continue
+            g = t - (L0 - 1)
+            ops.beam_step(logits, score[g & 1], done[g & 1], score[(g + 1) & 1], done[(g + 1) & 1], bufs["parent"][g], cur, t + 1,
+                          bufs["ws"], dc.eos_token_id, dc.pad_token_id)
+            if K > 1 and t + 1 < steps:
+                sets = st["QKVc"]
+                ops.beam_reorder([a.t.view(Bn * K, Umax, 3 * H) for a in sets[cset]],
+                                 [a.t.view(Bn * K, Umax, 3 * H) for a in sets[1 - cset]], bufs["parent"][g], t, H)
+                cset = 1 - cset
+        return max_seq_len & 1
+
+    def _beam_session(self, ins, L0, max_seq_len, K):
+        """hipGraph form of a beam call, as `_decode_session` is of a sampling call: static copies of the inputs, one graph for
+        `encode` and ONE for the whole beam loop (every position's decoder stack, beam step and cache reorder)."""
+        static = tuple(x.clone() if x is not None else None for x in ins)
+        ids, dec_ids = static[3], static[6]
+        bufs = self._beam_buffers(ids.shape[0], K, L0, max_seq_len, ids.device)
+        encode, one_token, st = self._decode_plan(static, L0, max_seq_len, beams=K)
+        from .graph import capture, gc_quiet
+        with gc_quiet():
+            g_enc = torch.cuda.CUDAGraph()
+            with capture(g_enc):
+                encode()
+            g_dec = torch.cuda.CUDAGraph()
+            with capture(g_dec, pool=g_enc.pool(), quiesce=False):
+                fin = self._beam_loop(one_token, st, bufs, dec_ids, L0, max_seq_len, K)
+
+        def refresh(new):
+            for dst, src in zip(static, new):
+                if dst is not None:
+                    dst.copy_(src)
+
+        return refresh, g_enc.replay, g_dec.replay, bufs, fin
+
+    @torch.no_grad()
+    def beam_search(self, feats, loc, img_mask, ids, segs, att_mask, dec_ids, num_beams=5, length_penalty=1.0, max_seq_len=18):
+        """Deterministic beam-search decoding of the answer -> (sequences [B, K, max_seq_len] int64, scores [B, K] fp32), the K
+        hypotheses of every dialog row best first.  The reference has no beam search; this is the rule:
+
+        Layout: B dialog rows, K = num_beams in 1..8; beam j of dialog b is decoder row b*K + j.  Encoder, VLFusion and the cross
+        K/V projection run once on the B rows; cross-attention shares one encoder row among K decoder rows (kv_group = K).
+        State: per beam an fp32 score s[b,j] (sum of token log-probabilities) and a flag done[b,j]; in front of the first
+        generated position s[b,0] = 0, s[b,j>0] = -inf, nothing done.  The L0 prefix tokens of `dec_ids` go to all K rows alike.
+        Step: a live beam j offers every v in [0, V) with score s[b,j] + logp_j[v], logp_j[v] = (z[v] - max z) - log sum exp(z -
+        max z) in fp32 over the row's raw logits (temperature, top-k and top-p play no part); a done beam offers exactly one
+        candidate, (j, PAD), with its score unchanged.  The K best candidates of the row become the new beams in order: higher
+        score first, equal scores by smaller j, then smaller v; -inf sorts last under the same index rule.  New beam i records
+        parent[b,i] = j, tok[b,i] = v, the score, and done = done_j or v == EOS.
+        End: all max_seq_len steps always run (done beams are frozen, so the result equals stopping early and nothing depends on
+        the host).  Sequences are the parents walked back from the last step; len = tokens up to and including the first EOS, or
+        max_seq_len; final score = s / len ** length_penalty; hypotheses best first, ties to the smaller beam index; PAD follows
+        the first EOS (decoding.pad_after_eos).
+
+        The first call with a shape runs eagerly; from then on (params['amd_decode_graph'], default on) it replays two captured
+        hipGraphs keyed by shapes, K and length_penalty: the encoder side, and the whole loop -- decoder stack, beam step
+        (gstvd_beam_step) and cache reorder (gstvd_beam_reorder) at every position.  The back-trace and the final ordering are
+        sync-free torch index work (decoding.beam_backtrace / beam_finalize).  A beam call leaves no decode state behind:
+        `rescore_sampled` after it raises its "no decode state" error."""
+        from . import decoding
+        dc = self.dec_cfg
+        K = int(num_beams)
+        if not 1 <= K <= ops.BEAM_MAX:
+            raise GstvdError("beam_search: num_beams must be in 1..%d, got %r" % (ops.BEAM_MAX, num_beams))
+        if dc.vocab_size > ops.SAMPLE_MAX_VOCAB:
+            raise GstvdError("beam_search: vocabulary %d exceeds the beam kernel's %d" % (dc.vocab_size, ops.SAMPLE_MAX_VOCAB))
+        if dc.num_hidden_layers > ops.BEAM_MAX_LAYERS:
+            raise GstvdError("beam_search: at most %d decoder layers" % ops.BEAM_MAX_LAYERS)
+        if segs is None:
+            segs = torch.zeros_like(ids)
+        ins = (feats, loc, img_mask, ids, segs, att_mask, dec_ids)
+        L0, Bn = dec_ids.shape[1], ids.shape[0]
+        sig = ("beam", L0, max_seq_len, K, float(length_penalty)) + tuple((tuple(x.shape), x.dtype) if x is not None else None for x in ins)
+        use_graph = bool(self.model.params.get("amd_decode_graph", True))
+        self.prepare(ids.device)
+        sess = self._decode_sessions.get(sig) if use_graph else None
+        if sess is not None:
+            refresh, run_encode, run_loop, bufs, fin = sess
+            refresh(ins)
+            run_encode()
+            run_loop()
+        else:
+            run_encode, one_token, st = self._decode_plan(ins, L0, max_seq_len, beams=K)
+            run_encode()
+            bufs = self._beam_buffers(Bn, K, L0, max_seq_len, ids.device)
+            calls0 = _libmod.N_CALLS[0]
+            fin = self._beam_loop(one_token, st, bufs, dec_ids, L0, max_seq_len, K)
+            self.decode_lib_calls_per_token = (_libmod.N_CALLS[0] - calls0) / float(L0 + max_seq_len - 1)
+        tok = bufs["cur"][L0:].view(max_seq_len, Bn, K)
+        seqs = decoding.beam_backtrace(tok, bufs["parent"])
+        out, scores, order = decoding.beam_finalize(seqs, bufs["score"][fin], dc.eos_token_id, dc.pad_token_id, length_penalty)
+        # (what the step kernel decided, unsorted, for tests / debugging: tokens and parents per step, summed log-probabilities)
+        self.last = dict(beam_tok=tok.clone(), beam_parent=bufs["parent"].clone(), beam_logp=bufs["score"][fin].clone(), beam_order=order)
+        if use_graph and sess is None:
+            if len(self._decode_sessions) >= 4:
+                self._decode_sessions.clear()
+            self._decode_sessions[sig] = self._beam_session(ins, L0, max_seq_len, K)
+        self._last_decode = None          # K rows per dialog: not a state rescore_sampled could score an answer against
+        return out, scores
 
     @torch.no_grad()
     def rescore_sampled(self, dec_ids, dec_mask=None, loss_reduction=False):

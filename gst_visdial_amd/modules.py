@@ -439,13 +439,45 @@ class EncoderDecoderModel(nn.Module):
         return self.engine.score_candidates(enc_image_features, enc_image_spatials, enc_image_mask, enc_input_ids,
                                             enc_segments, enc_attention_mask, dec_input_ids, dec_attention_mask, num_options)
 
+    def beam_search(self, enc_image_features=None, enc_image_spatials=None, enc_image_mask=None, enc_input_ids=None,
+                    enc_segments=None, enc_attention_mask=None, dec_input_ids=None, num_beams=5, length_penalty=1.0,
+                    ngram_blocking_size=0, max_seq_len=18, **_):
+        """Beam-search decoding of the answer (Engine.beam_search states the rule): the forward's encoder / decoder keywords ->
+        (sequences [B, K, max_seq_len] int64, scores [B, K] fp32 = log-probability sum / len ** length_penalty), each row's K
+        hypotheses best first.  n-gram blocking is not available with beams."""
+        from ._lib import GstvdError
+        if int(ngram_blocking_size or 0) > 0:
+            raise GstvdError("beam search does not support ngram_blocking_size > 0 (a per-beam history needs the back-pointers); "
+                             "use the sampling branch for n-gram blocking")
+        if not 1 <= int(num_beams) <= 8:
+            raise GstvdError("num_beams must be in 1..8, got %r" % (num_beams,))
+        return self.engine.beam_search(enc_image_features, enc_image_spatials, enc_image_mask, enc_input_ids, enc_segments,
+                                       enc_attention_mask, dec_input_ids, num_beams=int(num_beams),
+                                       length_penalty=float(length_penalty), max_seq_len=int(max_seq_len))
+
     def forward(self, enc_image_features=None, enc_image_spatials=None, enc_image_mask=None, enc_image_target=None,
                 enc_image_label=None, enc_next_sentence_labels=None, enc_input_ids=None, enc_segments=None,
                 enc_sep_indices=None, enc_mlm_labels=None, enc_attention_mask=None, dec_input_ids=None,
                 dec_attention_mask=None, dec_labels=None, loss_reduction=True, **decoding_kwargs):
+        """Generation modes: `num_beams` = K > 1 among the decoding keywords decodes by beam search and returns each row's best
+        hypothesis as LongTensor [B, 18] -- type and padding of the sampling branch.  `temperature`, `top_k` and `top_p` are
+        accepted and ignored there (beam search ranks raw log-probabilities); `length_penalty` (default 1.0) is honoured;
+        `ngram_blocking_size` > 0 with beams raises (a per-beam history needs the back-pointers).  `num_beams` absent or 1: the
+        sampling branch, untouched."""
         mode = self.params["mode"]
         if "train" in mode or "eval" in mode:
             return self.engine.step(enc_image_features, enc_image_spatials, enc_image_mask, enc_input_ids, enc_segments,
                                     enc_attention_mask, dec_input_ids, dec_attention_mask, dec_labels, loss_reduction)
+        num_beams = decoding_kwargs.get("num_beams")
+        if num_beams is not None and int(num_beams) > 1:
+            kw = dict(num_beams=int(num_beams), ngram_blocking_size=decoding_kwargs.get("ngram_blocking_size", 0))
+            for k in ("length_penalty", "max_seq_len"):
+                if k in decoding_kwargs:
+                    kw[k] = decoding_kwargs[k]
+            seqs, _ = self.beam_search(enc_image_features, enc_image_spatials, enc_image_mask, enc_input_ids, enc_segments,
+                                       enc_attention_mask, dec_input_ids, **kw)
+            return seqs[:, 0].contiguous()
+        if num_beams is not None:
+            decoding_kwargs = {k: v for k, v in decoding_kwargs.items() if k != "num_beams"}
         return self.engine.sample(enc_image_features, enc_image_spatials, enc_image_mask, enc_input_ids, enc_segments,
                                   enc_attention_mask, dec_input_ids, **decoding_kwargs)

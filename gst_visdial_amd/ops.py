@@ -838,6 +838,89 @@ def answer_scores(logits, lse, dec_ids, rows, U, scores):
                                                            dt(logits), _p(scores), _stream()))
 
 
+BEAM_MAX = 8                   # beams per dialog row (gstvd_beam_step: K * K candidates fit one wave)
+BEAM_MAX_LAYERS = 16           # layer pointers a gstvd_beam_reorder_t carries
+
+
+def _beam_state(who, B, K, i32=(), f32=()):
+    for ts, want in ((i32, torch.int32), (f32, torch.float32)):
+        for t in ts:
+            if not t.is_cuda:
+                raise L.GstvdError("gst_visdial_amd ops need GPU tensors (got %s); there is no CPU path" % t.device)
+            if t.dtype != want or t.numel() != B * K or not t.is_contiguous():
+                raise L.GstvdError("%s: beam state is contiguous [B = %d, K = %d]: scores fp32, done / parent int32" % (who, B, K))
+
+
+def beam_workspace(B, K, device):
+    """The caller-owned workspace of `beam_step`: [B, K, K] pairs of (fp32 score, int32 token)."""
+    return torch.empty(B * K * K * 2, dtype=torch.int32, device=device)
+
+
+def beam_step(logits, score_in, done_in, score_out, done_out, parent, ids_tm, pos, workspace, eos, pad):
+    """One beam-search step (gstvd_beam_step; the rule is stated in include/gstvd_hip.h and Engine.beam_search): logits
+    [B*K, V] fp32 / bf16 (dense rows, row stride free) and the state in front of the step -- score_in fp32 [B, K], done_in int32
+    [B, K] -- give the K best of every dialog row's candidates, in order: token -> ids_tm[pos, b*K + i] (the time-major int64 id
+    buffer [positions, >= B*K]), parent int32 [B, K], score_out, done_out.  In and out state are different tensors; `workspace`
+    from `beam_workspace`.  No host synchronisation."""
+    lib = L.load()
+    if score_in.dim() != 2:
+        raise L.GstvdError("beam_step: score_in must be [B, K]")
+    B, K = score_in.shape
+    if not 1 <= K <= BEAM_MAX:
+        raise L.GstvdError("beam_step: num_beams must be in 1..%d, got %d" % (BEAM_MAX, K))
+    _beam_state("beam_step", B, K, i32=(done_in, done_out, parent), f32=(score_in, score_out))
+    if not logits.is_cuda or logits.dim() != 2 or logits.shape[0] != B * K or logits.stride(1) != 1 or logits.dtype not in _DT:
+        raise L.GstvdError("beam_step: logits must be fp32 / bf16 [B*K = %d, V] on the GPU with dense rows" % (B * K))
+    V = logits.shape[1]
+    if V > SAMPLE_MAX_VOCAB:
+        raise L.GstvdError("beam_step: vocabulary %d exceeds the kernel's %d" % (V, SAMPLE_MAX_VOCAB))
+    if (not ids_tm.is_cuda or ids_tm.dtype != torch.int64 or ids_tm.dim() != 2 or ids_tm.stride(1) != 1 or ids_tm.shape[1] < B * K
+            or not 0 <= pos < ids_tm.shape[0]):
+        raise L.GstvdError("beam_step: ids_tm must be int64 [positions > pos, >= B*K] time-major with dense rows")
+    if score_in.data_ptr() == score_out.data_ptr() or done_in.data_ptr() == done_out.data_ptr():
+        raise L.GstvdError("beam_step: in and out state must be different buffers")
+    if not workspace.is_cuda or workspace.dtype != torch.int32 or workspace.numel() < 2 * B * K * K or not workspace.is_contiguous():
+        raise L.GstvdError("beam_step: workspace must come from beam_workspace(B, K)")
+    d = L.BeamStepDesc()
+    d.logits, d.ld, d.dtype, d.B, d.K, d.V = _p(logits), logits.stride(0), dt(logits), B, K, V
+    d.score_in, d.done_in, d.score_out, d.done_out, d.parent = _p(score_in), _p(done_in), _p(score_out), _p(done_out), _p(parent)
+    d.ids_tm, d.ids_stride, d.positions, d.pos = _p(ids_tm), ids_tm.stride(0), ids_tm.shape[0], int(pos)
+    d.workspace, d.eos, d.pad = _p(workspace), int(eos), int(pad)
+    e0 = _prof_begin()
+    L.check("gstvd_beam_step", lib.gstvd_beam_step(C.byref(d), _stream()))
+    _prof_end(e0, "beam_step", 0.0, float(B * K * V * logits.element_size()), (B, K, V))
+
+
+def beam_reorder(src, dst, parent, t, H):
+    """dst[l][b*K + i, :t+1, H:3H] = src[l][b*K + parent[b, i], :t+1, H:3H] for every layer l in one launch (gstvd_beam_reorder).
+    src / dst: lists (<= 16) of the per-layer fused Q|K|V caches [B*K, Umax, 3H] (contiguous, one dtype), src[l] is not dst[l];
+    parent int32 [B, K].  Only the K | V columns of positions <= t are written."""
+    lib = L.load()
+    if parent.dim() != 2:
+        raise L.GstvdError("beam_reorder: parent must be [B, K]")
+    B, K = parent.shape
+    _beam_state("beam_reorder", B, K, i32=(parent,))
+    n = len(src)
+    if not 1 <= K <= BEAM_MAX or not 1 <= n <= BEAM_MAX_LAYERS or len(dst) != n:
+        raise L.GstvdError("beam_reorder: 1..%d beams and 1..%d layers, as many dst as src caches" % (BEAM_MAX, BEAM_MAX_LAYERS))
+    shape, dtype = tuple(src[0].shape), src[0].dtype
+    if len(shape) != 3 or shape[0] != B * K or shape[2] != 3 * H or dtype not in _DT or not 0 <= t < shape[1]:
+        raise L.GstvdError("beam_reorder: caches are fp32 / bf16 [B*K = %d, Umax > t, 3H = %d], got %s" % (B * K, 3 * H, shape))
+    d = L.BeamReorderDesc()
+    for l in range(n):
+        for c in (src[l], dst[l]):
+            if not c.is_cuda or tuple(c.shape) != shape or c.dtype != dtype or not c.is_contiguous():
+                raise L.GstvdError("beam_reorder: every cache must be a contiguous GPU tensor of one shape and dtype")
+        if src[l].data_ptr() == dst[l].data_ptr():
+            raise L.GstvdError("beam_reorder: src and dst must be two cache sets (a permutation cannot run in place)")
+        d.src[l], d.dst[l] = _p(src[l]), _p(dst[l])
+    d.parent, d.row_stride, d.ld = _p(parent), shape[1] * shape[2], shape[2]
+    d.n_layers, d.B, d.K, d.H, d.Umax, d.t, d.dtype = n, B, K, H, shape[1], int(t), _DT[dtype]
+    e0 = _prof_begin()
+    L.check("gstvd_beam_reorder", lib.gstvd_beam_reorder(C.byref(d), _stream()))
+    _prof_end(e0, "beam_reorder", 0.0, 2.0 * n * B * K * (t + 1) * 2 * H * src[0].element_size(), (n, B * K, t + 1, H))
+
+
 FUSION = {"mul": 0, "sum": 1}
 
 

@@ -459,6 +459,50 @@ typedef struct {
 int gstvd_nsp_train_fwd(const gstvd_nsp_train_t* a, gstvd_stream_t s);
 int gstvd_nsp_train_bwd(const gstvd_nsp_train_t* a, gstvd_stream_t s);
 
+/* ---- beam-search answer decoding (entry points added, no signature changed: ABI stays 9) --------------------------------------
+ * The reference ships no beam search (its _reorder_cache, visual_dialog_decoder.py:177-181, is never called), so this is the
+ * specification.  B dialog rows, K beams (1..8), V vocabulary; beam j of dialog b is decoder row b * K + j.  Per beam an fp32
+ * score s[b,j] (the sum of its tokens' log-probabilities) and a flag done[b,j]; in front of the first generated position
+ * s[b,0] = 0, s[b,j>0] = -inf, nothing done.
+ * One step:
+ *   a live beam j offers every v in [0, V) with score s[b,j] + logp_j[v],
+ *       logp_j[v] = (z[v] - max z) - log sum_v exp(z[v] - max z)     in fp32 over the beam row's raw logits z (no temperature, no
+ *                                                                    top-k / top-p);
+ *   a done beam j offers exactly one candidate, (j, pad), with its score s[b,j] unchanged;
+ *   the K best candidates of the dialog row become the new beams IN ORDER: higher score first, equal scores by smaller j, then by
+ *       smaller v; scores of -inf sort last under the same index rule;
+ *   new beam i:  parent[b,i] = j,  token = v -> ids_tm[pos * ids_stride + b*K + i]  (the TIME-MAJOR id buffer [positions,
+ *       ids_stride >= B*K]: the next token step's embedding reads the row as it is),  score_out[b,i] = the candidate's score,
+ *       done_out[b,i] = done_in[b,j] || v == eos.
+ * logits [B*K, ld >= V] fp32 or bf16; score_in / score_out fp32 [B, K], done_in / done_out / parent int32 [B, K]; in and out state
+ * are separate buffers (ping-pong, nothing is updated in place).  workspace: caller-owned, 8 * B * K * K bytes ([B, K, K] pairs of
+ * (fp32 score, int32 token): the K best continuations of every live beam, which phase A -- one workgroup per beam row, the row in
+ * registers -- leaves for phase B -- one wave per dialog row, which merges them under the rule).  Two launches, no allocation, no
+ * synchronisation.  Refused before any launch: K outside 1..8 (GSTVD_E_SHAPE), V > 31744 (GSTVD_E_UNSUPPORTED), a null pointer. */
+typedef struct {
+  const void* logits; int64_t ld; int32_t dtype; int32_t B; int32_t K; int32_t V;
+  const float* score_in; const int32_t* done_in;
+  float* score_out; int32_t* done_out; int32_t* parent;
+  int64_t* ids_tm; int64_t ids_stride; int32_t positions; int32_t pos;
+  void* workspace;
+  int32_t eos; int32_t pad;
+} gstvd_beam_step_t;
+int gstvd_beam_step(const gstvd_beam_step_t* a, gstvd_stream_t s);
+
+/* The self-attention caches of the surviving beams, all decoder layers in ONE launch: for every layer l < n_layers
+ *   dst[l][b*K + i, 0..t, H..3H) = src[l][b*K + parent[b,i], 0..t, H..3H)
+ * over the fused Q|K|V caches [B*K, Umax, ld >= 3H] (row_stride >= Umax * ld elements between decoder rows): only the K and V
+ * columns move, only positions <= t; the Q columns and later positions of dst are left alone, src is only read.  src[l] != dst[l]:
+ * the caller keeps two cache sets that swap roles every step, so a permutation never reads a row it has already overwritten.
+ * 16-byte copies: H * sizeof(T), ld * sizeof(T), row_stride * sizeof(T) and every pointer multiples of 16 (GSTVD_E_ALIGN). */
+typedef struct {
+  const void* src[16]; void* dst[16];
+  const int32_t* parent;
+  int64_t row_stride; int64_t ld;
+  int32_t n_layers; int32_t B; int32_t K; int32_t H; int32_t Umax; int32_t t; int32_t dtype; int32_t reserved_;
+} gstvd_beam_reorder_t;
+int gstvd_beam_reorder(const gstvd_beam_reorder_t* a, gstvd_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
