@@ -46,25 +46,9 @@ template <typename T, int D> struct Img {
   static DEVFN int f32_off(int row, int col) { return row * RB + col * 4; }
 };
 
-// copy rows [r0, r0+64) x D of a [rows, ld] matrix into LDS image(s); rows >= rmax are zero filled
-template <typename T, int D>
-DEVFN void stage64(const T* g, int64_t ld, int r0, int rmax, char* img_row, char* img_tr, int tid) {
-  constexpr int VE = 16 / sizeof(T), VPR = D / VE, TOT = 64 * VPR;
-  for (int v = tid; v < TOT; v += 256) {
-    const int row = v / VPR, cv = v % VPR;
-    u32x4 z = {0u, 0u, 0u, 0u};
-    if (r0 + row < rmax) z = *(const u32x4*)(g + (int64_t)(r0 + row) * ld + cv * VE);
-    if (Img<T, D>::BF) {
-      if (img_row) *(u32x4*)(img_row + Img<T, D>::row_off(row, cv)) = z;
-      if (img_tr) *(u32x4*)(img_tr + Img<T, D>::tr_off(row, cv * 8)) = z;
-    } else {
-      *(u32x4*)(img_row + row * Img<T, D>::RB + cv * 16) = z;
-    }
-  }
-}
-
-// Two-phase form of stage64 for software pipelining: `load` issues the chunk's global loads into registers (they stay in
-// flight while the previous chunk is being consumed), `store` writes them into the LDS image(s) after the barrier.
+// Copy of rows [r0, r0+64) x D of a [rows, ld] matrix into LDS image(s), rows >= rmax zero filled, in two phases for software
+// pipelining: `load` issues the chunk's global loads into registers (they stay in flight while the previous chunk is being
+// consumed), `store` writes them into the LDS image(s) after the barrier.
 template <typename T, int D> struct Stage64 {
   static constexpr int VE = 16 / sizeof(T), VPR = D / VE, TOT = 64 * VPR, NV = TOT / 256;
   static_assert(TOT % 256 == 0, "chunk must split evenly over 256 threads");
@@ -185,7 +169,7 @@ DEVFN void second_product(f32x4 (&acc)[D / 16], const char* img_tr, int xb, cons
   }
 }
 
-DEVFN int round4(int x) { return (x + 3) & ~3; }
+__host__ DEVFN int round4(int x) { return (x + 3) & ~3; }
 
 // The second product of TWO 16-row tiles (rows xb.. and xb+16..).  bf16: ONE 16x16x32 MFMA per 16 output columns -- k-slot 8g+j
 // of the instruction is row 4g+j of the first tile (j < 4) or of the second (j >= 4), i.e. the A operand is the concatenation
@@ -225,6 +209,76 @@ template <bool E32> DEVFN f32x4 drop_factor4e(const DropKey& k, uint64_t e) {   
   f[3] = (r1 >> 16) >= k.thr ? k.scale : 0.f;
   return f;
 }
+// The dK/dV lane layout (one key per lane, four consecutive queries): draw index set-up and the factors of one tile.
+// e2lane: pair index (element index >> 1) of (query 4g of the chunk at c0 = 0, this lane's key); Lkp = round4(Lk) is even, so a
+// step of one query is a step of `half` = Lkp / 2 pairs.  Not clamped for keys past the end: the partner lane may be a valid key
+// and takes our draws.
+struct PairDraw {
+  uint64_t half, e2lane;
+  bool odd;
+  DEVFN PairDraw(int64_t stat0, int Lk, int g, int key)
+      : half((uint64_t)(round4(Lk) >> 1)), e2lane(((uint64_t)stat0 + (uint64_t)(4 * g)) * half + (uint64_t)(key >> 1)), odd((key & 1) != 0) {}
+  DEVFN uint64_t chunk(int c0) const { return e2lane + (uint64_t)c0 * half; }   // the same for the chunk at query c0
+};
+// The two keys of a pair sit in neighbouring lanes (li, li ^ 1): the even lane draws for rows r = 0, 1 of the tile q0 rows
+// below pair index e2 (the chunk's base, formed once per chunk), the odd lane for rows 2, 3, and one quad permute hands each its
+// partner's draws.  f stays as it is without dropout.
+template <bool E32> DEVFN void pair_drop_factors(const DropKey& dk, uint64_t e2, int q0, uint64_t half, bool odd, float (&f)[4]) {
+  if (!dk.on) return;
+  const int r0 = odd ? 2 : 0;
+  const uint32_t mine0 = draw_pair<E32>(dk, e2 + (uint64_t)(q0 + r0) * half);
+  const uint32_t mine1 = draw_pair<E32>(dk, e2 + (uint64_t)(q0 + r0 + 1) * half);
+  const uint32_t other0 = (uint32_t)__builtin_amdgcn_mov_dpp((int)mine0, 0xB1, 0xf, 0xf, true);   // quad_perm [1,0,3,2]
+  const uint32_t other1 = (uint32_t)__builtin_amdgcn_mov_dpp((int)mine1, 0xB1, 0xf, 0xf, true);
+  const uint32_t d0 = odd ? other0 : mine0, d1 = odd ? other1 : mine1, d2 = odd ? mine0 : other0, d3 = odd ? mine1 : other1;
+  const uint32_t sh = odd ? 16u : 0u;
+  f[0] = ((d0 >> sh) & 0xffffu) >= dk.thr ? dk.scale : 0.f;
+  f[1] = ((d1 >> sh) & 0xffffu) >= dk.thr ? dk.scale : 0.f;
+  f[2] = ((d2 >> sh) & 0xffffu) >= dk.thr ? dk.scale : 0.f;
+  f[3] = ((d3 >> sh) & 0xffffu) >= dk.thr ? dk.scale : 0.f;
+}
+
+// additive mask term of key `key` of batch row bk: 0 (valid), mask_neg (masked out), -inf (past the end => p = 0)
+DEVFN float key_add(const gstvd_attn_t& a, int bk, int key) {
+  if (key >= a.Lk) return -INFINITY;
+  return (a.key_mask == nullptr || a.key_mask[(int64_t)bk * a.Lk + key] != 0.f) ? 0.f : a.mask_neg;
+}
+// causal x padding: a key after the query gets mask_neg only when its term is still 0 -- the term is added once
+DEVFN float causal_add(const gstvd_attn_t& a, float add, int key, int q) { return (key > q && add == 0.f) ? a.mask_neg : add; }
+
+// Row 0 of Q / K / V (and, on demand, row q of O / dO) of (batch row b, head h).  STRIDED (forward, decode): kv_group query rows share the keys of batch
+// row bk, and q_bstride / kv_bstride sequence positions separate two batch rows; the backward takes neither (attn_check).
+template <typename T, int D, bool STRIDED> struct HeadBase {
+  const T *Q, *K, *V;
+  int bk, h;
+  int64_t qrow0;                                              // first query row of batch row b
+  DEVFN HeadBase(const gstvd_attn_t& a, int b, int h_) : h(h_) {
+    bk = STRIDED && a.kv_group > 1 ? b / a.kv_group : b;
+    const int64_t kbs = STRIDED && a.kv_bstride > 0 ? a.kv_bstride : a.Lk;
+    qrow0 = (int64_t)b * (STRIDED && a.q_bstride > 0 ? a.q_bstride : a.Lq);
+    Q = (const T*)a.Q + qrow0 * a.ldq + h * D;
+    K = (const T*)a.K + (int64_t)bk * kbs * a.ldk + h * D;
+    V = (const T*)a.V + (int64_t)bk * kbs * a.ldv + h * D;
+  }
+  DEVFN T* O(const gstvd_attn_t& a, int64_t q) const { return (T*)a.O + (qrow0 + q) * a.ldo + h * D; }             // row q of O
+  DEVFN const T* dO(const gstvd_attn_t& a, int64_t q) const { return (const T*)a.dO + (qrow0 + q) * a.lddo + h * D; }
+};
+
+// K + V + additive-mask registers of one 64-key chunk (forward, dQ): `load` issues the global loads, `store` fills the LDS images
+template <typename T, int D> struct KVStage {
+  Stage64<T, D> k, v;
+  float m;
+  DEVFN void load(const gstvd_attn_t& a, const T* Kb, const T* Vb, int bk, int c0, int tid) {
+    k.load(Kb, a.ldk, c0, a.Lk, tid);
+    v.load(Vb, a.ldv, c0, a.Lk, tid);
+    if (tid < 64) m = key_add(a, bk, c0 + tid);
+  }
+  DEVFN void store(char* k_row, char* k_tr, char* v_row, char* v_tr, float* smask, int tid) const {
+    k.store(k_row, k_tr, tid);
+    v.store(v_row, v_tr, tid);
+    if (tid < 64) smask[tid] = m;
+  }
+};
 
 // The three bodies below work on a whole 64-row chunk at a time: the first products of its (up to four) 16x16 tiles are issued
 // together, the element-wise part runs on 16 values per lane, the softmax statistics are updated ONCE per chunk, and the second
@@ -245,13 +299,9 @@ DEVFN void attn_fwd_body(const gstvd_attn_t& a, char* smem) {
   const int b = blockIdx.z, h = blockIdx.y;
   const int q = blockIdx.x * 64 + wave * 16 + li;
   const bool qv = q < a.Lq;
-  const int bk = a.kv_group > 1 ? b / a.kv_group : b;       // batch row of the (possibly shared) keys / values
-  const int64_t qbs = a.q_bstride > 0 ? a.q_bstride : a.Lq, kbs = a.kv_bstride > 0 ? a.kv_bstride : a.Lk;
-  const T* Qb = (const T*)a.Q + (int64_t)b * qbs * a.ldq + h * D;
-  const T* Kb = (const T*)a.K + (int64_t)bk * kbs * a.ldk + h * D;
-  const T* Vb = (const T*)a.V + (int64_t)bk * kbs * a.ldv + h * D;
+  const HeadBase<T, D, true> hp(a, b, h);
   RowFrag<T, D> qf;
-  qf.load(Qb + (int64_t)q * a.ldq, qv, g);
+  qf.load(hp.Q + (int64_t)q * a.ldq, qv, g);
   const DropKey dk = make_drop(a.dropout_p, a.site, a.rng);
   const int Lkp = round4(a.Lk);
   const uint64_t ebase = ((uint64_t)(b * a.nh + h) * a.Lq + (uint64_t)(qv ? q : 0)) * (uint64_t)Lkp + (uint64_t)(4 * g);
@@ -265,28 +315,16 @@ DEVFN void attn_fwd_body(const gstvd_attn_t& a, char* smem) {
 #pragma unroll
   for (int i = 0; i < D / 16; ++i) accO[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
-  // The K / V / mask loads of a chunk are issued PF chunks ahead of its use (PF register stages).  PF = 2 was measured in
+  // The K / V / mask loads of a chunk are issued one chunk ahead of its use (one register stage).  Two stages were measured in
   // round 3 (d = 64, 154 registers): 18.1 us against 17.1 us for the text shape, 10.6 against 10.5 us for the cross-attention
   // shape -- the kernel is not waiting for these loads; one stage it stays.
-  constexpr int PF = 1;
-  struct Stage { Stage64<T, D> k, v; float m; };
-  Stage st[PF];
-  auto prefetch = [&](Stage& sg, int c0) {
-    sg.k.load(Kb, a.ldk, c0, a.Lk, tid);
-    sg.v.load(Vb, a.ldv, c0, a.Lk, tid);
-    if (tid < 64) {      // additive mask term of the key: 0 (valid), mask_neg (masked out), -inf (past the end)
-      const int key = c0 + tid;
-      sg.m = -INFINITY;
-      if (key < a.Lk) sg.m = (a.key_mask == nullptr || a.key_mask[(int64_t)bk * a.Lk + key] != 0.f) ? 0.f : a.mask_neg;
-    }
-  };
-  auto chunk = [&](Stage& sg, const int c0) {
+  KVStage<T, D> st;
+  st.load(a, hp.K, hp.V, hp.bk, 0, tid);
+  for (int c0 = 0; c0 < a.Lk; c0 += 64) {
     __syncthreads();
-    sg.k.store(sK, nullptr, tid);
-    sg.v.store(Img<T, D>::BF ? nullptr : sV, Img<T, D>::BF ? sV : nullptr, tid);
-    if (tid < 64) smask[tid] = sg.m;
+    st.store(sK, nullptr, Img<T, D>::BF ? nullptr : sV, Img<T, D>::BF ? sV : nullptr, smask, tid);
     __syncthreads();
-    if (c0 + 64 * PF < a.Lk) prefetch(sg, c0 + 64 * PF);
+    if (c0 + 64 < a.Lk) st.load(a, hp.K, hp.V, hp.bk, c0 + 64, tid);
     const int ntile = (a.Lk - c0 + 15) / 16 < 4 ? (a.Lk - c0 + 15) / 16 : 4;
     // TF tiles per softmax update: the whole chunk for d <= 64, half of it for d = 128 (register budget of two waves per SIMD).
     // FULL: all TF tiles present and no causal mask -- the body then has no control flow at all (the generic form tests
@@ -305,8 +343,7 @@ DEVFN void attn_fwd_body(const gstvd_attn_t& a, char* smem) {
           f32x4 madd = *(const f32x4*)(smask + k0 + t * 16 + 4 * g);
           if (!FULL && a.causal) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r)
-              if (c0 + k0 + t * 16 + 4 * g + r > q && madd[r] == 0.f) madd[r] = a.mask_neg;   // causal x padding: the term is added once
+            for (int r = 0; r < 4; ++r) madd[r] = causal_add(a, madd[r], c0 + k0 + t * 16 + 4 * g + r, q);
           }
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
@@ -357,19 +394,11 @@ DEVFN void attn_fwd_body(const gstvd_attn_t& a, char* smem) {
       if (TF == 4 && nt >= TF && !a.causal) tiles(std::true_type{}, TF, k0);
       else tiles(std::false_type{}, nt, k0);
     }
-  };
-#pragma unroll
-  for (int j = 0; j < PF; ++j)
-    if (64 * j < a.Lk) prefetch(st[j], 64 * j);
-  for (int c0 = 0; c0 < a.Lk; c0 += 64 * PF) {
-#pragma unroll
-    for (int j = 0; j < PF; ++j)
-      if (c0 + 64 * j < a.Lk) chunk(st[j], c0 + 64 * j);
   }
   const float l_tot = rows_sum(l_part);
   const float inv = 1.f / l_tot;
   if (qv) {
-    T* Op = (T*)a.O + ((int64_t)b * qbs + q) * a.ldo + h * D;
+    T* Op = hp.O(a, q);
 #pragma unroll
     for (int i = 0; i < D / 16; ++i) st4(Op + i * 16 + 4 * g, accO[i] * inv);
     if (g == 0 && a.LSE) a.LSE[((int64_t)b * a.nh + h) * a.Lq + q] = m_run + __logf(l_tot);
@@ -395,12 +424,9 @@ __global__ __launch_bounds__(DEC_NT) void attn_decode_kernel(gstvd_attn_t a) {
   __shared__ float sacc[DEC_NT];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int h = blockIdx.x, b = blockIdx.y;
-  const int bk = a.kv_group > 1 ? b / a.kv_group : b;
-  const int64_t qbs = a.q_bstride > 0 ? a.q_bstride : a.Lq, kbs = a.kv_bstride > 0 ? a.kv_bstride : a.Lk;
-  const T* Qr = (const T*)a.Q + (int64_t)b * qbs * a.ldq + h * D;
-  const T* Kb = (const T*)a.K + (int64_t)bk * kbs * a.ldk + h * D;
-  const T* Vb = (const T*)a.V + (int64_t)bk * kbs * a.ldv + h * D;
-  if (tid < D) sq[tid] = to_f(Qr[tid]);
+  const HeadBase<T, D, true> hp(a, b, h);
+  const T *Kb = hp.K, *Vb = hp.V;
+  if (tid < D) sq[tid] = to_f(hp.Q[tid]);
   __syncthreads();
   // scores: PPK lanes share one key (a 16-byte piece of its K row each), a wave scores 64 / PPK keys per round, the four waves
   // interleave rounds; every lane has one load per round in flight and the rounds are independent (unrolled)
@@ -429,8 +455,7 @@ __global__ __launch_bounds__(DEC_NT) void attn_decode_kernel(gstvd_attn_t a) {
 #pragma unroll
       for (int o = 1; o < PPK; o <<= 1) s += __shfl_xor(s, o, 64);
       if (key < a.Lk) {
-        const float madd = (a.key_mask == nullptr || a.key_mask[(int64_t)bk * a.Lk + key] != 0.f) ? 0.f : a.mask_neg;
-        s = s * a.scale + madd;
+        s = s * a.scale + key_add(a, hp.bk, key);
         if (piece == 0) sp[key] = s;
         mx = fmaxf(mx, s);
       }
@@ -479,13 +504,13 @@ __global__ __launch_bounds__(DEC_NT) void attn_decode_kernel(gstvd_attn_t a) {
     float o = 0.f;
 #pragma unroll
     for (int g2 = 0; g2 < NG; ++g2) o += sacc[g2 * D + tid];
-    T* Op = (T*)a.O + (int64_t)b * qbs * a.ldo + h * D;
-    Op[tid] = from_f<T>(o / sum);
+    hp.O(a, 0)[tid] = from_f<T>(o / sum);
     if (tid == 0 && a.LSE) a.LSE[((int64_t)b * a.nh + h) * a.Lq] = mx + __logf(sum);
   }
 }
 
-DEVFN bool attn_small_index_space(const gstvd_attn_t& a) {
+// fewer than 2^33 score elements: the dropout draws of the launch take 32-bit index arithmetic (draw_pair); also part of the route
+__host__ DEVFN bool attn_small_index_space(const gstvd_attn_t& a) {
   return (uint64_t)a.B * (uint64_t)a.nh * (uint64_t)a.Lq * (uint64_t)round4(a.Lk) < (1ull << 33);
 }
 
@@ -514,15 +539,11 @@ DEVFN void attn_bwd_dq_body(const gstvd_attn_t& a, const int bx, const int h, co
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, li = lane & 15;
   const int q = bx * 64 + wave * 16 + li;
   const bool qv = q < a.Lq;
-  const T* Qb = (const T*)a.Q + (int64_t)b * a.Lq * a.ldq + h * D;
-  const T* Kb = (const T*)a.K + (int64_t)b * a.Lk * a.ldk + h * D;
-  const T* Vb = (const T*)a.V + (int64_t)b * a.Lk * a.ldv + h * D;
-  const T* dOb = (const T*)a.dO + (int64_t)b * a.Lq * a.lddo + h * D;
-  const T* Ob = (const T*)a.O + (int64_t)b * a.Lq * a.ldo + h * D;
+  const HeadBase<T, D, false> hp(a, b, h);
   RowFrag<T, D> qf, dof;
-  qf.load(Qb + (int64_t)q * a.ldq, qv, g);
-  dof.load(dOb + (int64_t)q * a.lddo, qv, g);
-  float delta = rows_sum(dof.dot(Ob + (int64_t)q * a.ldo, qv, g));
+  qf.load(hp.Q + (int64_t)q * a.ldq, qv, g);
+  dof.load(hp.dO(a, q), qv, g);
+  float delta = rows_sum(dof.dot(hp.O(a, q), qv, g));
   const int64_t stat = ((int64_t)b * a.nh + h) * a.Lq + q;
   if (qv && g == 0) a.delta[stat] = delta;
   const float lse = qv ? a.LSE[stat] : INFINITY;              // +inf => p = 0 for padded query rows
@@ -534,25 +555,13 @@ DEVFN void attn_bwd_dq_body(const gstvd_attn_t& a, const int bx, const int h, co
 #pragma unroll
   for (int i = 0; i < D / 16; ++i) acc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
-  Stage64<T, D> pk, pv;
-  float pm = -INFINITY;
-  auto prefetch = [&](int c0) {
-    pk.load(Kb, a.ldk, c0, a.Lk, tid);
-    pv.load(Vb, a.ldv, c0, a.Lk, tid);
-    if (tid < 64) {      // additive mask term of the key: 0 (valid), mask_neg (masked out), -inf (past the end)
-      const int key = c0 + tid;
-      pm = -INFINITY;
-      if (key < a.Lk) pm = (a.key_mask == nullptr || a.key_mask[(int64_t)b * a.Lk + key] != 0.f) ? 0.f : a.mask_neg;
-    }
-  };
-  prefetch(0);
+  KVStage<T, D> st;
+  st.load(a, hp.K, hp.V, hp.bk, 0, tid);
   for (int c0 = 0; c0 < a.Lk; c0 += 64) {
     __syncthreads();
-    pk.store(sKr, BF ? sKt : nullptr, tid);
-    pv.store(sVr, nullptr, tid);
-    if (tid < 64) smask[tid] = pm;
+    st.store(sKr, BF ? sKt : nullptr, sVr, nullptr, smask, tid);
     __syncthreads();
-    if (c0 + 64 < a.Lk) prefetch(c0 + 64);
+    if (c0 + 64 < a.Lk) st.load(a, hp.K, hp.V, hp.bk, c0 + 64, tid);
     const int ntile = (a.Lk - c0 + 15) / 16 < 4 ? (a.Lk - c0 + 15) / 16 : 4;
     // TP tiles at a time.  d <= 64: two (32 keys) -- enough to pair them on the 16x16x32 second product and to halve the
     // per-tile bookkeeping, few enough live values for three waves per SIMD (a whole chunk at once needed 296 registers in the
@@ -578,8 +587,7 @@ DEVFN void attn_bwd_dq_body(const gstvd_attn_t& a, const int bx, const int h, co
           f32x4 madd = *(const f32x4*)(smask + k0 + 4 * g);
           if (!FULL && a.causal) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r)
-              if (c0 + k0 + 4 * g + r > q && madd[r] == 0.f) madd[r] = a.mask_neg;
+            for (int r = 0; r < 4; ++r) madd[r] = causal_add(a, madd[r], c0 + k0 + 4 * g + r, q);
           }
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
@@ -609,6 +617,19 @@ DEVFN void attn_bwd_dq_body(const gstvd_attn_t& a, const int bx, const int h, co
 // =====================================================================================================
 // backward, part 2: dK and dV; one wave owns 16 keys, queries stream through LDS
 // =====================================================================================================
+// dK / dV rows of this lane's key from the accumulators (dK^T, dV^T: rows d = 16 i + 4g + r, column = key li)
+template <typename T, int D>
+DEVFN void store_dkv(const gstvd_attn_t& a, int b, int h, int key, int g, const f32x4 (&accK)[D / 16], const f32x4 (&accV)[D / 16]) {
+  if (key >= a.Lk) return;
+  T* dKp = (T*)a.dK + ((int64_t)b * a.Lk + key) * a.lddk + h * D;
+  T* dVp = (T*)a.dV + ((int64_t)b * a.Lk + key) * a.lddv + h * D;
+#pragma unroll
+  for (int i = 0; i < D / 16; ++i) {
+    st4(dKp + i * 16 + 4 * g, accK[i]);
+    st4(dVp + i * 16 + 4 * g, accV[i]);
+  }
+}
+
 template <typename T, int D, bool E32>
 DEVFN void attn_bwd_dkv_body(const gstvd_attn_t& a, const int bx, const int h, const int b, char* smem) {
   constexpr bool BF = Img<T, D>::BF;
@@ -623,25 +644,15 @@ DEVFN void attn_bwd_dkv_body(const gstvd_attn_t& a, const int bx, const int h, c
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, li = lane & 15;
   const int key = bx * 64 + wave * 16 + li;
   const bool kv = key < a.Lk;
-  const T* Ob = (const T*)a.O + (int64_t)b * a.Lq * a.ldo + h * D;
-  const T* Qb = (const T*)a.Q + (int64_t)b * a.Lq * a.ldq + h * D;
-  const T* Kb = (const T*)a.K + (int64_t)b * a.Lk * a.ldk + h * D;
-  const T* Vb = (const T*)a.V + (int64_t)b * a.Lk * a.ldv + h * D;
-  const T* dOb = (const T*)a.dO + (int64_t)b * a.Lq * a.lddo + h * D;
+  const HeadBase<T, D, false> hp(a, b, h);
+  const T *Ob = hp.O(a, 0), *Qb = hp.Q, *dOb = hp.dO(a, 0);
   RowFrag<T, D> kf, vf;
-  kf.load(Kb + (int64_t)key * a.ldk, kv, g);
-  vf.load(Vb + (int64_t)key * a.ldv, kv, g);
-  const bool kmasked = kv && a.key_mask != nullptr && a.key_mask[(int64_t)b * a.Lk + key] == 0.f;
-  const float kadd = kv ? (kmasked ? a.mask_neg : 0.f) : -INFINITY;      // additive term of this lane's key (-inf: past the end => p = 0)
+  kf.load(hp.K + (int64_t)key * a.ldk, kv, g);
+  vf.load(hp.V + (int64_t)key * a.ldv, kv, g);
+  const float kadd = key_add(a, b, key);                      // additive term of this lane's key
   const DropKey dk = make_drop(a.dropout_p, a.site, a.rng);
-  const int Lkp = round4(a.Lk);
   const int64_t stat0 = ((int64_t)b * a.nh + h) * a.Lq;
-  // pair index (element index >> 1) of (query 4g of the chunk at c0 = 0, this lane's key); Lkp is even, so a step of one query
-  // is a step of Lkp / 2 pairs.  The two keys of a pair sit in neighbouring lanes (li, li ^ 1): the even lane draws for rows
-  // r = 0, 1 of a tile, the odd lane for rows 2, 3, and one quad permute hands each its partner's draws.
-  const uint64_t half = (uint64_t)(Lkp >> 1);
-  const uint64_t e2lane = ((uint64_t)stat0 + (uint64_t)(4 * g)) * half + (uint64_t)(key >> 1);        // not clamped for keys past the end: the partner lane may be a valid key and takes our draws
-  const bool odd = (key & 1) != 0;
+  const PairDraw pw(stat0, a.Lk, g, key);
 
   f32x4 accK[D / 16], accV[D / 16];
 #pragma unroll
@@ -650,6 +661,8 @@ DEVFN void attn_bwd_dkv_body(const gstvd_attn_t& a, const int bx, const int h, c
   // delta[q] = rowsum(dO * O) is recomputed here for every query chunk (four threads per query row, a quarter of the head
   // dimension each) instead of being read from the dQ half: the two halves of the backward then share no data and run as ONE
   // launch, side by side (they used to be two dependent launches).
+  // (The one-pass kernel's row sum adds in another order -- two 8-wide halves per thread, not ld4 groups of four -- so the two
+  // are not one helper: either order in the other kernel would change the bits of dQ / dK.)
   Stage64<T, D> pq, po;
   float plse = INFINITY, pdel = 0.f;
   auto prefetch = [&](int c0) {
@@ -684,7 +697,7 @@ DEVFN void attn_bwd_dkv_body(const gstvd_attn_t& a, const int bx, const int h, c
     __syncthreads();
     if (c0 + 64 < a.Lq) prefetch(c0 + 64);
     const int ntile = (a.Lq - c0 + 15) / 16 < 4 ? (a.Lq - c0 + 15) / 16 : 4;
-    const uint64_t e2chunk = e2lane + (uint64_t)c0 * half;
+    const uint64_t e2chunk = pw.chunk(c0);
     auto tiles = [&](auto full_tag, const int pr, const int nt) {
       constexpr bool FULL = decltype(full_tag)::value;
       f32x4 s[TP], dp[TP];
@@ -703,23 +716,11 @@ DEVFN void attn_bwd_dkv_body(const gstvd_attn_t& a, const int bx, const int h, c
           const f32x4 lse4 = *(const f32x4*)(sLse + q0 + 4 * g);
           const f32x4 del4 = *(const f32x4*)(sDel + q0 + 4 * g);
           float f[4] = {1.f, 1.f, 1.f, 1.f};
-          if (dk.on) {
-            const int r0 = odd ? 2 : 0;
-            const uint32_t mine0 = draw_pair<E32>(dk, e2chunk + (uint64_t)(q0 + r0) * half);
-            const uint32_t mine1 = draw_pair<E32>(dk, e2chunk + (uint64_t)(q0 + r0 + 1) * half);
-            const uint32_t other0 = (uint32_t)__builtin_amdgcn_mov_dpp((int)mine0, 0xB1, 0xf, 0xf, true);   // quad_perm [1,0,3,2]
-            const uint32_t other1 = (uint32_t)__builtin_amdgcn_mov_dpp((int)mine1, 0xB1, 0xf, 0xf, true);
-            const uint32_t d0 = odd ? other0 : mine0, d1 = odd ? other1 : mine1, d2 = odd ? mine0 : other0, d3 = odd ? mine1 : other1;
-            const uint32_t sh = odd ? 16u : 0u;
-            f[0] = ((d0 >> sh) & 0xffffu) >= dk.thr ? dk.scale : 0.f;
-            f[1] = ((d1 >> sh) & 0xffffu) >= dk.thr ? dk.scale : 0.f;
-            f[2] = ((d2 >> sh) & 0xffffu) >= dk.thr ? dk.scale : 0.f;
-            f[3] = ((d3 >> sh) & 0xffffu) >= dk.thr ? dk.scale : 0.f;
-          }
+          pair_drop_factors<E32>(dk, e2chunk, q0, pw.half, pw.odd, f);
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             float add = kadd;
-            if (!FULL && a.causal && key > c0 + q0 + 4 * g + r && add == 0.f) add = a.mask_neg;
+            if (!FULL && a.causal) add = causal_add(a, add, key, c0 + q0 + 4 * g + r);
             const float p = __expf(s[tt][r] * a.scale + add - lse4[r]);
             pd[tt][r] = p * f[r];
             ds[tt][r] = p * (dp[tt][r] * f[r] - del4[r]) * a.scale;
@@ -742,15 +743,7 @@ DEVFN void attn_bwd_dkv_body(const gstvd_attn_t& a, const int bx, const int h, c
       else tiles(std::false_type{}, pr, nt);
     }
   }
-  if (kv) {
-    T* dKp = (T*)a.dK + ((int64_t)b * a.Lk + key) * a.lddk + h * D;
-    T* dVp = (T*)a.dV + ((int64_t)b * a.Lk + key) * a.lddv + h * D;
-#pragma unroll
-    for (int i = 0; i < D / 16; ++i) {
-      st4(dKp + i * 16 + 4 * g, accK[i]);
-      st4(dVp + i * 16 + 4 * g, accV[i]);
-    }
-  }
+  store_dkv<T, D>(a, b, h, key, g, accK, accV);
 }
 
 // =====================================================================================================
@@ -787,22 +780,15 @@ __global__ __launch_bounds__(1024) void attn_bwd_onepass_kernel(gstvd_attn_t a) 
   const int h = blockIdx.x, b = blockIdx.y;
   const int key = wave * 16 + li;
   const bool kv = key < a.Lk;
-  const T* Ob = (const T*)a.O + (int64_t)b * a.Lq * a.ldo + h * D;
-  const T* Qb = (const T*)a.Q + (int64_t)b * a.Lq * a.ldq + h * D;
-  const T* Kb = (const T*)a.K + (int64_t)b * a.Lk * a.ldk + h * D;
-  const T* Vb = (const T*)a.V + (int64_t)b * a.Lk * a.ldv + h * D;
-  const T* dOb = (const T*)a.dO + (int64_t)b * a.Lq * a.lddo + h * D;
+  const HeadBase<T, D, false> hp(a, b, h);
+  const T *Ob = hp.O(a, 0), *Qb = hp.Q, *Kb = hp.K, *dOb = hp.dO(a, 0);
   RowFrag<T, D> kf, vf;
   kf.load(Kb + (int64_t)key * a.ldk, kv, g);
-  vf.load(Vb + (int64_t)key * a.ldv, kv, g);
-  const bool kmasked = kv && a.key_mask != nullptr && a.key_mask[(int64_t)b * a.Lk + key] == 0.f;
-  const float kadd = kv ? (kmasked ? a.mask_neg : 0.f) : -INFINITY;
+  vf.load(hp.V + (int64_t)key * a.ldv, kv, g);
+  const float kadd = key_add(a, b, key);
   const DropKey dk = make_drop(a.dropout_p, a.site, a.rng);
-  const int Lkp = round4(a.Lk);
   const int64_t stat0 = ((int64_t)b * a.nh + h) * a.Lq;
-  const uint64_t half = (uint64_t)(Lkp >> 1);
-  const uint64_t e2lane = ((uint64_t)stat0 + (uint64_t)(4 * g)) * half + (uint64_t)(key >> 1);
-  const bool odd = (key & 1) != 0;
+  const PairDraw pw(stat0, a.Lk, g, key);
   // the K image for the dQ product: all (up to 256) keys, rows past the end zero
 #pragma unroll
   for (int v = tid; v < 256 * 8; v += 1024) {
@@ -817,7 +803,8 @@ __global__ __launch_bounds__(1024) void attn_bwd_onepass_kernel(gstvd_attn_t a) 
   for (int i = 0; i < D / 16; ++i) accK[i] = accV[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
   // delta = rowsum(dO * O) and LSE of ALL queries once, in the prologue (four threads per query row; the loads sit beside the K / V
-  // loads above): the chunk loop below then carries no global-memory result that arithmetic has to wait for
+  // loads above): the chunk loop below then carries no global-memory result that arithmetic has to wait for.  (Two 8-wide halves
+  // per thread: another order of additions than attn_bwd_dkv_body's row sum, see there.)
   for (int q0 = 0; q0 < a.Lq; q0 += 256) {
     const int qq = q0 + (tid >> 2), part = tid & 3;
     float dsum = 0.f;
@@ -872,7 +859,7 @@ __global__ __launch_bounds__(1024) void attn_bwd_onepass_kernel(gstvd_attn_t a) 
     if (BITS && tid < 256) sBits[tid] = pbits;
     __syncthreads();
     if (c0 + 64 < a.Lq) prefetch(c0 + 64);
-    const uint64_t e2chunk = e2lane + (uint64_t)c0 * half;
+    const uint64_t e2chunk = pw.chunk(c0);
 #pragma unroll 1
     for (int pr = 0; pr < 4 / TP; ++pr) {
       f32x4 s[TP], dp[TP];
@@ -893,18 +880,8 @@ __global__ __launch_bounds__(1024) void attn_bwd_onepass_kernel(gstvd_attn_t a) 
           const unsigned m4 = (unsigned)(w >> (((li >> 2) << 4) + 4 * g)) & 0xfu;
 #pragma unroll
           for (int r = 0; r < 4; ++r) f[r] = ((m4 >> r) & 1u) ? dk.scale : 0.f;
-        } else if (!BITS && dk.on) {      // the two keys of a draw's pair sit in neighbouring lanes: each lane draws for two rows, one quad permute swaps
-          const int r0 = odd ? 2 : 0;
-          const uint32_t mine0 = draw_pair<E32>(dk, e2chunk + (uint64_t)(q0 + r0) * half);
-          const uint32_t mine1 = draw_pair<E32>(dk, e2chunk + (uint64_t)(q0 + r0 + 1) * half);
-          const uint32_t other0 = (uint32_t)__builtin_amdgcn_mov_dpp((int)mine0, 0xB1, 0xf, 0xf, true);
-          const uint32_t other1 = (uint32_t)__builtin_amdgcn_mov_dpp((int)mine1, 0xB1, 0xf, 0xf, true);
-          const uint32_t d0 = odd ? other0 : mine0, d1 = odd ? other1 : mine1, d2 = odd ? mine0 : other0, d3 = odd ? mine1 : other1;
-          const uint32_t sh = odd ? 16u : 0u;
-          f[0] = ((d0 >> sh) & 0xffffu) >= dk.thr ? dk.scale : 0.f;
-          f[1] = ((d1 >> sh) & 0xffffu) >= dk.thr ? dk.scale : 0.f;
-          f[2] = ((d2 >> sh) & 0xffffu) >= dk.thr ? dk.scale : 0.f;
-          f[3] = ((d3 >> sh) & 0xffffu) >= dk.thr ? dk.scale : 0.f;
+        } else {
+          pair_drop_factors<E32>(dk, e2chunk, q0, pw.half, pw.odd, f);
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -946,15 +923,7 @@ __global__ __launch_bounds__(1024) void attn_bwd_onepass_kernel(gstvd_attn_t a) 
       if (q < a.Lq) st4((T*)a.dQ + ((int64_t)b * a.Lq + q) * a.lddq + h * D + dq_i * 16 + 4 * g, acc);
     }
   }
-  if (kv) {
-    T* dKp = (T*)a.dK + ((int64_t)b * a.Lk + key) * a.lddk + h * D;
-    T* dVp = (T*)a.dV + ((int64_t)b * a.Lk + key) * a.lddv + h * D;
-#pragma unroll
-    for (int i = 0; i < D / 16; ++i) {
-      st4(dKp + i * 16 + 4 * g, accK[i]);
-      st4(dVp + i * 16 + 4 * g, accV[i]);
-    }
-  }
+  store_dkv<T, D>(a, b, h, key, g, accK, accV);
 }
 
 // ---- host side ---------------------------------------------------------------------------------------
@@ -992,8 +961,11 @@ static AttnRoute attn_fwd_route(const gstvd_attn_t& a) {
   return r;
 }
 
-static bool attn_small_index_space_host(const gstvd_attn_t& a) {
-  return (uint64_t)a.B * (uint64_t)a.nh * (uint64_t)a.Lq * (uint64_t)((a.Lk + 3) & ~3) < (1ull << 33);
+// the one-pass kernel of a route kind (plan, LDS attribute and launch all ask here)
+typedef void (*OnepassKernel)(gstvd_attn_t);
+static OnepassKernel attn_onepass_kernel(int kind) {
+  return kind == ATTN_BWD_ONEPASS_BITS ? attn_bwd_onepass_kernel<true, true>
+       : kind == ATTN_BWD_ONEPASS_E32 ? attn_bwd_onepass_kernel<true, false> : attn_bwd_onepass_kernel<false, false>;
 }
 
 static AttnRoute attn_bwd_route(const gstvd_attn_t& a) {
@@ -1004,7 +976,7 @@ static AttnRoute attn_bwd_route(const gstvd_attn_t& a) {
     static const int onepass = [] { const char* e = getenv("GSTVD_ATTN_ONEPASS"); return e ? atoi(e) : 1; }();
     if (onepass && !a.causal && a.Lk > 64 && a.Lk <= 256 && a.Lq >= 64 && a.Lq <= ONEPASS_MAX_LQ) {
       const bool bits = a.drop_bits != nullptr && a.dropout_p > 0.f && a.rng != nullptr;     // forward left the keep bits of its draws
-      r.kind = bits ? ATTN_BWD_ONEPASS_BITS : attn_small_index_space_host(a) ? ATTN_BWD_ONEPASS_E32 : ATTN_BWD_ONEPASS_E64;
+      r.kind = bits ? ATTN_BWD_ONEPASS_BITS : attn_small_index_space(a) ? ATTN_BWD_ONEPASS_E32 : ATTN_BWD_ONEPASS_E64;
       r.dq_first = -1;
       return r;
     }
@@ -1070,20 +1042,13 @@ template <typename T, int D> static int attn_bwd_launch(const gstvd_attn_t& a, h
   // taking another kernel than the one gstvd_attn_kernel_name reports
   if constexpr (BF && D == 64) {
     if (r.kind != ATTN_BWD_TWOPART) {
-      if (plan) {
-        plan->fn = r.kind == ATTN_BWD_ONEPASS_BITS ? (const void*)attn_bwd_onepass_kernel<true, true>
-                 : r.kind == ATTN_BWD_ONEPASS_E32 ? (const void*)attn_bwd_onepass_kernel<true, false>
-                                                  : (const void*)attn_bwd_onepass_kernel<false, false>;
-        return 0;
-      }
+      const OnepassKernel kernel = attn_onepass_kernel(r.kind);
+      if (plan) { plan->fn = (const void*)kernel; return 0; }
       constexpr int lds1p = 12 * Img<T, D>::BYTES + 2 * ONEPASS_MAX_LQ * 4 + 256 * 8;
-      static int rc1 = attn_lds_attr(attn_bwd_onepass_kernel<true, false>, lds1p) | attn_lds_attr(attn_bwd_onepass_kernel<false, false>, lds1p) |
-                       attn_lds_attr(attn_bwd_onepass_kernel<true, true>, lds1p);
+      static int rc1 = attn_lds_attr(attn_onepass_kernel(ATTN_BWD_ONEPASS_BITS), lds1p) | attn_lds_attr(attn_onepass_kernel(ATTN_BWD_ONEPASS_E32), lds1p) |
+                       attn_lds_attr(attn_onepass_kernel(ATTN_BWD_ONEPASS_E64), lds1p);
       if (rc1) return rc1;
-      dim3 grid((unsigned)a.nh, (unsigned)a.B);
-      if (r.kind == ATTN_BWD_ONEPASS_BITS) hipLaunchKernelGGL((attn_bwd_onepass_kernel<true, true>), grid, dim3(1024), lds1p, s, a);
-      else if (r.kind == ATTN_BWD_ONEPASS_E32) hipLaunchKernelGGL((attn_bwd_onepass_kernel<true, false>), grid, dim3(1024), lds1p, s, a);
-      else hipLaunchKernelGGL((attn_bwd_onepass_kernel<false, false>), grid, dim3(1024), lds1p, s, a);
+      hipLaunchKernelGGL(kernel, dim3((unsigned)a.nh, (unsigned)a.B), dim3(1024), lds1p, s, a);
       GSTVD_LAUNCH_CHECK();
       return 0;
     }
