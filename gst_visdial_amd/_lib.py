@@ -216,8 +216,14 @@ def load():
 N_CALLS = [0]      # launching library calls made so far (each is >= 1 kernel launch): bench.py reports calls per decode token
 
 
+def status_name(rc):
+    """The name of an entry point's return value: "ok", a GSTVD_E_* name, or the hipError_t of the launch."""
+    if rc == 0:
+        return "ok"
+    return _STATUS.get(rc, "hipError_t %d" % rc if rc > 0 else "status %d" % rc)
+
+
 def check(name, rc):
     N_CALLS[0] += 1
     if rc != 0:
-        what = _STATUS.get(rc, "hipError_t %d" % rc if rc > 0 else "status %d" % rc)
-        raise GstvdError("%s failed: %s" % (name, what))
+        raise GstvdError("%s failed: %s" % (name, status_name(rc)))

@@ -229,10 +229,15 @@ extern "C" int gstvd_vl_split(const void* d_enc, int64_t B, int64_t R, int64_t T
 extern "C" int gstvd_abi_version(void) { return 9; }
 extern "C" const char* gstvd_build_arch(void) { return "gfx950"; }
 
+// The CE entries read logits (and write dlogits) in 4-element vectors: 16 bytes of fp32, 8 bytes of bf16
+static bool ce_misaligned(const void* p, int32_t dtype) { return ((uintptr_t)p & (dtype == GSTVD_BF16 ? 7 : 15)) != 0; }
+
 extern "C" int gstvd_ce_fwd(const void* logits, int64_t ldl, const int64_t* labels, int64_t M, int64_t V, int64_t ignore_index,
                             int32_t dtype, float* row_loss, float* lse, float* stats, gstvd_stream_t stream) {
   if (!logits || !labels || !row_loss || !lse || !stats) return GSTVD_E_NULL;
-  if (M <= 0 || V <= 0 || (ldl % 4)) return GSTVD_E_SHAPE;
+  if (M <= 0 || V <= 0 || (ldl % 4) || ldl < V) return GSTVD_E_SHAPE;
+  if (dtype != GSTVD_BF16 && dtype != GSTVD_F32) return GSTVD_E_DTYPE;
+  if (ce_misaligned(logits, dtype)) return GSTVD_E_ALIGN;
   hipStream_t s = (hipStream_t)stream;
   GSTVD_FOR_DTYPE(dtype, T, hipLaunchKernelGGL(ce_fwd_kernel<T>, dim3((unsigned)M), dim3(256), 0, s, (const T*)logits, ldl, labels, V, ignore_index, row_loss, lse));
   GSTVD_LAUNCH_CHECK();
@@ -245,7 +250,9 @@ extern "C" int gstvd_ce_bwd(const void* logits, int64_t ldl, const int64_t* labe
                             const float* gscale, int32_t mean, int64_t M, int64_t V, int64_t ignore_index, int32_t dtype,
                             void* dlogits, int64_t ldd, gstvd_stream_t stream) {
   if (!logits || !labels || !lse || !stats || !dlogits) return GSTVD_E_NULL;
-  if (M <= 0 || V <= 0 || (ldl % 4) || (ldd % 4) || ldd < V) return GSTVD_E_SHAPE;
+  if (M <= 0 || V <= 0 || (ldl % 4) || (ldd % 4) || ldl < V || ldd < V) return GSTVD_E_SHAPE;
+  if (dtype != GSTVD_BF16 && dtype != GSTVD_F32) return GSTVD_E_DTYPE;
+  if (ce_misaligned(logits, dtype) || ce_misaligned(dlogits, dtype)) return GSTVD_E_ALIGN;
   hipStream_t s = (hipStream_t)stream;
   GSTVD_FOR_DTYPE(dtype, T, hipLaunchKernelGGL(ce_bwd_kernel<T>, dim3((unsigned)M), dim3(256), 0, s, (const T*)logits, ldl, labels, lse, stats, gscale, mean, V, ignore_index, (T*)dlogits, ldd));
   GSTVD_LAUNCH_CHECK();
@@ -255,7 +262,9 @@ extern "C" int gstvd_ce_bwd(const void* logits, int64_t ldl, const int64_t* labe
 extern "C" int gstvd_ce_bwd_rows(const void* logits, int64_t ldl, const int64_t* labels, const float* lse, const float* g, int64_t M,
                                  int64_t V, int64_t ignore_index, int32_t dtype, void* dlogits, int64_t ldd, gstvd_stream_t stream) {
   if (!logits || !labels || !lse || !g || !dlogits) return GSTVD_E_NULL;
-  if (M <= 0 || V <= 0 || (ldl % 4) || (ldd % 4) || ldd < V) return GSTVD_E_SHAPE;
+  if (M <= 0 || V <= 0 || (ldl % 4) || (ldd % 4) || ldl < V || ldd < V) return GSTVD_E_SHAPE;
+  if (dtype != GSTVD_BF16 && dtype != GSTVD_F32) return GSTVD_E_DTYPE;
+  if (ce_misaligned(logits, dtype) || ce_misaligned(dlogits, dtype)) return GSTVD_E_ALIGN;
   hipStream_t s = (hipStream_t)stream;
   GSTVD_FOR_DTYPE(dtype, T, hipLaunchKernelGGL(ce_bwd_rows_kernel<T>, dim3((unsigned)M), dim3(256), 0, s, (const T*)logits, ldl, labels, lse, g, V, ignore_index, (T*)dlogits, ldd));
   GSTVD_LAUNCH_CHECK();

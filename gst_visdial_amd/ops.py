@@ -1160,8 +1160,10 @@ def adamw_blocks(param, grad, m, v, shadow, seg_end, hp, step, blocks, seg_skip,
                  begin=0, end=None):
     """AdamW on the listed 1024-element blocks (int32 device tensor of absolute block indices), clipped to [begin, end), leaving
     the segments flagged in `seg_skip` (uint8 device tensor, one per segment) alone: the remainder behind a weight-gradient
-    launch that updated its weights itself (GemmGroup.flush(fuse=...))."""
+    launch that updated its weights itself (GemmGroup.flush(fuse=...)).  An empty list launches nothing."""
     lib = L.load()
+    if blocks.numel() == 0:          # (an empty tensor has no address to pass; the entry point would launch nothing either)
+        return
     n = param.numel() if end is None else end
     e0 = _prof_begin()
     L.check("gstvd_adamw_blocks", lib.gstvd_adamw_blocks(_p(param), _p(grad), _p(m), _p(v), _p(shadow), n, _p(seg_end), _p(hp),

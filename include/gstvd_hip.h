@@ -246,7 +246,13 @@ int gstvd_attn_kernel_name(const gstvd_attn_t* a, int32_t bwd, char* buf, int32_
 /* ---- LM head loss: CrossEntropyLoss(ignore_index) of visual_dialog_decoder.py:70-77 ----------
  * logits [M, ldl >= V]; row_loss [M] (0 for ignored rows); stats (fp32[3], written by the call):
  * stats[0] = sum of row losses, stats[1] = number of non-ignored rows, stats[2] = mean loss
- * (= stats[0] / stats[1], NaN when every row is ignored, like torch); lse [M] saved. */
+ * (= stats[0] / stats[1], NaN when every row is ignored, like torch); lse [M] saved.
+ * A label outside [0, V) that is not ignore_index (the engines never produce one): the row's loss is 0 and its gradient row is
+ * zero, like an ignored row's, but the row COUNTS in stats[1] (only label == ignore_index is left out of the count).
+ * The three cross-entropy entries read logits and write dlogits in 4-element vectors; refused before any launch:
+ * ldl < V or ldd < V or a leading dimension that is no multiple of 4 (GSTVD_E_SHAPE), a logits / dlogits pointer that is not
+ * 16-byte (fp32) / 8-byte (bf16) aligned (GSTVD_E_ALIGN), a dtype that is neither GSTVD_F32 nor GSTVD_BF16 (GSTVD_E_DTYPE,
+ * checked before the alignment, which depends on it). */
 int gstvd_ce_fwd(const void* logits, int64_t ldl, const int64_t* labels, int64_t M, int64_t V,
                  int64_t ignore_index, int32_t dtype, float* row_loss, float* lse, float* stats,
                  gstvd_stream_t s);
