@@ -155,6 +155,7 @@ SIGNATURES = {
     "gstvd_fgsm_step": (_i32, [_vp, _vp, _f32, _vp, _i64, _vp]),
     "gstvd_answer_scores": (_i32, [_vp, _i64, _vp, _vp, _i64, _i64, _i32, _vp, _vp]),
     "gstvd_sample_topk": (_i32, [C.POINTER(SampleDesc), _vp]),
+    "gstvd_sample_topk_scored": (_i32, [C.POINTER(SampleDesc), _vp, _i64, _vp]),
     "gstvd_vl_split": (_i32, [_vp, _i64, _i64, _i64, _i64, _i32, _vp, _vp, _f32, _u32, _u32, _vp, _vp]),
     "gstvd_cast": (_i32, [_vp, _i32, _vp, _i32, _i64, _vp]),
     "gstvd_cast_ranges": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _vp]),

@@ -55,8 +55,10 @@ DEVFN float block_sum(float x, float* smf, int tid) {
   return t;
 }
 
-template <typename T>
-__global__ __launch_bounds__(NT) void sample_topk_kernel(gstvd_sample_t a) {
+// SCORED (gstvd_sample_topk_scored): the same draw, and the drawn id's log-probability under the row's RAW logits in the same
+// launch -- one body for the two entry points, as nsp_head_kernel<T, TRAIN> has.  logp / logp_stride are unused otherwise.
+template <typename T, bool SCORED>
+__global__ __launch_bounds__(NT) void sample_topk_kernel(gstvd_sample_t a, float* logp, int64_t logp_stride) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* z = (float*)smem;                                   // [V]
   __shared__ __attribute__((aligned(16))) float smf[NWV];
@@ -78,6 +80,19 @@ __global__ __launch_bounds__(NT) void sample_topk_kernel(gstvd_sample_t a) {
     const int i = tid + j * NT;
     zr[j] = i < V ? to_f(row[i]) : 0.f;
     bn[j] = (ban && i < V) ? ban[i] : (uint8_t)0;
+  }
+  // the score's normaliser, over the raw row while it is still in the registers: max x and sum exp(x - max x) in fp32 with
+  // expf / logf (gstvd_beam_step's logp_j[v]); temperature, bans and the filters below play no part in it
+  float xmax = 0.f, xlse = 0.f;
+  if constexpr (SCORED) {
+    float rm = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < SEG; ++j) rm = (tid + j * NT < V) ? fmaxf(rm, zr[j]) : rm;
+    xmax = block_reduce(rm, smf, true);
+    float re = 0.f;
+#pragma unroll
+    for (int j = 0; j < SEG; ++j) re += (tid + j * NT < V) ? expf(zr[j] - xmax) : 0.f;
+    xlse = logf(block_reduce(re, smf, false));
   }
   float m = -INFINITY;
   int c = 0;
@@ -255,32 +270,47 @@ __global__ __launch_bounds__(NT) void sample_topk_kernel(gstvd_sample_t a) {
     }
     if (idx >= V) idx = last >= 0 ? last : 0;                  // (a row with no weight at all -- everything banned: id 0)
     a.out[(int64_t)b * a.out_stride] = idx;
+    if constexpr (SCORED) logp[(int64_t)b * logp_stride] = (to_f(row[idx]) - xmax) - xlse;
   }
 }
 
-template <typename T> int launch(const gstvd_sample_t& a, hipStream_t s) {
+template <typename T, bool SCORED> int launch(const gstvd_sample_t& a, float* logp, int64_t logp_stride, hipStream_t s) {
   const int lds = (int)(((int64_t)a.V * 4 + 15) & ~15ll);
-  static int attr_done = 0, attr_rc = 0;
+  static int attr_done = 0, attr_rc = 0;                      // (per instantiation)
   if (lds > 48 * 1024 && lds > attr_done) {
-    hipError_t e = hipFuncSetAttribute((const void*)sample_topk_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    hipError_t e = hipFuncSetAttribute((const void*)sample_topk_kernel<T, SCORED>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     attr_rc = e == hipSuccess ? 0 : (int)e;
     attr_done = lds;
   }
   if (attr_rc) return attr_rc;
-  hipLaunchKernelGGL((sample_topk_kernel<T>), dim3((unsigned)a.B), dim3(NT), lds, s, a);
+  hipLaunchKernelGGL((sample_topk_kernel<T, SCORED>), dim3((unsigned)a.B), dim3(NT), lds, s, a, logp, logp_stride);
   GSTVD_LAUNCH_CHECK();
   return 0;
 }
 
 }  // namespace
 
-extern "C" int gstvd_sample_topk(const gstvd_sample_t* a, gstvd_stream_t stream) {
+// what both entry points refuse before any launch
+static int sample_check(const gstvd_sample_t* a) {
   if (!a || !a->logits || !a->u || !a->out) return GSTVD_E_NULL;
   if (a->dtype != GSTVD_F32 && a->dtype != GSTVD_BF16) return GSTVD_E_DTYPE;
   if (a->B <= 0 || a->V <= 0 || a->ld < a->V || a->top_k < 0 || !(a->temperature > 0.f) || !(a->top_p >= 0.f)) return GSTVD_E_SHAPE;
   if (a->V > 31 * 1024) return GSTVD_E_UNSUPPORTED;                         // the row must fit the CU's LDS (and 31 weights per thread)
   if (a->ngram > 0 && (!a->hist || !a->ids_tm || a->hist_T < 0 || a->cur_len < 0 || a->n_special < 0 || a->n_special > 8 || a->ids_stride < a->B))
     return a->hist && a->ids_tm ? GSTVD_E_SHAPE : GSTVD_E_NULL;
+  return 0;
+}
+
+extern "C" int gstvd_sample_topk(const gstvd_sample_t* a, gstvd_stream_t stream) {
+  if (const int rc = sample_check(a)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  return a->dtype == GSTVD_BF16 ? launch<bf16>(*a, s) : launch<float>(*a, s);
+  return a->dtype == GSTVD_BF16 ? launch<bf16, false>(*a, nullptr, 0, s) : launch<float, false>(*a, nullptr, 0, s);
+}
+
+extern "C" int gstvd_sample_topk_scored(const gstvd_sample_t* a, float* logp, int64_t logp_stride, gstvd_stream_t stream) {
+  if (const int rc = sample_check(a)) return rc;
+  if (!logp) return GSTVD_E_NULL;
+  if (logp_stride < 1) return GSTVD_E_SHAPE;
+  hipStream_t s = (hipStream_t)stream;
+  return a->dtype == GSTVD_BF16 ? launch<bf16, true>(*a, logp, logp_stride, s) : launch<float, true>(*a, logp, logp_stride, s);
 }

@@ -131,3 +131,16 @@ def beam_finalize(sequences, scores, eos_token_id, pad_token_id, length_penalty=
     final, order = torch.sort(final, dim=1, descending=True, stable=True)
     seqs = pad_after_eos(sequences.reshape(B * K, steps), eos_token_id, pad_token_id).view(B, K, steps)
     return seqs.gather(1, order[:, :, None].expand(B, K, steps)), final, order
+
+
+def rank_samples(sequences, token_logp, eos_token_id, pad_token_id, length_penalty=1.0):
+    """End of a sample-and-rank call: sequences [B, S, steps] int64 and the drawn tokens' log-probabilities token_logp [B, S, steps]
+    -> (sequences, scores, token_logp, order), every dialog's samples best first.  Positions after the first EOS become PAD with
+    token_logp 0; score = sum(token_logp up to and including the first EOS) / len ** length_penalty; order and ties by
+    `beam_finalize` (ties to the smaller sample index).  Index work only: no host round trip."""
+    B, S, steps = sequences.shape
+    eq = (sequences == eos_token_id).long()
+    inside = (torch.cumsum(eq, dim=2) - eq) == 0
+    tl = torch.where(inside, token_logp.float(), torch.zeros((), dtype=torch.float32, device=token_logp.device))
+    seqs, scores, order = beam_finalize(sequences.contiguous(), tl.sum(2), eos_token_id, pad_token_id, length_penalty)
+    return seqs, scores, tl.gather(1, order[:, :, None].expand(B, S, steps)), order

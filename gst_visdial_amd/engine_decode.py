@@ -10,13 +10,15 @@ from ._lib import GstvdError, EPI_GELU
 
 
 class DecodeMixin(object):
-    def _decode_plan(self, ins, L0, max_seq_len, beams=1):
+    def _decode_plan(self, ins, L0, max_seq_len, beams=1, reorder=True):
         """Builds the two device programs of a decode call on the engine's arena: `encode()` (encoder, VLFusion, the
         cross-attention K/V of all decoder layers -- once per call) and `one_token(tok, t)` (ONE token per row through
         the decoder stack at position t, its self-attention K/V appended to the per-layer caches) -> fp32 logits [B, V].
         `ins` = (feats, loc, img_mask, ids, segs, att_mask, dec_ids) are the tensors the kernels read.
         beams = K > 1 (beam_search): B * K decoder rows over the B encoder rows -- cross-attention with kv_group = K -- and a
-        SECOND set of self-attention caches; `one_token(tok, t, cset)` appends to and reads set `cset` (st["QKVc"][cset])."""
+        SECOND set of self-attention caches; `one_token(tok, t, cset)` appends to and reads set `cset` (st["QKVc"][cset]).
+        reorder=False (sample_ranked: K independent rows per dialog, nothing is ever permuted): the K rows per dialog over ONE
+        cache set of B * K rows."""
         feats, loc, img_mask, ids, segs, att_mask, dec_ids = ins
         dc = self.dec_cfg
         st = {}
@@ -34,16 +36,17 @@ class DecodeMixin(object):
             st["Umax"] = Umax
             # per-layer cache of the fused Q|K|V rows, [B, Umax, 3H]: the QKV GEMM of position t writes its output rows straight
             # into cache[:, t] (row stride Umax*3H), attention reads K / V from the same rows -- no append copies
-            if beams > 1:
+            if beams > 1 and reorder:
                 Dn = Bn * beams
                 st["QKVc"] = [[Act(self.buf(Dn * Umax, 3 * H), Dn * Umax, 3 * H) for _ in range(L)] for _ in range(2)]
             else:
-                st["QKVc"] = [Act(self.buf(Bn * Umax, 3 * H), Bn * Umax, 3 * H) for _ in range(L)]
+                Dn = Bn * beams
+                st["QKVc"] = [Act(self.buf(Dn * Umax, 3 * H), Dn * Umax, 3 * H) for _ in range(L)]
             st["mark"] = self.arena.mark()
 
         def one_token(tok, t, cset=0):
             I, Bn, S, kv, QKVc, Umax = st["I"], st["Bn"] * beams, st["S"], st["kv"], st["QKVc"], st["Umax"]
-            if beams > 1:
+            if beams > 1 and reorder:
                 QKVc = QKVc[cset]
             V, Vp = dc.vocab_size, self.flat.Vp
             L, H, nh, eps = dc.num_hidden_layers, dc.hidden_size, dc.num_attention_heads, dc.layer_norm_eps
@@ -361,6 +364,124 @@ class DecodeMixin(object):
             self._decode_sessions[sig] = self._beam_session(ins, L0, max_seq_len, K)
         self._last_decode = None          # K rows per dialog: not a state rescore_sampled could score an answer against
         return out, scores
+
+    # ------------------------------------------------------------------------------------------ sample and rank
+    def _ranked_loop(self, one_token, cur, lp, hist, dec_ids, L0, max_seq_len, S, P, u):
+        """The token loop of `sample_ranked` on static buffers, free of host synchronisation (eager issue and graph capture run
+        this same code): the prefix goes to all S rows of a dialog alike; from position L0 - 1 on every token step is followed
+        by ONE launch (gstvd_sample_topk_scored) that draws token row t + 1 of the time-major id buffer `cur` and writes the
+        drawn ids' log-probabilities into row t - (L0 - 1) of the time-major buffer `lp`.  Returns the last logits."""
+        Bn = dec_ids.shape[0]
+        cur[:L0] = dec_ids.t()[:, :, None].expand(L0, Bn, S).reshape(L0, Bn * S)
+        for t in range(L0 + max_seq_len - 1):
+            logits = one_token(cur[t], t)
+            if t >= L0 - 1:
+                g = t - (L0 - 1)
+                ops.sample_topk_scored(logits, P["temperature"], P["top_k"], u[g], cur[t + 1], lp[g], None,
+                                       ngram=(hist, cur, t + 1, P["ngram"]) if P["ngram"] > 0 else None, top_p=P["top_p"])
+        return logits
+
+    def _ranked_session(self, ins, L0, max_seq_len, S, P):
+        """hipGraph form of a `sample_ranked` call, as `_decode_session` is of a `sample` call: static copies of the inputs, one
+        graph for `encode` (and the expanded n-gram history) and ONE for the whole token loop with its scored draws."""
+        static = tuple(x.clone() if x is not None else None for x in ins)
+        ids, segs, dec_ids = static[3], static[4], static[6]
+        Dn, dev = ids.shape[0] * S, ids.device
+        cur = torch.zeros(L0 + max_seq_len, Dn, dtype=torch.long, device=dev)
+        lp = torch.zeros(max_seq_len, Dn, dtype=torch.float32, device=dev)
+        u_buf = torch.zeros(max_seq_len, Dn, dtype=torch.float32, device=dev)
+        encode, one_token, st = self._decode_plan(static, L0, max_seq_len, beams=S, reorder=False)
+        from .graph import capture, gc_quiet
+        with gc_quiet():
+            g_enc = torch.cuda.CUDAGraph()
+            with capture(g_enc):
+                encode()
+                hist = (ids * (segs == 0).long()).repeat_interleave(S, 0)
+            g_dec = torch.cuda.CUDAGraph()
+            with capture(g_dec, pool=g_enc.pool(), quiesce=False):
+                logits = self._ranked_loop(one_token, cur, lp, hist, dec_ids, L0, max_seq_len, S, P, u_buf)
+
+        def refresh(new, uniforms):
+            for dst, src in zip(static, new):
+                if dst is not None:
+                    dst.copy_(src)
+            u_buf.copy_(uniforms)
+
+        return refresh, g_enc.replay, g_dec.replay, st, cur, lp, logits
+
+    @torch.no_grad()
+    def sample_ranked(self, feats, loc, img_mask, ids, segs, att_mask, dec_ids, num_samples=4, length_penalty=1.0, temperature=1.0,
+                      top_k=0, top_p=0.0, ngram_blocking_size=0, max_seq_len=18, uniforms=None):
+        """Sample-and-rank decoding of the answer -> (sequences [B, S, max_seq_len] int64, scores [B, S] fp32, token_logp
+        [B, S, max_seq_len] fp32): S = num_samples in 1..8 independent draws per dialog row under the settings of `sample`, each
+        with the model's log-probability of every drawn token, the S samples of a dialog best first.
+
+        Layout: sample j of dialog b is decoder row b*S + j over encoder row b.  Encoder, VLFusion and the cross K/V projection
+        run once on the B rows; cross-attention shares one encoder row among S decoder rows (kv_group = S); ONE set of
+        self-attention caches of B*S rows -- the rows are independent, nothing is reordered.  The n-gram filter of row b*S + j
+        reads the history of dialog b.
+        Draw: the rule of `sample` (gstvd_sample_topk) from uniforms[t, b*S + j]; `uniforms` is [max_seq_len, B*S] in (0, 1), drawn
+        once from torch's generator when absent.  With S = 1 and the same uniforms the ids are those of `sample`.
+        Score: the same launch (gstvd_sample_topk_scored) writes the drawn token's log-probability under the row's RAW logits,
+        (x[id] - max x) - log sum exp(x - max x) in fp32 -- temperature, bans, top-k and top-p play no part; this is the beam
+        step's logp, so sampled and beam scores compare.  Positions after the first EOS are PAD with token_logp 0; len = tokens
+        up to and including the first EOS, or max_seq_len; score = sum(token_logp) / len ** length_penalty; samples best first,
+        ties to the smaller sample index (decoding.beam_finalize).  All max_seq_len steps always run: nothing asks the host.
+
+        The first call with a shape runs eagerly; from then on (params['amd_decode_graph'], default on) it replays two captured
+        hipGraphs keyed by shapes, S and the sampling settings.  One library call per token more than the decoder stack's, as in
+        `sample`.  The encoder side of the call stays valid for the B best answers: `rescore_sampled(best)` works as after
+        `sample` (encoder states and cross K/V have B rows)."""
+        from . import decoding
+        dc = self.dec_cfg
+        S = int(num_samples)
+        if not 1 <= S <= ops.BEAM_MAX:
+            raise GstvdError("sample_ranked: num_samples must be in 1..%d, got %r" % (ops.BEAM_MAX, num_samples))
+        if dc.vocab_size > ops.SAMPLE_MAX_VOCAB:
+            raise GstvdError("sample_ranked: vocabulary %d exceeds the sampling kernel's %d" % (dc.vocab_size, ops.SAMPLE_MAX_VOCAB))
+        L0, Bn = dec_ids.shape[1], ids.shape[0]
+        Dn = Bn * S
+        if uniforms is not None and (uniforms.dim() != 2 or uniforms.shape[0] < max_seq_len or uniforms.shape[1] != Dn):
+            raise GstvdError("uniforms must be [max_seq_len = %d, batch * num_samples = %d] (one draw per step and decoder row), "
+                             "got %s" % (max_seq_len, Dn, tuple(uniforms.shape)))
+        if segs is None:
+            segs = torch.zeros_like(ids)
+        ins = (feats, loc, img_mask, ids, segs, att_mask, dec_ids)
+        P = dict(temperature=float(temperature), top_k=int(top_k), top_p=float(top_p), ngram=int(ngram_blocking_size))
+        sig = ("ranked", L0, max_seq_len, S, tuple(sorted(P.items()))) + tuple((tuple(x.shape), x.dtype) if x is not None else None for x in ins)
+        if uniforms is None:
+            u = torch.rand(max_seq_len, Dn, device=ids.device, dtype=torch.float32).clamp_min_(1e-12)
+        else:
+            u = uniforms.to(ids.device, torch.float32)[:max_seq_len].contiguous()
+        use_graph = bool(self.model.params.get("amd_decode_graph", True))
+        self.prepare(ids.device)
+        sess = self._decode_sessions.get(sig) if use_graph else None
+        if sess is not None:
+            refresh, run_encode, run_tokens, dst, cur, lp, logits = sess
+            refresh(ins, u)
+            run_encode()
+            run_tokens()
+        else:
+            run_encode, one_token, dst = self._decode_plan(ins, L0, max_seq_len, beams=S, reorder=False)
+            run_encode()
+            hist = (ids * (segs == 0).long()).repeat_interleave(S, 0)
+            cur = torch.zeros(L0 + max_seq_len, Dn, dtype=torch.long, device=ids.device)
+            lp = torch.zeros(max_seq_len, Dn, dtype=torch.float32, device=ids.device)
+            calls0 = _libmod.N_CALLS[0]
+            logits = self._ranked_loop(one_token, cur, lp, hist, dec_ids, L0, max_seq_len, S, P, u)
+            self.decode_lib_calls_per_token = (_libmod.N_CALLS[0] - calls0) / float(L0 + max_seq_len - 1)
+        self.last = dict(decode_logits=logits.float())
+        out, scores, token_logp, order = decoding.rank_samples(cur[L0:].view(max_seq_len, Bn, S).permute(1, 2, 0),
+                                                               lp.view(max_seq_len, Bn, S).permute(1, 2, 0),
+                                                               dc.eos_token_id, dc.pad_token_id, length_penalty)
+        self.last["sample_order"] = order
+        if use_graph and sess is None:
+            if len(self._decode_sessions) >= 4:
+                self._decode_sessions.clear()
+            self._decode_sessions[sig] = self._ranked_session(ins, L0, max_seq_len, S, P)
+        # (as in sample(): the capture executes nothing, the eager call's encoder states are what the arena holds)
+        self._last_decode = (dst, Bn, self.arena)
+        return out, scores, token_logp
 
     @torch.no_grad()
     def rescore_sampled(self, dec_ids, dec_mask=None, loss_reduction=False):

@@ -455,6 +455,23 @@ class EncoderDecoderModel(nn.Module):
                                        enc_attention_mask, dec_input_ids, num_beams=int(num_beams),
                                        length_penalty=float(length_penalty), max_seq_len=int(max_seq_len))
 
+    def sample_ranked(self, enc_image_features=None, enc_image_spatials=None, enc_image_mask=None, enc_input_ids=None,
+                      enc_segments=None, enc_attention_mask=None, dec_input_ids=None, num_samples=4, length_penalty=1.0,
+                      temperature=1.0, top_k=0, top_p=0.0, ngram_blocking_size=0, max_seq_len=18, uniforms=None, **_):
+        """Sample-and-rank decoding of the answer (Engine.sample_ranked states the rule): the forward's encoder / decoder keywords
+        -> (sequences [B, S, max_seq_len] int64, scores [B, S] fp32 = sum of the drawn tokens' log-probabilities / len **
+        length_penalty, token_logp [B, S, max_seq_len] fp32), each row's S = num_samples samples best first."""
+        from ._lib import GstvdError
+        if not 1 <= int(num_samples) <= 8:
+            raise GstvdError("num_samples must be in 1..8, got %r" % (num_samples,))
+        if _.get("num_beams") is not None and int(_["num_beams"]) > 1:
+            raise GstvdError("num_samples and num_beams = %d exclude each other: sample-and-rank draws, beam search does not"
+                             % int(_["num_beams"]))
+        return self.engine.sample_ranked(enc_image_features, enc_image_spatials, enc_image_mask, enc_input_ids, enc_segments,
+                                         enc_attention_mask, dec_input_ids, num_samples=int(num_samples),
+                                         length_penalty=float(length_penalty), temperature=temperature, top_k=top_k, top_p=top_p,
+                                         ngram_blocking_size=ngram_blocking_size, max_seq_len=int(max_seq_len), uniforms=uniforms)
+
     def forward(self, enc_image_features=None, enc_image_spatials=None, enc_image_mask=None, enc_image_target=None,
                 enc_image_label=None, enc_next_sentence_labels=None, enc_input_ids=None, enc_segments=None,
                 enc_sep_indices=None, enc_mlm_labels=None, enc_attention_mask=None, dec_input_ids=None,
@@ -463,12 +480,25 @@ class EncoderDecoderModel(nn.Module):
         hypothesis as LongTensor [B, 18] -- type and padding of the sampling branch.  `temperature`, `top_k` and `top_p` are
         accepted and ignored there (beam search ranks raw log-probabilities); `length_penalty` (default 1.0) is honoured;
         `ngram_blocking_size` > 0 with beams raises (a per-beam history needs the back-pointers).  `num_beams` absent or 1: the
-        sampling branch, untouched."""
+        sampling branch, untouched.
+        `num_samples` = S > 1 (1..8) among the decoding keywords draws S answers per row under the sampling keywords and returns
+        the most likely one (`sample_ranked`, `length_penalty` default 1.0) as LongTensor [B, 18], the sampling branch's type
+        and padding; together with `num_beams` > 1 it raises.  `num_samples` absent or 1: the sampling branch, untouched."""
         mode = self.params["mode"]
         if "train" in mode or "eval" in mode:
             return self.engine.step(enc_image_features, enc_image_spatials, enc_image_mask, enc_input_ids, enc_segments,
                                     enc_attention_mask, dec_input_ids, dec_attention_mask, dec_labels, loss_reduction)
         num_beams = decoding_kwargs.get("num_beams")
+        num_samples = decoding_kwargs.get("num_samples")
+        if num_samples is not None:
+            from ._lib import GstvdError
+            if not 1 <= int(num_samples) <= 8:
+                raise GstvdError("num_samples must be in 1..8, got %r" % (num_samples,))
+            if int(num_samples) > 1:
+                seqs, _, _ = self.sample_ranked(enc_image_features, enc_image_spatials, enc_image_mask, enc_input_ids, enc_segments,
+                                                enc_attention_mask, dec_input_ids, **decoding_kwargs)
+                return seqs[:, 0].contiguous()
+            decoding_kwargs = {k: v for k, v in decoding_kwargs.items() if k != "num_samples"}
         if num_beams is not None and int(num_beams) > 1:
             kw = dict(num_beams=int(num_beams), ngram_blocking_size=decoding_kwargs.get("ngram_blocking_size", 0))
             for k in ("length_penalty", "max_seq_len"):

@@ -797,6 +797,35 @@ SAMPLE_MAX_VOCAB = 31 * 1024   # a row of scaled logits lives in one CU's LDS (a
 SPECIAL_TOKEN_IDS = (0, 100, 101, 102, 103)      # utils/decoding_utils.py:38 (the default no reference caller overrides)
 
 
+def _sample_desc(who, logits, temperature, top_k, u, out, banned, ngram, top_p):
+    """The gstvd_sample_t of one sampling step, validated (`who` names the op in the messages)."""
+    Bn, V = logits.shape
+    d = L.SampleDesc()
+    d.logits, d.ld, d.dtype, d.B, d.V, d.top_k, d.temperature = _p(logits), logits.stride(0), dt(logits), Bn, V, int(top_k), float(temperature)
+    d.top_p = float(top_p)
+    if u.dtype != torch.float32 or not u.is_contiguous() or u.numel() != Bn:
+        raise L.GstvdError("%s: u must be a contiguous fp32 vector of B uniforms" % who)
+    if out.dtype != torch.int64 or out.numel() != Bn or logits.stride(1) != 1:
+        raise L.GstvdError("%s: out must hold B int64 ids; logits rows must be dense" % who)
+    d.u, d.out, d.out_stride = _p(u), _p(out), (out.stride(0) if out.dim() else 1)
+    if banned is not None:
+        if banned.dtype not in (torch.bool, torch.uint8) or banned.stride(1) != 1 or banned.shape[1] < V:
+            raise L.GstvdError("%s: banned must be bool / uint8 [B, >= V] with dense rows" % who)
+        d.banned, d.banned_ld = _p(banned), banned.stride(0)
+    if ngram is not None and int(ngram[3]) > 0:
+        hist, ids_tm, cur_len, n = ngram[:4]
+        special = tuple(ngram[4]) if len(ngram) > 4 else SPECIAL_TOKEN_IDS
+        if hist.dtype != torch.int64 or ids_tm.dtype != torch.int64 or hist.stride(1) != 1 or ids_tm.stride(1) != 1 or hist.shape[0] != Bn:
+            raise L.GstvdError("%s: hist [B, T] and ids_tm [L, B] must be int64 with dense rows" % who)
+        if len(special) > 8 or ids_tm.shape[0] < cur_len:
+            raise L.GstvdError("%s: at most 8 special ids; ids_tm must hold cur_len positions" % who)
+        d.hist, d.hist_ld, d.hist_T, d.ngram = _p(hist), hist.stride(0), hist.shape[1], int(n)
+        d.ids_tm, d.ids_stride, d.cur_len, d.n_special = _p(ids_tm), ids_tm.stride(0), int(cur_len), len(special)
+        for i, t in enumerate(special):
+            d.special[i] = int(t)
+    return d
+
+
 def sample_topk(logits, temperature, top_k, u, out, banned=None, ngram=None, top_p=0.0):
     """One sampling step (gstvd_sample_topk): out[b] <- inverse-CDF draw from softmax(top_p(top_k(logits / temperature, banned -> -inf))).
     top_p in (0, 1): nucleus filtering (utils/decoding_utils.py:22-34) inside the launch; 0 / >= 1: off.
@@ -805,31 +834,22 @@ def sample_topk(logits, temperature, top_k, u, out, banned=None, ngram=None, top
     ngram = (hist [B, T] int64, ids_tm [L, B] int64 time-major, cur_len, n[, special ids]): the n-gram filter of
     utils/decoding_utils.py:38-77 inside the same launch (the row's last n-1 ids are ids_tm[cur_len-(n-1) : cur_len, b])."""
     lib = L.load()
-    Bn, V = logits.shape
-    d = L.SampleDesc()
-    d.logits, d.ld, d.dtype, d.B, d.V, d.top_k, d.temperature = _p(logits), logits.stride(0), dt(logits), Bn, V, int(top_k), float(temperature)
-    d.top_p = float(top_p)
-    if u.dtype != torch.float32 or not u.is_contiguous() or u.numel() != Bn:
-        raise L.GstvdError("sample_topk: u must be a contiguous fp32 vector of B uniforms")
-    if out.dtype != torch.int64 or out.numel() != Bn or logits.stride(1) != 1:
-        raise L.GstvdError("sample_topk: out must hold B int64 ids; logits rows must be dense")
-    d.u, d.out, d.out_stride = _p(u), _p(out), (out.stride(0) if out.dim() else 1)
-    if banned is not None:
-        if banned.dtype not in (torch.bool, torch.uint8) or banned.stride(1) != 1 or banned.shape[1] < V:
-            raise L.GstvdError("sample_topk: banned must be bool / uint8 [B, >= V] with dense rows")
-        d.banned, d.banned_ld = _p(banned), banned.stride(0)
-    if ngram is not None and int(ngram[3]) > 0:
-        hist, ids_tm, cur_len, n = ngram[:4]
-        special = tuple(ngram[4]) if len(ngram) > 4 else SPECIAL_TOKEN_IDS
-        if hist.dtype != torch.int64 or ids_tm.dtype != torch.int64 or hist.stride(1) != 1 or ids_tm.stride(1) != 1 or hist.shape[0] != Bn:
-            raise L.GstvdError("sample_topk: hist [B, T] and ids_tm [L, B] must be int64 with dense rows")
-        if len(special) > 8 or ids_tm.shape[0] < cur_len:
-            raise L.GstvdError("sample_topk: at most 8 special ids; ids_tm must hold cur_len positions")
-        d.hist, d.hist_ld, d.hist_T, d.ngram = _p(hist), hist.stride(0), hist.shape[1], int(n)
-        d.ids_tm, d.ids_stride, d.cur_len, d.n_special = _p(ids_tm), ids_tm.stride(0), int(cur_len), len(special)
-        for i, t in enumerate(special):
-            d.special[i] = int(t)
+    d = _sample_desc("sample_topk", logits, temperature, top_k, u, out, banned, ngram, top_p)
     L.check("gstvd_sample_topk", lib.gstvd_sample_topk(C.byref(d), _stream()))
+
+
+def sample_topk_scored(logits, temperature, top_k, u, out, logp, banned=None, ngram=None, top_p=0.0):
+    """`sample_topk` -- the same draw, the same ids -- and in the same launch (gstvd_sample_topk_scored) logp[b] <- the drawn id's
+    log-probability under the row's RAW logits, (x[id] - max x) - log sum exp(x - max x) in fp32: temperature, bans and filters
+    play no part in it (the definition `beam_step` uses).  logp: fp32 view with B elements (any positive stride, e.g. a row of a
+    time-major buffer or a column), as `out` is."""
+    lib = L.load()
+    d = _sample_desc("sample_topk_scored", logits, temperature, top_k, u, out, banned, ngram, top_p)
+    if (not isinstance(logp, torch.Tensor) or not logp.is_cuda or logp.dtype != torch.float32 or logp.dim() > 1
+            or logp.numel() != logits.shape[0] or (logp.dim() == 1 and logp.numel() > 1 and logp.stride(0) < 1)):
+        raise L.GstvdError("sample_topk_scored: logp must hold B fp32 values on the GPU (a vector or a strided column)")
+    stride = logp.stride(0) if logp.dim() and logp.stride(0) > 0 else 1
+    L.check("gstvd_sample_topk_scored", lib.gstvd_sample_topk_scored(C.byref(d), _p(logp), stride, _stream()))
 
 
 def answer_scores(logits, lse, dec_ids, rows, U, scores):

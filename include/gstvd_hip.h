@@ -301,6 +301,14 @@ typedef struct {
   float top_p; int32_t reserved_;                                       /* ABI 6 */
 } gstvd_sample_t;
 int gstvd_sample_topk(const gstvd_sample_t* a, gstvd_stream_t s);
+/* (entry point added for sample-and-rank decoding, no signature changed: ABI stays 9)
+ * The same draw -- the rule above, the same ids -- and in the same launch the drawn id's log-probability
+ *   logp[b * logp_stride] = (x[id] - max x) - log(sum_v exp(x[v] - max x))
+ * in fp32 (expf / logf) over the row's RAW logits x[0..V): temperature, `banned`, the n-gram filter, top-k and top-p play no
+ * part in it.  This is gstvd_beam_step's logp_j[v], so sampled and beam scores mean the same thing.  A row in which everything
+ * is banned draws id 0 and reports the log-probability of id 0; columns V..ld are never read.  Refuses what gstvd_sample_topk
+ * refuses, then logp == NULL (GSTVD_E_NULL) and logp_stride < 1 (GSTVD_E_SHAPE), before any launch. */
+int gstvd_sample_topk_scored(const gstvd_sample_t* a, float* logp, int64_t logp_stride, gstvd_stream_t s);
 
 /* backward of VLFusion's concat + dropout (visual_dialog_model.py:132-133): d_enc [B, R+T, H] ->
  * d_v [B*R, H] (vision rows first) and d_t [B*T, H], each multiplied by the dropout mask its forward GEMM
