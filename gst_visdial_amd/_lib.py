@@ -110,6 +110,26 @@ class BeamReorderDesc(C.Structure):
                 ("reserved_", _i32)]
 
 
+class ContextAppendDesc(C.Structure):
+    """gstvd_context_append_t: the context splice of the generation loop for all rows in one launch."""
+    _fields_ = [("ctx_ids", _vp), ("ld_ctx", _i64), ("segments", _vp), ("ld_seg", _i64), ("att_mask", _vp), ("ld_att", _i64),
+                ("ctx_len", _vp), ("new_ids", _vp), ("ld_new", _i64), ("B", _i64), ("T", _i64), ("U", _i64),
+                ("sep_id", _i64), ("segment_value", _i64), ("n_out", _vp), ("abnormal", _vp), ("full", _vp)]
+
+
+class DialogRowsDesc(C.Structure):
+    """gstvd_dialog_rows_t: the student's train rows of B generated dialogs of R rounds, one launch."""
+    _fields_ = [("cap", _vp), ("ld_cap", _i64), ("ques", _vp), ("ans", _vp), ("ld_utt", _i64), ("ppl", _vp), ("valid", _vp),
+                ("u_tok", _vp), ("ld_u", _i64),
+                ("enc_ids", _vp), ("enc_seg", _vp), ("enc_mlm", _vp), ("enc_att", _vp), ("ld_enc", _i64),
+                ("enc_sep", _vp), ("ld_sep", _i64), ("enc_hist_len", _vp),
+                ("dec_ids", _vp), ("dec_labels", _vp), ("dec_att", _vp), ("ld_dec", _i64),
+                ("mask_prob", C.c_double), ("threshold", C.c_double),
+                ("cls", _i64), ("sep", _i64), ("mask", _i64), ("special", _i64 * 8),
+                ("B", _i32), ("R", _i32), ("U", _i32), ("Lc", _i32), ("T", _i32), ("S", _i32), ("Ud", _i32), ("n_special", _i32),
+                ("select_data", _i32), ("reserved_", _i32)]
+
+
 class ColsumEntry(C.Structure):
     _fields_ = [("partial", _vp), ("out", _vp * 3), ("nblk", _i64), ("stride", _i64), ("H", _i64),
                 ("nvec", _i32), ("accumulate", _i32 * 3), ("blk0", _i32)]
@@ -177,6 +197,8 @@ SIGNATURES = {
     "gstvd_nsp_train_bwd": (_i32, [C.POINTER(NspTrainDesc), _vp]),
     "gstvd_beam_step": (_i32, [C.POINTER(BeamStepDesc), _vp]),
     "gstvd_beam_reorder": (_i32, [C.POINTER(BeamReorderDesc), _vp]),
+    "gstvd_context_append": (_i32, [C.POINTER(ContextAppendDesc), _vp]),
+    "gstvd_dialog_rows": (_i32, [C.POINTER(DialogRowsDesc), _vp]),
 }
 
 _STATUS = {-1: "GSTVD_E_DTYPE", -2: "GSTVD_E_SHAPE", -3: "GSTVD_E_ALIGN", -4: "GSTVD_E_NULL", -5: "GSTVD_E_UNSUPPORTED"}

@@ -941,6 +941,131 @@ def beam_reorder(src, dst, parent, t, H):
     _prof_end(e0, "beam_reorder", 0.0, 2.0 * n * B * K * (t + 1) * 2 * H * src[0].element_size(), (n, B * K, t + 1, H))
 
 
+def _rows_i64(who, name, t, cols=None, dtype=torch.int64):
+    """A 2-D tensor of `dtype` with dense rows (row stride free) -- the layout the self-training entries take."""
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1) \
+            or (cols is not None and t.shape[1] != cols) or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        raise L.GstvdError("%s: %s must be %s [rows, %s] with dense rows" % (who, name, str(dtype).replace("torch.", ""),
+                                                                             "cols" if cols is None else cols))
+    return t
+
+
+def _flag_vec(who, name, t, B, dtype):
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.dim() != 1 or t.numel() != B or not t.is_contiguous():
+        raise L.GstvdError("%s: %s must be a contiguous %s vector of %d elements" % (who, name, str(dtype).replace("torch.", ""), B))
+    return t
+
+
+def context_append(ctx_ids, ctx_len, new_ids, sep_id, abnormal, full, segments=None, segment_value=0, att_mask=None, n_out=None):
+    """`generate.append_to_context` for all rows in one launch, without a host synchronisation (gstvd_context_append; the rule is
+    stated in include/gstvd_hip.h).  ctx_ids int64 [B, T], ctx_len int64 [B] and, when given, segments int64 [B, T] / att_mask
+    fp32 [B, T] are updated in place from new_ids int64 [B, U]; a row that would overflow receives one [SEP] and abnormal[b] = 1;
+    a row whose context is full already is left alone with abnormal[b] = full[b] = 1 (int32 [B]; the kernel only ever sets them:
+    zero them in front of a loop, read `full` once behind it).  n_out int64 [B], when given, receives the tokens written per row."""
+    who = "context_append"
+    _rows_i64(who, "ctx_ids", ctx_ids)
+    B, T = ctx_ids.shape
+    _rows_i64(who, "new_ids", new_ids)
+    if new_ids.shape[0] != B or new_ids.shape[1] < 1 or T < 1:
+        raise L.GstvdError("%s: new_ids must be [B = %d, U >= 1] and T >= 1" % (who, B))
+    _flag_vec(who, "ctx_len", ctx_len, B, torch.int64)
+    _flag_vec(who, "abnormal", abnormal, B, torch.int32)
+    _flag_vec(who, "full", full, B, torch.int32)
+    if segments is not None and _rows_i64(who, "segments", segments, T).shape[0] != B:
+        raise L.GstvdError("%s: segments must be [B, T]" % who)
+    if att_mask is not None and _rows_i64(who, "att_mask", att_mask, T, torch.float32).shape[0] != B:
+        raise L.GstvdError("%s: att_mask must be [B, T]" % who)
+    if n_out is not None:
+        _flag_vec(who, "n_out", n_out, B, torch.int64)
+    d = L.ContextAppendDesc()
+    d.ctx_ids, d.ld_ctx = _p(ctx_ids), ctx_ids.stride(0)
+    d.segments, d.ld_seg = (_p(segments), segments.stride(0)) if segments is not None else (None, 0)
+    d.att_mask, d.ld_att = (_p(att_mask), att_mask.stride(0)) if att_mask is not None else (None, 0)
+    d.ctx_len, d.new_ids, d.ld_new = _p(ctx_len), _p(new_ids), new_ids.stride(0)
+    d.B, d.T, d.U, d.sep_id, d.segment_value = B, T, new_ids.shape[1], int(sep_id), int(segment_value)
+    d.n_out, d.abnormal, d.full = _p(n_out), _p(abnormal), _p(full)
+    lib = L.load()
+    L.check("gstvd_context_append", lib.gstvd_context_append(C.byref(d), _stream()))
+
+
+DIALOG_MAX_SEP = 25            # max_sep_len of utils/data_utils.py:34 (no reference caller overrides it)
+DIALOG_MAX_UTT = 64            # tokens of one utterance row the kernel's lanes cover (U, Lc)
+_DIALOG_OUT = (("enc_ids", torch.int64, "T"), ("enc_seg", torch.int64, "T"), ("enc_mlm", torch.int64, "T"),
+               ("enc_att", torch.float32, "T"), ("enc_sep", torch.int64, "S"), ("dec_ids", torch.int64, "Ud"),
+               ("dec_labels", torch.int64, "Ud"), ("dec_att", torch.float32, "Ud"))
+
+
+def dialog_rows(cap, ques, ans, ppl, T, Ud, select_data, threshold, mask_prob, valid=None, u_tok=None, cls=101, sep=102,
+                mask=103, special=SPECIAL_TOKEN_IDS, S=DIALOG_MAX_SEP, out=None):
+    """The student's train rows of B generated dialogs of R rounds in one launch (gstvd_dialog_rows; the rule -- the loader of
+    dataloader/dataloader_cc12m_gen.py:104-248 on token ids -- is stated in include/gstvd_hip.h).
+    cap int64 [B, Lc <= 64] (0-padded captions); ques, ans int64 [B, R, U <= 64] as the generation loop recorded them; ppl fp32
+    [B, R]; valid int32 [B] or None (0: the dialog's labels are zeroed); u_tok fp32 [B, R, T], required when mask_prob > 0.
+    Returns a dict: enc_ids, enc_seg, enc_mlm int64 [B, R, T], enc_att fp32 [B, R, T], enc_sep int64 [B, R, S], enc_hist_len int64
+    [B, R], dec_ids, dec_labels int64 [B, R, Ud], dec_att fp32 [B, R, Ud].  `out`: a dict of caller-owned 2-D views [B * R, .] with
+    dense rows (enc_* of one row stride, dec_* of one) and enc_hist_len [B * R] to write into instead (returned as it is)."""
+    who = "dialog_rows"
+    for name, t in (("ques", ques), ("ans", ans)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.dim() != 3 or not t.is_contiguous():
+            raise L.GstvdError("%s: %s must be a contiguous int64 [B, R, U] tensor" % (who, name))
+    B, R, U = ques.shape
+    T, Ud, S = int(T), int(Ud), int(S)
+    if tuple(ans.shape) != (B, R, U):
+        raise L.GstvdError("%s: ques and ans must share one shape [B, R, U]" % who)
+    if R < 1 or 2 * R > S or 2 * R > 64:
+        raise L.GstvdError("%s: %d rounds give %d separators, more than max_sep_len = %d allows (1 <= R, 2R <= S)" % (who, R, 2 * R, S))
+    _rows_i64(who, "cap", cap)
+    Lc = cap.shape[1]
+    if cap.shape[0] != B or not 1 <= U <= DIALOG_MAX_UTT or not 1 <= Lc <= DIALOG_MAX_UTT or T < 2 or Ud < 3:
+        raise L.GstvdError("%s: cap [B, Lc], 1 <= U, Lc <= %d, T >= 2 and Ud >= 3 (got U %d, Lc %d, T %d, Ud %d)"
+                           % (who, DIALOG_MAX_UTT, U, Lc, T, Ud))
+    if not isinstance(ppl, torch.Tensor) or ppl.dtype != torch.float32 or tuple(ppl.shape) != (B, R) or not ppl.is_contiguous():
+        raise L.GstvdError("%s: ppl must be a contiguous fp32 [B, R] tensor" % who)
+    if valid is not None:
+        _flag_vec(who, "valid", valid, B, torch.int32)
+    special = tuple(int(t) for t in special)
+    if len(special) > 8:
+        raise L.GstvdError("%s: at most 8 special ids" % who)
+    mask_prob, threshold = float(mask_prob), float(threshold)
+    if u_tok is None and mask_prob > 0.0:
+        raise L.GstvdError("%s: mask_prob = %g needs u_tok, one uniform per row position [B, R, T]" % (who, mask_prob))
+    if u_tok is not None and (not isinstance(u_tok, torch.Tensor) or u_tok.dtype != torch.float32 or tuple(u_tok.shape) != (B, R, T)
+                              or not u_tok.is_contiguous()):
+        raise L.GstvdError("%s: u_tok must be a contiguous fp32 [B, R, T = %d] tensor" % (who, T))
+    dims = dict(T=T, S=S, Ud=Ud)
+    if out is None:
+        if not ques.is_cuda:
+            _p(ques)
+        o = {k: torch.empty(B * R, dims[c], dtype=dtp, device=ques.device) for k, dtp, c in _DIALOG_OUT}
+        o["enc_hist_len"] = torch.empty(B * R, dtype=torch.int64, device=ques.device)
+    else:
+        o = out
+        for k, dtp, c in _DIALOG_OUT:
+            if _rows_i64(who, "out[%s]" % k, o[k], dims[c], dtp).shape[0] != B * R:
+                raise L.GstvdError("%s: out[%s] must have B * R = %d rows" % (who, k, B * R))
+        _flag_vec(who, "out[enc_hist_len]", o["enc_hist_len"], B * R, torch.int64)
+        for grp in (("enc_ids", "enc_seg", "enc_mlm", "enc_att"), ("dec_ids", "dec_labels", "dec_att")):
+            if len(set(o[k].stride(0) for k in grp)) != 1:
+                raise L.GstvdError("%s: %s must share one row stride" % (who, ", ".join(grp)))
+    d = L.DialogRowsDesc()
+    d.cap, d.ld_cap, d.ques, d.ans, d.ld_utt = _p(cap), cap.stride(0), _p(ques), _p(ans), U
+    d.ppl, d.valid, d.u_tok, d.ld_u = _p(ppl), _p(valid), _p(u_tok), T
+    d.enc_ids, d.enc_seg, d.enc_mlm, d.enc_att, d.ld_enc = _p(o["enc_ids"]), _p(o["enc_seg"]), _p(o["enc_mlm"]), _p(o["enc_att"]), o["enc_ids"].stride(0)
+    d.enc_sep, d.ld_sep, d.enc_hist_len = _p(o["enc_sep"]), o["enc_sep"].stride(0), _p(o["enc_hist_len"])
+    d.dec_ids, d.dec_labels, d.dec_att, d.ld_dec = _p(o["dec_ids"]), _p(o["dec_labels"]), _p(o["dec_att"]), o["dec_ids"].stride(0)
+    d.mask_prob, d.threshold, d.cls, d.sep, d.mask = mask_prob, threshold, int(cls), int(sep), int(mask)
+    for i, t in enumerate(special):
+        d.special[i] = t
+    d.B, d.R, d.U, d.Lc, d.T, d.S, d.Ud, d.n_special, d.select_data = B, R, U, Lc, T, S, Ud, len(special), int(bool(select_data))
+    lib = L.load()
+    L.check("gstvd_dialog_rows", lib.gstvd_dialog_rows(C.byref(d), _stream()))
+    if out is not None:
+        return o
+    res = {k: o[k].view(B, R, dims[c]) for k, _, c in _DIALOG_OUT}
+    res["enc_hist_len"] = o["enc_hist_len"].view(B, R)
+    return res
+
+
 FUSION = {"mul": 0, "sum": 1}
 
 

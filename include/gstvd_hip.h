@@ -517,6 +517,74 @@ typedef struct {
 } gstvd_beam_reorder_t;
 int gstvd_beam_reorder(const gstvd_beam_reorder_t* a, gstvd_stream_t s);
 
+/* ---- self-training glue (entry points added, no signature changed: ABI stays 9) ------------------------------------------------
+ * Both entries are one launch each, without atomics, workspace, allocation or host synchronisation (capture-safe).
+ *
+ * gstvd_context_append: the context splice of the generation loop (generate.py:145-160, 214-228) for all B rows at once.
+ * ctx_ids int64 [B, T] (row stride ld_ctx), segments int64 [B, T] or NULL, att_mask fp32 [B, T] or NULL, ctx_len int64 [B],
+ * new_ids int64 [B, U] (row stride ld_new), n_out int64 [B] or NULL, abnormal / full int32 [B].  Row b:
+ *   n = the number of non-zero entries of new_ids[b],  start = ctx_len[b];
+ *   start + n <= T:  ctx_ids[b, start + c] = new_ids[b, c] for c < n -- the FIRST n entries, a zero among them included (the
+ *                    reference copies ids[:n]);  n_eff = n;
+ *   else start < T:  ctx_ids[b, start] = sep_id;  n_eff = 1;  abnormal[b] = 1;
+ *   else (the context is full already):  nothing of the row is written;  n_eff = 0;  abnormal[b] = full[b] = 1  (the reference
+ *                    raises here; the caller reads `full` once, after its loop, and raises then).  A negative ctx_len[b] is
+ *                    handled as a full row;
+ *   over [start, start + n_eff):  segments = segment_value when given,  att_mask[p] = (ctx_ids[b, p] != 0) when given;
+ *   ctx_len[b] += n_eff;  n_out[b] = n_eff when given.
+ * abnormal is OR-ed and full is set: the kernel never clears either.  Refused before the launch: a null required pointer
+ * (GSTVD_E_NULL); T < 1, U < 1 or a row stride below its row (GSTVD_E_SHAPE). */
+typedef struct {
+  int64_t* ctx_ids; int64_t ld_ctx;
+  int64_t* segments; int64_t ld_seg;
+  float* att_mask; int64_t ld_att;
+  int64_t* ctx_len;
+  const int64_t* new_ids; int64_t ld_new;
+  int64_t B; int64_t T; int64_t U;
+  int64_t sep_id; int64_t segment_value;
+  int64_t* n_out; int32_t* abnormal; int32_t* full;
+} gstvd_context_append_t;
+int gstvd_context_append(const gstvd_context_append_t* a, gstvd_stream_t s);
+
+/* gstvd_dialog_rows: the student's train rows of B generated dialogs of R rounds -- what dataloader/dataloader_cc12m_gen.py:104-248
+ * builds through utils/data_utils.py:34-71 (encode_input) from re-tokenised text, computed from the token ids for all B * R rows.
+ * Inputs: cap int64 [B, Lc] (row stride ld_cap); ques, ans int64 [B, R, U] (row stride ld_utt between the B * R rows); ppl fp32
+ * [B, R]; valid int32 [B] or NULL; u_tok fp32 [B, R, T] (row stride ld_u; may be NULL when mask_prob == 0).
+ * Outputs, over the B * R rows: enc_ids, enc_seg, enc_mlm int64 [., T] and enc_att fp32 [., T] (row stride ld_enc, in elements of
+ * each); enc_sep int64 [., S] (ld_sep); enc_hist_len int64 [.]; dec_ids, dec_labels int64 [., Ud] and dec_att fp32 [., Ud]
+ * (ld_dec).  Every output element is written exactly once: nothing needs zeroing in front.
+ *   Utterances.  The caption: the entries of cap[b] in front of its first zero.  Question / answer k: the entries of ques[b, k] /
+ *     ans[b, k] that are not among special[0 .. n_special), in order (what tokenizer.decode(skip_special_tokens=True) keeps).  An
+ *     utterance may be empty.
+ *   Context of round j (0-based): caption, q0, a0, ..., q(j-1), a(j-1), qj -- 2j + 2 utterances, answers uncut -- under
+ *     encode_input with start_segment 1: [CLS] opens the row, every utterance is followed by [SEP], the segment starts at 1 and
+ *     flips after every utterance ([CLS] and each [SEP] carry their utterance's segment), the row is cut at T (which may lose the
+ *     last [SEP]) and padded with 0.  enc_sep: the running positions of the separators, the first S of them, 0-padded, NOT cut at
+ *     T (positions >= T are listed).  enc_hist_len = 2j + 1.  enc_att = (enc_ids != 0), after the masking.
+ *   Mask noise.  An utterance token at (untruncated) position p < T is masked iff (double)u_tok[b, j, p] < mask_prob (strict, in
+ *     double): enc_ids = mask, enc_mlm = the token (no 80 / 10 / 10 rule).  Everything else -- [CLS], [SEP], padding -- has
+ *     enc_mlm = -1.
+ *   Target of round j.  The answer's first Ud - 2 tokens; dec_ids = [CLS] answer [SEP], 0-padded to Ud; dec_att = (dec_ids != 0)
+ *     at this point (1 through the [SEP] slot); dec_labels = dec_ids shifted left by one -- all 0 when
+ *     select_data && (double)ppl[b, j] >= threshold (literal: a NaN perplexity keeps its labels) or when valid is given and
+ *     valid[b] == 0; last, [SEP] -> 0 in dec_ids.
+ * Refused before the launch: a null required pointer, mask_prob > 0 without u_tok (GSTVD_E_NULL); R < 1, 2R > S, R > 32, U or Lc
+ * outside 1..64, T < 2, Ud < 3, n_special outside 0..8, a row stride below its row (GSTVD_E_SHAPE). */
+typedef struct {
+  const int64_t* cap; int64_t ld_cap;
+  const int64_t* ques; const int64_t* ans; int64_t ld_utt;
+  const float* ppl; const int32_t* valid;
+  const float* u_tok; int64_t ld_u;
+  int64_t* enc_ids; int64_t* enc_seg; int64_t* enc_mlm; float* enc_att; int64_t ld_enc;
+  int64_t* enc_sep; int64_t ld_sep; int64_t* enc_hist_len;
+  int64_t* dec_ids; int64_t* dec_labels; float* dec_att; int64_t ld_dec;
+  double mask_prob; double threshold;
+  int64_t cls; int64_t sep; int64_t mask; int64_t special[8];
+  int32_t B; int32_t R; int32_t U; int32_t Lc; int32_t T; int32_t S; int32_t Ud; int32_t n_special; int32_t select_data;
+  int32_t reserved_;
+} gstvd_dialog_rows_t;
+int gstvd_dialog_rows(const gstvd_dialog_rows_t* a, gstvd_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
