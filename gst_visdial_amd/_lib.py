@@ -199,6 +199,9 @@ SIGNATURES = {
     "gstvd_beam_reorder": (_i32, [C.POINTER(BeamReorderDesc), _vp]),
     "gstvd_context_append": (_i32, [C.POINTER(ContextAppendDesc), _vp]),
     "gstvd_dialog_rows": (_i32, [C.POINTER(DialogRowsDesc), _vp]),
+    "gstvd_rows_argmax": (_i32, [_vp, _i64, _i64, _i64, _i32, _vp, _vp, _vp]),
+    "gstvd_vocab_argmax_ws_bytes": (_i64, [_i64, _i64]),
+    "gstvd_vocab_argmax": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _i32, _vp, _i64, _vp, _vp, _vp]),
 }
 
 _STATUS = {-1: "GSTVD_E_DTYPE", -2: "GSTVD_E_SHAPE", -3: "GSTVD_E_ALIGN", -4: "GSTVD_E_NULL", -5: "GSTVD_E_UNSUPPORTED"}

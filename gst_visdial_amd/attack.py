@@ -13,8 +13,12 @@ What differs from the script, none of it in the numbers it defines:
   * the rounds that are not attacked are scored with one encoder pass per round (EncoderDecoderModel.score_candidates), as
     evaluate.py does; the attacked round cannot be -- its 100 contexts differ after the perturbation.
 
-The text attacks (`coreference`, `random_token`) need a pretrained BertForMaskedLM and counter-fitted word vectors
-(utils/text_attack.py); neither is part of this package, and asking for them raises.
+`random_token` (evaluate_gen_attack.py:209-226) fills the [MASK] tokens of a chunk's context with the arg-max token of a masked
+LM and scores the options on the filled-in context.  The masked LM is not part of this package's weights: the caller builds a
+`mlm.MaskedLMFiller` from a BertForMaskedLM state dict and passes it as `textattack=` (or params["textattack"]).  The filled
+chunk is row 0 repeated, so when its segments and attention masks are also one row repeated it is scored with ONE encoder pass
+(score_candidates), where the reference runs 100.  Without a filler `random_token` raises, as `coreference` always does: that
+one needs counter-fitted word vectors and host-side string work (utils/text_attack.py), neither of which is here.
 """
 import contextlib
 
@@ -107,22 +111,39 @@ def attacked_round(batch):
     return int(int((sep[0] != 0).sum()) / 2) == int(batch["round_id"].reshape(-1)[0])
 
 
-def forward_attack(model, batch, params, epsilon=1.0, inputs_only=True):
-    """The `fgsm` branch of evaluate_gen_attack.forward (evaluate_gen_attack.py:28-165) -> lm_scores [rows, U, vocab].
-    `batch`: one chunk of the eval loader's rows (host tensors) with its dialog's `round_id` and `gt_relevance`."""
+def _filler(params, textattack):
+    return textattack if textattack is not None else params.get("textattack")
+
+
+def _filled_ids(filler, batch):
+    """random_token: the chunk's context ids after the fill-in, [rows, T] on the filler's device.  The [MASK] positions of row 0
+    are found on the host tensor (no device round trip); the loader's tensor is left as it is."""
+    ids = _flat(batch["enc_input_ids"], 1)
+    return filler.fill(ids, _flat(batch["enc_segments"], 1), _flat(batch["enc_att_mask"], 1), rows=filler.host_rows(ids[:1]))
+
+
+def forward_attack(model, batch, params, epsilon=1.0, inputs_only=True, textattack=None):
+    """The `fgsm` and `random_token` branches of evaluate_gen_attack.forward (evaluate_gen_attack.py:28-165, 209-226) -> lm_scores
+    [rows, U, vocab].  `batch`: one chunk of the eval loader's rows (host tensors) with its dialog's `round_id` and
+    `gt_relevance`.  `textattack`: the masked-LM filler of `random_token` (mlm.MaskedLMFiller, or anything with its `fill` and
+    `host_rows`); also read from params["textattack"]."""
     attack = params.get("attack")
-    if attack in ("coreference", "random_token"):
+    filler = _filler(params, textattack)
+    if attack == "coreference" or (attack == "random_token" and filler is None):
         raise NotImplementedError(
             "attack=%r is a text attack (utils/text_attack.py): it needs a pretrained BertForMaskedLM, the counter-fitted word "
             "vectors (cos_sim_counter_fitting, cos_sim_idx2word, cos_sim_word2idx)%s, none of which this package carries.  "
-            "Only attack='fgsm' is implemented" % (attack, " and the coreference dependencies" if attack == "coreference" else ""))
-    if attack != "fgsm":
+            "Only attack='fgsm' is implemented without further inputs; attack='random_token' runs once a masked-LM filler is "
+            "supplied as textattack= (gst_visdial_amd.mlm.MaskedLMFiller, loaded from a BertForMaskedLM state dict)"
+            % (attack, " and the coreference dependencies" if attack == "coreference" else ""))
+    if attack not in ("fgsm", "random_token"):
         raise NotImplementedError("attack=%r: no such attack (the reference has 'fgsm', 'coreference', 'random_token'; only "
-                                  "'fgsm' is implemented)" % (attack,))
+                                  "'fgsm' and, with a filler, 'random_token' are implemented)" % (attack,))
     dev = params["device"]
-    hit = attacked_round(batch)                                  # on the host tensors: no device round trip
+    text = attack == "random_token"
+    hit = (not text) and attacked_round(batch)                   # on the host tensors: no device round trip
     kw = dict.fromkeys(_MODEL_KEYS)
-    kw.update(enc_input_ids=_flat(batch["enc_input_ids"], 1).to(dev), enc_segments=_flat(batch["enc_segments"], 1).to(dev),
+    kw.update(enc_input_ids=_filled_ids(filler, batch).to(dev) if text else _flat(batch["enc_input_ids"], 1).to(dev), enc_segments=_flat(batch["enc_segments"], 1).to(dev),
               enc_sep_indices=_flat(batch["enc_sep_indices"], 1).to(dev), enc_mlm_labels=_flat(batch["enc_mlm_labels"], 1).to(dev),
               enc_attention_mask=_flat(batch["enc_att_mask"], 1).to(dev),
               dec_input_ids=_flat(batch["dec_input_ids"], 1).to(dev, copy=True),     # (mutated below: never the loader's tensor)
@@ -139,13 +160,24 @@ def _same_context(batch, keys=("enc_input_ids", "enc_segments", "enc_att_mask"))
     return all(bool((batch[k] == batch[k][:1]).all()) for k in keys)
 
 
-def score_chunk(model, item, params, epsilon):
-    """Scores [rows] of one chunk: the script's lines 321-333 for the attacked round, one encoder pass for any other."""
+def score_chunk(model, item, params, epsilon, textattack=None):
+    """Scores [rows] of one chunk: the script's lines 321-333 for the round FGSM attacks, one encoder pass for any other.
+    random_token: every chunk is filled in; the filled context is row 0 repeated, so it takes the one-pass route whenever the
+    chunk's segments and attention masks are one row repeated too (they are in the eval loader's chunks)."""
     dev = params["device"]
     core = _core(model)
     ids = item["dec_input_ids"]
-    if attacked_round(item) or not _same_context(item):
-        forward_attack(model, item, params, epsilon)
+    if params.get("attack") == "random_token":
+        filler = _filler(params, textattack)
+        if filler is None or not _same_context(item, ("enc_segments", "enc_att_mask")):
+            many = True                                       # (no filler: forward_attack raises, naming what is missing)
+        else:
+            many = False
+            item = dict(item, enc_input_ids=_filled_ids(filler, item)[:1])
+    else:
+        many = attacked_round(item) or not _same_context(item)
+    if many:
+        forward_attack(model, item, params, epsilon, textattack=textattack)
         last = core.engine.last          # the second forward's logits and their log-sum-exp, still in the arena
         scores = torch.empty(ids.shape[0], dtype=torch.float32, device=dev)
         ops.answer_scores(last["logits"].t, last["lse"], ids.to(dev).contiguous(), ids.shape[0], ids.shape[1], scores)
@@ -157,10 +189,11 @@ def score_chunk(model, item, params, epsilon):
 
 
 @torch.no_grad()
-def evaluate_attack(model, dataloader, params, epsilon=1.0, mode="vd_eval_val"):
-    """The loop of evaluate_gen_attack.evaluate (evaluate_gen_attack.py:233-369) for attack='fgsm': chunks of 100 option rows,
-    the metrics of metrics.py; -> (ranks_json, metrics) as evaluate.evaluate returns them."""
-    if params.get("attack") != "fgsm":
+def evaluate_attack(model, dataloader, params, epsilon=1.0, mode="vd_eval_val", textattack=None):
+    """The loop of evaluate_gen_attack.evaluate (evaluate_gen_attack.py:233-369) for attack='fgsm' and, with a masked-LM filler
+    (`textattack=` or params["textattack"]), attack='random_token': chunks of 100 option rows, the metrics of metrics.py;
+    -> (ranks_json, metrics) as evaluate.evaluate returns them."""
+    if params.get("attack") != "fgsm" and not (params.get("attack") == "random_token" and _filler(params, textattack) is not None):
         forward_attack(model, {}, params)           # raises, naming what is missing
     sparse, ndcg, ranks_json = SparseGTMetrics(), NDCG(), []
     model.eval()
@@ -183,7 +216,7 @@ def evaluate_attack(model, dataloader, params, epsilon=1.0, mode="vd_eval_val"):
                 item["enc_image_mask"] = batch["enc_image_mask"][d:d + 1].expand(ROWS_PER_CALL, -1)
                 item["round_id"] = batch["round_id"][d:d + 1]
                 item["gt_relevance"] = batch["gt_relevance"][d]
-                out.append(score_chunk(model, item, params, epsilon))
+                out.append(score_chunk(model, item, params, epsilon, textattack=textattack))
         scores = torch.cat(out, 0).view(Bd, rounds, options)
         if mode == "vd_eval_val":
             sparse.observe(scores, batch["gt_option_inds"])

@@ -60,8 +60,11 @@ class BertConfig(_Cfg):
 
     def validate(self):
         assert len(self.v_biattention_id) == len(self.t_biattention_id)
-        assert max(self.v_biattention_id) < self.v_num_hidden_layers
-        assert max(self.t_biattention_id) < self.num_hidden_layers
+        if self.text_only():
+            pass        # no connection layer, no vision layer: encoder_schedule is ("t", 0..N-1), BertForMaskedLM's stack (mlm.py)
+        else:
+            assert max(self.v_biattention_id) < self.v_num_hidden_layers
+            assert max(self.t_biattention_id) < self.num_hidden_layers
         for k in ("fast_mode", "in_batch_pairs", "fixed_v_layer", "fixed_t_layer"):
             if getattr(self, k):
                 raise NotImplementedError("config.%s is not on the enc_dec_a path (reference default is off)" % k)
@@ -72,6 +75,12 @@ class BertConfig(_Cfg):
         if self.predict_feature and "enc_dec" not in str(getattr(self, "model_arch", "enc_dec")):
             raise NotImplementedError("predict_feature=True (the MSE region loss of models/vilbert_dialog.py:1489-1493) is not "
                                       "implemented; the shipped configs use the KL form")
+
+
+    def text_only(self):
+        """The degenerate single-stream form: no co-attention and no vision layer, so the text chain never meets the image."""
+        return (list(self.v_biattention_id) == [] and list(self.t_biattention_id) == [] and self.v_num_hidden_layers == 0
+                and self.num_hidden_layers >= 1)
 
 
 class DecoderConfig(_Cfg):

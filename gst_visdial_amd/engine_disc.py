@@ -197,6 +197,42 @@ class DiscMixin(object):
         self.last = dict(enc_t=xt, enc_v=xv)
         return z, prob0
 
+    # ------------------------------------------------------------------------------------------ masked-LM fill-in
+    @torch.no_grad()
+    def mlm_argmax(self, feats, loc, img_mask, ids, segs, att_mask, rows):
+        """Inference form of the MLM head (cls.predictions, models/vilbert_dialog.py:980-1003) at the flat token indices `rows`
+        (int64 [n], into ids.view(-1)): the encoder, the gather of those rows, the head transform, then the arg-max over the
+        vocabulary of the tied decoder's logits -> (idx [n] int64, val [n] fp32), equal logits to the smaller token id.  No tape,
+        no dropout.  bf16 engine: the product and the arg-max are one kernel pair (gstvd_vocab_argmax), the [n, vocab] logits
+        never exist; fp32 engine (or a width that kernel does not tile): the GEMM into [n, Vp] fp32 and gstvd_rows_argmax.
+        n == 0: the encoder does not run either, two empty tensors come back."""
+        if not self.enc_only:
+            raise GstvdError("mlm_argmax belongs to the encoder-only engine of an enc_only VisualDialogEncoder")
+        dev = ids.device
+        rows = rows.to(dev, torch.int64).contiguous().view(-1)
+        n = rows.numel()
+        if n == 0:
+            return torch.empty(0, dtype=torch.int64, device=dev), torch.empty(0, dtype=torch.float32, device=dev)
+        self._begin(dev, False, inference=True)
+        dummy = ids.new_zeros(ids.shape[0], 1)
+        I = self._inputs(feats, loc, img_mask, ids, segs, att_mask, dummy, None)
+        xt, xv = self.encoder(I)
+        c = self.enc_cfg
+        prev_scope, ops.Profiler.scope = ops.Profiler.scope, "head.mlm"
+        try:
+            y = self._head_transform(self._gathered(xt, rows, n), "mlm", c.hidden_size)
+            w, b, V = self.W["mlm.dec.w"], self.Pv["mlm.b"], c.vocab_size
+            out = None
+            if self.adt == torch.bfloat16:
+                ws = self.arena.alloc(ops.vocab_argmax_ws_bytes(n, V), torch.uint8)
+                out = ops.vocab_argmax_fused(y.t, w, b, V, n=n, ws=ws)
+            if out is None:
+                out = ops.vocab_argmax(y.t, w, b, V, n=n, logits=self.buf(n, self.flat.Vp, torch.float32), fused=False)
+        finally:
+            ops.Profiler.scope = prev_scope
+        self.last = dict(enc_t=xt, enc_v=xv, token_rows=rows)
+        return out
+
 
 class _DiscFn(torch.autograd.Function):
     """The counterpart of engine._StepFn for Engine.disc_step: hands out the three losses, receives their three upstream gradients

@@ -335,6 +335,19 @@ class VisualDialogEncoder(nn.Module):
         self._check_disc_inference()
         return self.engine.nsp_scores(image_feat, image_loc, image_attention_mask, input_ids, token_type_ids, attention_mask)
 
+    def predict_masked(self, input_ids, image_feat, image_loc, token_type_ids=None, attention_mask=None, image_attention_mask=None,
+                       rows=None, mask_token_id=103):
+        """enc_only_a, eval mode: the arg-max token of the model's own tied MLM head (cls.predictions) at the token positions
+        `rows` -> (token ids [n] int64, their logits [n] fp32), in the order of `rows`; equal logits go to the smaller id.
+        `rows`: flat indices into input_ids.view(-1) (int64, ascending), from a caller that has the ids on the host; None: the
+        positions equal to `mask_token_id`, taken from the device tensor with `nonzero` (one host synchronisation), the
+        convention of `token_rows` in forward.  No position: two empty tensors, nothing is launched for the head.  On the
+        two-stream model this is the visually grounded fill-in; on a text-only config (mlm.MaskedLMFiller) BertForMaskedLM's."""
+        self._check_disc_inference()
+        if rows is None:
+            rows = (input_ids.reshape(-1) == int(mask_token_id)).nonzero().view(-1)
+        return self.engine.mlm_argmax(image_feat, image_loc, image_attention_mask, input_ids, token_type_ids, attention_mask, rows)
+
     def forward(self, input_ids, image_feat, image_loc, sep_indices=None, token_type_ids=None, attention_mask=None,
                 masked_lm_labels=None, next_sentence_label=None, image_attention_mask=None, image_label=None,
                 image_target=None, token_rows=None, region_rows=None):

@@ -1153,6 +1153,83 @@ def rows_scatter(src, idx, dst, accumulate, M=None):
     return dst
 
 
+def _argmax_out(who, n, device, idx, val):
+    idx = torch.empty(n, dtype=torch.int64, device=device) if idx is None else idx
+    val = torch.empty(n, dtype=torch.float32, device=device) if val is None else val
+    if (idx.dtype != torch.int64 or val.dtype != torch.float32 or idx.numel() < n or val.numel() < n
+            or not idx.is_contiguous() or not val.is_contiguous()):
+        raise L.GstvdError("%s: idx (int64) and val (fp32) must be contiguous vectors of at least %d entries" % (who, n))
+    return idx, val
+
+
+def rows_argmax(logits, V, n=None, idx=None, val=None):
+    """(idx [n] int64, val [n] fp32): per row of logits [n, ld >= V] (fp32 or bf16) the largest of columns 0..V-1 and its column,
+    equal values to the smaller column (gstvd_rows_argmax).  n == 0: nothing is launched."""
+    lib = L.load()
+    n = logits.shape[0] if n is None else n
+    if logits.dim() != 2 or logits.stride(1) != 1 or logits.shape[1] < V or logits.shape[0] < n:
+        raise L.GstvdError("rows_argmax: logits must be [>= %d, >= %d] with dense rows" % (n, V))
+    idx, val = _argmax_out("rows_argmax", n, logits.device, idx, val)
+    if n == 0:
+        return idx[:0], val[:0]
+    e0 = _prof_begin()
+    L.check("gstvd_rows_argmax", lib.gstvd_rows_argmax(_p(logits), logits.stride(0), n, V, dt(logits), _p(idx), _p(val), _stream()))
+    _prof_end(e0, "rows_argmax", 0.0, float(n) * V * logits.element_size(), (n, V))
+    return idx[:n], val[:n]
+
+
+def vocab_argmax_ws_bytes(n, V):
+    return int(L.load().gstvd_vocab_argmax_ws_bytes(n, V))
+
+
+def vocab_argmax_fused(x, w, bias, V, n=None, idx=None, val=None, ws=None):
+    """The fused form alone (gstvd_vocab_argmax): x [n, H] bf16, w [>= V, H] bf16, bias fp32 [>= V] -> (idx, val), or None when the
+    library answers GSTVD_E_UNSUPPORTED (dtype, H) -- the caller then takes the GEMM + rows_argmax route.  `ws`: a uint8 workspace
+    of at least vocab_argmax_ws_bytes(n, V) bytes (None: allocated here)."""
+    lib = L.load()
+    n = x.shape[0] if n is None else n
+    H = x.shape[1]
+    if w.shape[1] != H or w.shape[0] < V or bias.numel() < V or bias.dtype != torch.float32 or x.stride(1) != 1 or w.stride(1) != 1:
+        raise L.GstvdError("vocab_argmax: x [n, H], w [>= V, H] with dense rows and an fp32 bias of >= V entries are needed")
+    if x.dtype != torch.bfloat16 or w.dtype != torch.bfloat16:
+        return None
+    idx, val = _argmax_out("vocab_argmax", n, x.device, idx, val)
+    if n == 0:
+        return idx[:0], val[:0]
+    need = vocab_argmax_ws_bytes(n, V)
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+    e0 = _prof_begin()
+    rc = lib.gstvd_vocab_argmax(_p(x), x.stride(0), _p(w), w.stride(0), _p(bias), n, V, H, dt(x), _p(ws), ws.numel() * ws.element_size(),
+                                _p(idx), _p(val), _stream())
+    if rc == -5:            # GSTVD_E_UNSUPPORTED: not an error, the other route exists
+        return None
+    L.check("gstvd_vocab_argmax", rc)
+    _prof_end(e0, "vocab_argmax", 2.0 * n * V * H, float(V) * H * 2, (n, V, H))
+    return idx[:n], val[:n]
+
+
+def vocab_argmax(x, w, bias, V, n=None, logits=None, ws=None, fused=True):
+    """Arg-max over v < V of x . w[v] + bias[v] -> (idx [n] int64, val [n] fp32), ties to the smaller v.  bf16 operands with a
+    width the fused kernel tiles: gstvd_vocab_argmax, no [n, V] buffer.  Anything else (fp32 operands: the fp32-precision path),
+    or `fused` False (measurements): gstvd_gemm into `logits` ([n, >= round_up(V, 4)] fp32; None: allocated here) and
+    gstvd_rows_argmax.  Both are HIP kernels of this library; n == 0 launches nothing."""
+    n = x.shape[0] if n is None else n
+    if n == 0:
+        return (torch.empty(0, dtype=torch.int64, device=x.device), torch.empty(0, dtype=torch.float32, device=x.device))
+    if fused:
+        out = vocab_argmax_fused(x, w, bias, V, n=n, ws=ws)
+        if out is not None:
+            return out
+    N = (V + 3) // 4 * 4                    # gstvd_gemm writes whole 4-column groups; rows_argmax never reads columns >= V
+    if w.shape[0] < N or bias.numel() < N:
+        raise L.GstvdError("vocab_argmax: the GEMM route needs the table and the bias padded to %d rows (a multiple of 4)" % N)
+    if logits is None:
+        logits = torch.empty(n, N, dtype=torch.float32, device=x.device)
+    gemm(x, w, logits, n, N, x.shape[1], bias=bias)
+    return rows_argmax(logits, V, n=n)
+
+
 def rows_mul_(x, a, M, N):
     """x[:M, :N] *= a[:M, :N] in place (gstvd_rows_mul)."""
     lib = L.load()

@@ -585,6 +585,28 @@ typedef struct {
 } gstvd_dialog_rows_t;
 int gstvd_dialog_rows(const gstvd_dialog_rows_t* a, gstvd_stream_t s);
 
+/* ---- vocabulary arg-max of the masked-LM fill-in (utils/text_attack.py:30-56; entry points added, no signature changed: ABI
+ * stays 9).  One total order in both forms: the larger value wins, equal values go to the SMALLER column.  Inputs are assumed
+ * finite: a NaN never wins, and a row without a single finite-or-infinite winner reports column 0 with value -inf.
+ *
+ * rows_argmax: logits [n, ld >= V] (GSTVD_F32 or GSTVD_BF16) -> idx[r] = arg-max over columns 0..V-1 (int64), val[r] its value
+ * (fp32).  Columns V..ld-1 are never read.  n >= 1 (a zero-row launch is the caller's to skip).
+ *
+ * vocab_argmax: the tied decoder's product fused in.  X [n, ldx >= H] bf16, W [>= V, ldw >= H] bf16 row-major (one table row per
+ * vocabulary entry, the "NT" form), bias fp32 [>= V]:
+ *     z[r, v] = (sum_k x[r, k] * w[v, k], accumulated in fp32) + bias[v] in fp32;   idx[r], val[r] as above over v = 0..V-1.
+ * The [n, V] logits are never stored: a first launch of MFMA tiles (64 rows x 64 vocabulary columns) leaves one (value, column)
+ * pair per row and tile in `ws` ([n, ceil(V / 64)] pairs of 8 bytes, gstvd_vocab_argmax_ws_bytes(n, V) bytes, 8-byte aligned), a
+ * second launch reduces a row's pairs.  No atomics: the result is deterministic.  Table rows and bias entries at or beyond V are
+ * never read.  GSTVD_E_UNSUPPORTED for a dtype other than GSTVD_BF16, an H that is no multiple of 32, n > 2^20 or V > 2^30: the
+ * caller then runs gstvd_gemm into a [n, >= V] buffer and gstvd_rows_argmax (also the fp32-precision path).  ldx, ldw multiples of
+ * 8 and X, W 16-byte aligned (GSTVD_E_ALIGN); ws_bytes below the helper's answer, n < 1, V < 1: GSTVD_E_SHAPE. */
+int gstvd_rows_argmax(const void* logits, int64_t ld, int64_t n, int64_t V, int32_t dtype, int64_t* idx, float* val,
+                      gstvd_stream_t s);
+int64_t gstvd_vocab_argmax_ws_bytes(int64_t n, int64_t V);
+int gstvd_vocab_argmax(const void* X, int64_t ldx, const void* W, int64_t ldw, const float* bias, int64_t n, int64_t V, int64_t H,
+                       int32_t dtype, void* ws, int64_t ws_bytes, int64_t* idx, float* val, gstvd_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
