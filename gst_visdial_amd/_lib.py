@@ -169,6 +169,7 @@ SIGNATURES = {
     "gstvd_attn_bwd": (_i32, [C.POINTER(AttnDesc), _vp]),
     "gstvd_ln_kernel_name": (_i32, [_vp, _i32, C.c_char_p, _i32]),
     "gstvd_attn_kernel_name": (_i32, [C.POINTER(AttnDesc), _i32, C.c_char_p, _i32]),
+    "gstvd_attn_probs": (_i32, [C.POINTER(AttnDesc), _vp, _i32, _vp]),
     "gstvd_ce_fwd": (_i32, [_vp, _i64, _vp, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp]),
     "gstvd_ce_bwd": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i64, _i32, _vp, _i64, _vp]),
     "gstvd_ce_bwd_rows": (_i32, [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp, _i64, _vp]),

@@ -27,7 +27,7 @@ import weakref
 
 import torch
 
-from . import ops
+from . import attn_maps, ops
 from .config import encoder_schedule
 from .engine_decode import DecodeMixin
 from .engine_disc import DiscMixin, _DiscFn       # noqa: F401  (_DiscFn: importable from here as before)
@@ -84,6 +84,7 @@ class Engine(DecodeMixin, DiscMixin):
         self.pipe = None               # BackwardPipeline (pipeline.py): slice-wise wgrad / all-reduce / AdamW on the aux stream
         self.tape, self.rec = [], False
         self.accumulate, self.written = False, set()
+        self._maps = None               # attn_maps.MapRequest while attention maps are being captured (attn_maps.capture)
         self._inputs_only, self._io = False, False     # inputs_only(): asked for by the caller / in force during the running replay
         self.stats = {}
         self._validate = True
@@ -590,6 +591,10 @@ class Engine(DecodeMixin, DiscMixin):
                           site=self.site(label, p, "attn", (Bn, nh, Lq, (Lk + 3) // 4 * 4), Lk=Lk), rng=self.rng,
                           kv_group=kv_group, kv_bstride=kv_bstride, drop_bits=bits)
         ops.attn_fwd(a)
+        if self._maps is not None and label in self._maps.out:
+            # a selected site of an attention-map request: the probabilities of the descriptor just launched, on the site's stream
+            ops.attn_probs(a, self._maps.out[label], self._maps.head_mean)
+            self._maps.pending.discard(label)
         o.req = qa.req or ka.req or va.req
         self.push(lambda: self._attn_bwd(a, q, k, v, o, Bn, nh, Lq, Hh))
         return o
@@ -816,8 +821,22 @@ class Engine(DecodeMixin, DiscMixin):
         I["feats_grad"] = bool(feats.requires_grad and torch.is_grad_enabled())
         return I
 
-    def _begin(self, device, record, inference=False):
-        """Start of every engine call.  `inference`: dropout off whatever the module's mode (the RNG still advances with it)."""
+    def _refuse_maps(self, what):
+        if self._maps is not None:
+            raise GstvdError("%s under an attention-map request: %s" % (what, attn_maps.ALLOWED))
+
+    def _begin(self, device, record, inference=False, maps_ok=False):
+        """Start of every engine call.  `inference`: dropout off whatever the module's mode (the RNG still advances with it).
+        `maps_ok`: the call is one that serves an attention-map request (eval-mode forward, the encoder alone)."""
+        if self._maps is not None:
+            if not maps_ok:
+                self._refuse_maps("this engine call")
+            if self.model.training or "train" in str(self.model.params.get("mode", "")):
+                self._refuse_maps("a module in training state or a 'train' mode")
+            if record:
+                self._refuse_maps("a forward that records its backward (wrap the call in torch.no_grad())")
+            if torch.cuda.is_current_stream_capturing():
+                self._refuse_maps("a stream capture (the forward of a request is issued eagerly)")
         self.prepare(device)
         self._last_decode = None          # the arena is rewound: a previous decode call's encoder states are about to be overwritten
         self.arena.reset()
@@ -853,7 +872,7 @@ class Engine(DecodeMixin, DiscMixin):
     def step(self, feats, loc, img_mask, ids, segs, att_mask, dec_ids, dec_mask, labels, loss_reduction=True):
         """EncoderDecoderModel.forward, train/eval branch -> (loss, logits)."""
         record = torch.is_grad_enabled()
-        self._begin(ids.device, record)
+        self._begin(ids.device, record, maps_ok=True)
         if labels is None:
             labels = self._shift_labels(dec_ids)
         I = self._inputs(feats, loc, img_mask, ids, segs, att_mask, dec_ids, dec_mask)
@@ -997,6 +1016,7 @@ class Engine(DecodeMixin, DiscMixin):
         [round, candidate].  Returns score[E*group] = sum_u [tgt != 0] log softmax(logits)[u, tgt], tgt = ids shifted left;
         the decoder input is the eos->pad masked copy, as visual_dialog_decoder.py:53-57 makes it."""
         dc = self.dec_cfg
+        self._refuse_maps("score_candidates")
         E, rows = ids.shape[0], dec_ids.shape[0]
         if rows != E * group:
             raise GstvdError("score_candidates: %d decoder rows for %d encoder rows x %d candidates" % (rows, E, group))
@@ -1041,7 +1061,7 @@ def _owner_engine(module, kind):
 def standalone_encoder_forward(module, input_ids, image_feat, image_loc, token_type_ids, attention_mask, image_attention_mask):
     eng = _owner_engine(module, "VisualDialogEncoder")
     with torch.no_grad():
-        eng._begin(input_ids.device, False)
+        eng._begin(input_ids.device, False, maps_ok=True)
         dummy = input_ids.new_zeros(input_ids.shape[0], 1)
         I = eng._inputs(image_feat, image_loc, image_attention_mask, input_ids, token_type_ids, attention_mask, dummy, None)
         xt, xv = eng.encoder(I)
@@ -1074,3 +1094,30 @@ def standalone_decoder_forward(module, dec_ids, attention_mask, enc_hidden, enc_
         y, logits = eng.decoder(enc, I)
         loss, lv, _ = eng._ce(logits, labels, Bn, U, loss_reduction)
         return loss.clone(), lv.float()
+
+
+def encoder_attention_maps(eng, input_ids, image_feat, image_loc, token_type_ids, attention_mask, image_attention_mask, select, heads):
+    """VisualDialogEncoder.attention_maps on engine `eng` (the module's own encoder-only engine, or the engine of the
+    EncoderDecoderModel it belongs to): the two-stream encoder alone, eagerly, with the selected maps -> attn_maps.AttentionMaps."""
+    layers = attn_maps.parse_select(select, attn_maps.layer_counts(eng.enc_cfg), attn_maps.ENCODER_KINDS)
+    req = attn_maps.MapRequest(layers, attn_maps.parse_heads(heads))
+    req.alloc(eng.enc_cfg, None, input_ids.shape[0], input_ids.shape[1], image_feat.shape[1], 0, input_ids.device)
+    with torch.no_grad(), attn_maps.capture(eng, req):
+        eng._begin(input_ids.device, False, inference=True, maps_ok=True)
+        dummy = input_ids.new_zeros(input_ids.shape[0], 1)
+        I = eng._inputs(image_feat, image_loc, image_attention_mask, input_ids, token_type_ids, attention_mask, dummy, None)
+        eng.encoder(I)                    # (its join before VLFusion orders the vision stream's map writes behind the caller's stream)
+    req.check_complete()
+    return req.encoder_maps()
+
+
+def model_attention_maps(eng, feats, loc, img_mask, ids, segs, att_mask, dec_ids, dec_mask, labels, loss_reduction, select, heads):
+    """EncoderDecoderModel.attention_maps: the eval-mode teacher-forced forward, eagerly, with the selected maps ->
+    ((loss, logits), attn_maps.ModelAttentionMaps)."""
+    layers = attn_maps.parse_select(select, attn_maps.layer_counts(eng.enc_cfg, eng.dec_cfg))
+    req = attn_maps.MapRequest(layers, attn_maps.parse_heads(heads))
+    req.alloc(eng.enc_cfg, eng.dec_cfg, ids.shape[0], ids.shape[1], feats.shape[1], dec_ids.shape[1], ids.device)
+    with torch.no_grad(), attn_maps.capture(eng, req):
+        out = eng.step(feats, loc, img_mask, ids, segs, att_mask, dec_ids, dec_mask, labels, loss_reduction)
+    req.check_complete()
+    return out, req.model_maps()

@@ -176,6 +176,7 @@ class DecodeMixin(object):
         Token t is drawn by inverse CDF from uniforms[t] ([max_seq_len, B] in (0, 1); drawn from torch's default generator when
         the caller passes none) instead of torch.multinomial (whose stream is device specific) -- the same rule the oracle
         applies to the reference, so sampled ids can be compared under real sampling."""
+        self._refuse_maps("sample")
         from . import decoding
         if _.get("num_beams") is not None and int(_["num_beams"]) > 1:
             raise GstvdError("sample() draws one answer per row; num_beams = %d is beam search: call beam_search(...) or "
@@ -324,6 +325,7 @@ class DecodeMixin(object):
         (gstvd_beam_step) and cache reorder (gstvd_beam_reorder) at every position.  The back-trace and the final ordering are
         sync-free torch index work (decoding.beam_backtrace / beam_finalize).  A beam call leaves no decode state behind:
         `rescore_sampled` after it raises its "no decode state" error."""
+        self._refuse_maps("beam_search")
         from . import decoding
         dc = self.dec_cfg
         K = int(num_beams)
@@ -432,6 +434,7 @@ class DecodeMixin(object):
         hipGraphs keyed by shapes, S and the sampling settings.  One library call per token more than the decoder stack's, as in
         `sample`.  The encoder side of the call stays valid for the B best answers: `rescore_sampled(best)` works as after
         `sample` (encoder states and cross K/V have B rows)."""
+        self._refuse_maps("sample_ranked")
         from . import decoding
         dc = self.dec_cfg
         S = int(num_samples)

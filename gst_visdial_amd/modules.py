@@ -348,6 +348,23 @@ class VisualDialogEncoder(nn.Module):
             rows = (input_ids.reshape(-1) == int(mask_token_id)).nonzero().view(-1)
         return self.engine.mlm_argmax(image_feat, image_loc, image_attention_mask, input_ids, token_type_ids, attention_mask, rows)
 
+    def attention_maps(self, input_ids, image_feat, image_loc, token_type_ids=None, attention_mask=None, image_attention_mask=None,
+                       select=None, heads="all"):
+        """The softmax probabilities of the encoder's attention sites, what the reference's BertModel returns under
+        output_all_attention_masks=True (models/vilbert_dialog.py:806-912; the fifth output of the enc_only_a eval branch, :1519)
+        -> attn_maps.AttentionMaps(t, v, c, layers): t[i] [B, nh, T, T], v[i] [B, nhv, R, R], c[i] = (probs1 [B, nhb, T, R] text
+        queries over the regions, probs2 [B, nhb, R, T] region queries over the tokens), fp32 on the device.  `select`: None (every
+        site) or a dict kind -> "all" / iterable of layer indices over "t", "v", "c"; `heads`: "all" or "mean" (the mean over the
+        heads, no head dimension).  Eval only; the encoder runs eagerly, on the module's own engine (enc_only_a) or on the engine
+        of the EncoderDecoderModel it belongs to."""
+        from .engine import encoder_attention_maps, _owner_engine
+        if self.model_arch == "enc_only_a":
+            eng = self.engine
+        else:
+            eng = _owner_engine(self, "VisualDialogEncoder")
+        return encoder_attention_maps(eng, input_ids, image_feat, image_loc, token_type_ids, attention_mask, image_attention_mask,
+                                      select, heads)
+
     def forward(self, input_ids, image_feat, image_loc, sep_indices=None, token_type_ids=None, attention_mask=None,
                 masked_lm_labels=None, next_sentence_label=None, image_attention_mask=None, image_label=None,
                 image_target=None, token_rows=None, region_rows=None):
@@ -484,6 +501,24 @@ class EncoderDecoderModel(nn.Module):
                                          enc_attention_mask, dec_input_ids, num_samples=int(num_samples),
                                          length_penalty=float(length_penalty), temperature=temperature, top_k=top_k, top_p=top_p,
                                          ngram_blocking_size=ngram_blocking_size, max_seq_len=int(max_seq_len), uniforms=uniforms)
+
+    def attention_maps(self, enc_image_features=None, enc_image_spatials=None, enc_image_mask=None, enc_image_target=None,
+                       enc_image_label=None, enc_next_sentence_labels=None, enc_input_ids=None, enc_segments=None,
+                       enc_sep_indices=None, enc_mlm_labels=None, enc_attention_mask=None, dec_input_ids=None,
+                       dec_attention_mask=None, dec_labels=None, select=None, heads="all"):
+        """The eval-mode teacher-forced forward with its attention maps -> ((loss, logits), maps): (loss, logits) as `forward`
+        returns them, maps an attn_maps.ModelAttentionMaps -- maps.encoder as VisualDialogEncoder.attention_maps returns it,
+        maps.decoder_self[i] [B, nh, U, U], maps.decoder_cross[i] [B, nh, U, R + T] (regions first), maps.layers.  `select`: None
+        (every site) or a dict over "t", "v", "c", "decoder_self", "decoder_cross" -> "all" / iterable of layer indices (a missing
+        key: none); `heads`: "all" or "mean".  Needs an 'eval' mode and .eval(); issued eagerly, without autograd."""
+        from ._lib import GstvdError
+        from . import attn_maps
+        from .engine import model_attention_maps
+        mode = self.params["mode"]
+        if "train" in mode or "eval" not in mode or self.training:
+            raise GstvdError("attention_maps(mode=%r, training=%s): %s" % (mode, self.training, attn_maps.ALLOWED))
+        return model_attention_maps(self.engine, enc_image_features, enc_image_spatials, enc_image_mask, enc_input_ids, enc_segments,
+                                    enc_attention_mask, dec_input_ids, dec_attention_mask, dec_labels, True, select, heads)
 
     def forward(self, enc_image_features=None, enc_image_spatials=None, enc_image_mask=None, enc_image_target=None,
                 enc_image_label=None, enc_next_sentence_labels=None, enc_input_ids=None, enc_segments=None,

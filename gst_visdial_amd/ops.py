@@ -734,6 +734,19 @@ def attn_fwd(a):
     _prof_end(e0, "attn_fwd_d%d" % a.d, 4.0 * a.B * a.nh * a.Lq * a.Lk * a.d, 0.0, (a.B, a.nh, a.Lq, a.Lk))
 
 
+def attn_probs(a, out, head_mean=False):
+    """The attention map of descriptor `a` (gstvd_attn_probs): softmax(scale * Q K^T + mask) in fp32 into `out`, a contiguous
+    fp32 tensor of B * nh * Lq * Lk elements, or of B * Lq * Lk with `head_mean` (the mean over the heads).  Reads Q, K and the
+    key mask only; a descriptor with dropout or batch strides is refused."""
+    n = a.B * (1 if head_mean else a.nh) * a.Lq * a.Lk
+    if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != n:
+        raise L.GstvdError("attn_probs: `out` must be a contiguous fp32 tensor of %d elements" % n)
+    lib = L.load()
+    e0 = _prof_begin()
+    L.check("gstvd_attn_probs", lib.gstvd_attn_probs(C.byref(a), _p(out), int(bool(head_mean)), _stream()))
+    _prof_end(e0, "attn_probs_d%d" % a.d, 2.0 * 2.0 * a.B * a.nh * a.Lq * a.Lk * a.d, 4.0 * n, (a.B, a.nh, a.Lq, a.Lk))
+
+
 def attn_bwd(a, dO, dQ, dK, dV, delta, lddo=None, lddq=None, lddk=None, lddv=None):
     lib = L.load()
     a.dO, a.dQ, a.dK, a.dV, a.delta = _p(dO), _p(dQ), _p(dK), _p(dV), _p(delta)

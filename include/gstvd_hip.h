@@ -242,6 +242,14 @@ int gstvd_attn_bwd(const gstvd_attn_t* a, gstvd_stream_t s);  /* dQ (+delta) the
  * launched.  The two-part backward's answer carries its block order: "<symbol> dq_first=0|1".  GSTVD_E_SHAPE when buf_len is
  * too small for the answer. */
 int gstvd_attn_kernel_name(const gstvd_attn_t* a, int32_t bwd, char* buf, int32_t buf_len);
+/* P = softmax_j(scale * q_i . k_j + mask(b, i, j)) in fp32, the probabilities gstvd_attn_fwd applies for the same descriptor:
+ * p = __expf(s - m) times the correctly rounded 1 / sum (row maximum m and row sum taken by this call; one multiply, not a division),
+ * with dropout off.  mask() as defined above gstvd_attn_t: key_mask, causal, mask_neg, kv_group.  Reads Q, K, key_mask only:
+ * V, O, LSE, rng are not touched; the call does not depend on an earlier launch.  head_mean == 0: P [B, nh, Lq, Lk] contiguous;
+ * head_mean != 0: P [B, Lq, Lk] = (p_0 + p_1 + ... + p_{nh-1}) * (1.0f / nh), heads added in ascending order in fp32 (nh <= 16).
+ * Every element of P is written exactly once (a masked entry is written as the value the formula gives, 0.0f unless the whole row
+ * is masked).  dropout_p != 0, q_bstride != 0 or kv_bstride != 0: GSTVD_E_UNSUPPORTED.  d in {32, 64, 128}, bf16 and fp32. */
+int gstvd_attn_probs(const gstvd_attn_t* a, float* P, int32_t head_mean, gstvd_stream_t s);
 
 /* ---- LM head loss: CrossEntropyLoss(ignore_index) of visual_dialog_decoder.py:70-77 ----------
  * logits [M, ldl >= V]; row_loss [M] (0 for ignored rows); stats (fp32[3], written by the call):
