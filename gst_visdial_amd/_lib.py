@@ -167,6 +167,7 @@ SIGNATURES = {
     "gstvd_locgrad": (_i32, [_vp, _i64, _vp, _i64, _i64, _i32, _vp, _i32, _vp]),
     "gstvd_attn_fwd": (_i32, [C.POINTER(AttnDesc), _vp]),
     "gstvd_attn_bwd": (_i32, [C.POINTER(AttnDesc), _vp]),
+    "gstvd_attn_group_bwd": (_i32, [C.POINTER(AttnDesc), _vp]),
     "gstvd_ln_kernel_name": (_i32, [_vp, _i32, C.c_char_p, _i32]),
     "gstvd_attn_kernel_name": (_i32, [C.POINTER(AttnDesc), _i32, C.c_char_p, _i32]),
     "gstvd_attn_probs": (_i32, [C.POINTER(AttnDesc), _vp, _i32, _vp]),
@@ -175,6 +176,7 @@ SIGNATURES = {
     "gstvd_ce_bwd_rows": (_i32, [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp, _i64, _vp]),
     "gstvd_fgsm_step": (_i32, [_vp, _vp, _f32, _vp, _i64, _vp]),
     "gstvd_answer_scores": (_i32, [_vp, _i64, _vp, _vp, _i64, _i64, _i32, _vp, _vp]),
+    "gstvd_rank_loss": (_i32, [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _f32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gstvd_sample_topk": (_i32, [C.POINTER(SampleDesc), _vp]),
     "gstvd_sample_topk_scored": (_i32, [C.POINTER(SampleDesc), _vp, _i64, _vp]),
     "gstvd_vl_split": (_i32, [_vp, _i64, _i64, _i64, _i64, _i32, _vp, _vp, _f32, _u32, _u32, _vp, _vp]),

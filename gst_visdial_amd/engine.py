@@ -31,6 +31,7 @@ from . import attn_maps, ops
 from .config import encoder_schedule
 from .engine_decode import DecodeMixin
 from .engine_disc import DiscMixin, _DiscFn       # noqa: F401  (_DiscFn: importable from here as before)
+from .engine_rank import RankMixin, _RankFn       # noqa: F401
 from .storage import Act, Arena, FlatParams
 from ._lib import GstvdError, EPI_GELU, EPI_DGELU, LN_RESID, LN_EMBED, LN_IMAGE
 
@@ -52,7 +53,7 @@ def device_streams(device):
     return _DEVICE_STREAMS[key]
 
 
-class Engine(DecodeMixin, DiscMixin):
+class Engine(DecodeMixin, DiscMixin, RankMixin):
     def __init__(self, model):
         # weak: the model owns the engine, not the other way round -- no reference cycle, so dropping the model frees the
         # flat buffers, the arena and any captured decode sessions by reference counting, not at some later GC pass
@@ -608,6 +609,9 @@ class Engine(DecodeMixin, DiscMixin):
                 act.g = self.buf(act.M, act.N)
             gs.append(act.g[:, c:c + Hh])
         delta = self.vec(Bn * nh * Lq)
+        if a.kv_group > 1:      # rank_step's cross-attention: the query rows of a group share K / V, whose gradients are the group's sums
+            ops.attn_group_bwd(a, o.g, gs[0], gs[1], gs[2], delta)
+            return
         ops.attn_bwd(a, o.g, gs[0], gs[1], gs[2], delta)
 
     # ------------------------------------------------------------------------------------------ blocks

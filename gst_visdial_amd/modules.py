@@ -469,6 +469,16 @@ class EncoderDecoderModel(nn.Module):
         return self.engine.score_candidates(enc_image_features, enc_image_spatials, enc_image_mask, enc_input_ids,
                                             enc_segments, enc_attention_mask, dec_input_ids, dec_attention_mask, num_options)
 
+    def rank_loss(self, enc_image_features=None, enc_image_spatials=None, enc_image_mask=None, enc_input_ids=None, enc_segments=None,
+                  enc_attention_mask=None, dec_input_ids=None, dec_attention_mask=None, relevance=None, num_options=None,
+                  temperature=1.0):
+        """Listwise candidate training (Engine.rank_step; rank_train.forward_rank): encoder tensors with one row per round,
+        decoder tensors and `relevance` with num_options rows / values per round -> (loss, scores [rounds, num_options]).  The
+        loss is differentiable like `forward`'s: `loss.backward()` fills `.grad` of every live parameter."""
+        return self.engine.rank_step(enc_image_features, enc_image_spatials, enc_image_mask, enc_input_ids, enc_segments,
+                                     enc_attention_mask, dec_input_ids, dec_attention_mask, relevance, int(num_options),
+                                     temperature=temperature)
+
     def beam_search(self, enc_image_features=None, enc_image_spatials=None, enc_image_mask=None, enc_input_ids=None,
                     enc_segments=None, enc_attention_mask=None, dec_input_ids=None, num_beams=5, length_penalty=1.0,
                     ngram_blocking_size=0, max_seq_len=18, **_):

@@ -759,6 +759,20 @@ def attn_bwd(a, dO, dQ, dK, dV, delta, lddo=None, lddq=None, lddk=None, lddv=Non
     _prof_end(e0, "attn_bwd_d%d" % a.d, 14.0 * a.B * a.nh * a.Lq * a.Lk * a.d, 0.0, (a.B, a.nh, a.Lq, a.Lk))
 
 
+def attn_group_bwd(a, dO, dQ, dK, dV, delta, lddo=None, lddq=None, lddk=None, lddv=None):
+    """The backward of a grouped launch (gstvd_attn_group_bwd): `a` as attn_fwd left it with kv_group = G; dQ, delta per query
+    row, dK / dV [B / G * Lk rows] written (not accumulated) as the sums over each group's query rows."""
+    lib = L.load()
+    a.dO, a.dQ, a.dK, a.dV, a.delta = _p(dO), _p(dQ), _p(dK), _p(dV), _p(delta)
+    a.lddo = dO.stride(-2) if lddo is None else lddo
+    a.lddq = dQ.stride(-2) if lddq is None else lddq
+    a.lddk = dK.stride(-2) if lddk is None else lddk
+    a.lddv = dV.stride(-2) if lddv is None else lddv
+    e0 = _prof_begin()
+    L.check("gstvd_attn_group_bwd", lib.gstvd_attn_group_bwd(C.byref(a), _stream()))
+    _prof_end(e0, "attn_group_bwd_d%d" % a.d, 14.0 * a.B * a.nh * a.Lq * a.Lk * a.d, 0.0, (a.B, a.nh, a.Lq, a.Lk, a.kv_group))
+
+
 def ce_fwd(logits, labels, M, V, row_loss, lse, stats, ignore_index=0):
     lib = L.load()
     e0 = _prof_begin()
@@ -869,6 +883,23 @@ def answer_scores(logits, lse, dec_ids, rows, U, scores):
     lib = L.load()
     L.check("gstvd_answer_scores", lib.gstvd_answer_scores(_p(logits), logits.stride(-2), _p(lse), _p(dec_ids), rows, U,
                                                            dt(logits), _p(scores), _stream()))
+
+
+def rank_loss(logits, lse, dec_ids, relevance, E, G, U, inv_temperature, scores, p, round_loss, g_tok, stats):
+    """The listwise loss head (gstvd_rank_loss): scores, p [E * G], round_loss [E], g_tok [E * G * U] and stats [3] are written,
+    all contiguous fp32; g_tok is the upstream gradient ce_bwd_rows takes."""
+    lib = L.load()
+    for name, t, n in (("relevance", relevance, E * G), ("scores", scores, E * G), ("p", p, E * G), ("round_loss", round_loss, E),
+                       ("g_tok", g_tok, E * G * U), ("stats", stats, 3), ("lse", lse, E * G * U)):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n:
+            raise L.GstvdError("rank_loss: %s must be a contiguous fp32 tensor of %d elements" % (name, n))
+    if dec_ids.dtype != torch.int64 or not dec_ids.is_contiguous() or dec_ids.numel() != E * G * U:
+        raise L.GstvdError("rank_loss: dec_ids must be a contiguous int64 tensor of %d elements" % (E * G * U))
+    e0 = _prof_begin()
+    L.check("gstvd_rank_loss", lib.gstvd_rank_loss(_p(logits), logits.stride(-2), _p(lse), _p(dec_ids), _p(relevance), E, G, U,
+                                                   float(inv_temperature), dt(logits), _p(scores), _p(p), _p(round_loss), _p(g_tok),
+                                                   _p(stats), _stream()))
+    _prof_end(e0, "rank_loss", 0.0, 0.0, (E, G, U))
 
 
 BEAM_MAX = 8                   # beams per dialog row (gstvd_beam_step: K * K candidates fit one wave)

@@ -242,6 +242,16 @@ int gstvd_attn_bwd(const gstvd_attn_t* a, gstvd_stream_t s);  /* dQ (+delta) the
  * launched.  The two-part backward's answer carries its block order: "<symbol> dq_first=0|1".  GSTVD_E_SHAPE when buf_len is
  * too small for the answer. */
 int gstvd_attn_kernel_name(const gstvd_attn_t* a, int32_t bwd, char* buf, int32_t buf_len);
+/* (entry point added for listwise candidate training, no signature changed: ABI stays 9)
+ * The backward of a GROUPED forward launch, which gstvd_attn_bwd refuses: kv_group = G consecutive query rows share the K, V and
+ * key_mask of row b / G.  Reads the descriptor as gstvd_attn_fwd left it (B query rows, B % G == 0) plus the backward fields.
+ * dQ [B * Lq rows] and delta [B, nh, Lq] are per query row, bit for bit what gstvd_attn_bwd's two-part kernel gives with K, V and
+ * the mask replicated G times.  dK, dV have (B / G) * Lk rows and are WRITTEN, not accumulated: row (e, k) is the sum over the
+ * query rows e * G .. e * G + G - 1, added in ascending order by the one block that owns the key -- no atomics, the same bits
+ * every run.  Dropout: the forward's draws, element index ((b * nh + h) * Lq + q) * round4(Lk) + k with b the query row;
+ * drop_bits is ignored.  causal != 0, q_bstride != 0, kv_bstride != 0 or B % G != 0: GSTVD_E_UNSUPPORTED, nothing is written.
+ * kv_group 0 or 1 is the ungrouped two-part backward.  d in {32, 64, 128}, bf16 and fp32. */
+int gstvd_attn_group_bwd(const gstvd_attn_t* a, gstvd_stream_t s);
 /* P = softmax_j(scale * q_i . k_j + mask(b, i, j)) in fp32, the probabilities gstvd_attn_fwd applies for the same descriptor:
  * p = __expf(s - m) times the correctly rounded 1 / sum (row maximum m and row sum taken by this call; one multiply, not a division),
  * with dropout off.  mask() as defined above gstvd_attn_t: key_mask, causal, mask_neg, kv_group.  Reads Q, K, key_mask only:
@@ -282,6 +292,18 @@ int gstvd_fgsm_step(const float* x, const float* g, float eps, float* out, int64
 /* evaluate_gen.py:94-106: score[m] = sum_u [tgt != 0] * (logits[m,u,tgt] - lse[m,u]) with tgt = ids shifted left */
 int gstvd_answer_scores(const void* logits, int64_t ldl, const float* lse, const int64_t* dec_ids,
                         int64_t rows, int64_t U, int32_t dtype, float* scores, gstvd_stream_t s);
+/* (entry point added for listwise candidate training, no signature changed: ABI stays 9)
+ * Listwise ranking loss over the G answer candidates of each of E dialog rounds, one launch, no host synchronisation.
+ * logits [E*G*U, ldl], lse [E*G*U], dec_ids [E*G, U] as for gstvd_answer_scores; relevance [E*G] fp32, >= 0.
+ *   scores[i]     = gstvd_answer_scores' value, bit for bit
+ *   t             = relevance / sum(relevance) per round; p = softmax over the round of scores * inv_temperature (fp32)
+ *   round_loss[e] = -sum_{t_i > 0} t_i log p_i; a round whose relevance sums to 0 has loss 0, weights 0 and is not counted
+ *   stats         = [sum of round_loss, counted rounds, mean (0 when no round counts)]
+ *   g_tok[i, u]   = -(p_i - t_i) * inv_temperature / counted where dec_ids[i, u + 1] != 0, exactly 0 elsewhere: the upstream
+ *                   gradient of the per-token cross entropies, as gstvd_ce_bwd_rows takes it (d mean loss / d ce[i, u]). */
+int gstvd_rank_loss(const void* logits, int64_t ldl, const float* lse, const int64_t* dec_ids, const float* relevance,
+                    int64_t E, int64_t G, int64_t U, float inv_temperature, int32_t dtype, float* scores, float* p,
+                    float* round_loss, float* g_tok, float* stats, gstvd_stream_t s);
 
 /* One sampling step of the decode loop (models/visual_dialog_model.py:96-108 after the n-gram filter has produced `banned`;
  * utils/decoding_utils.py:4-35 for the top-k rule): z = logits / temperature (banned -> -inf); top_k > 0: z below the k-th
