@@ -1,12 +1,126 @@
-"""Sampling decode of the engine (models/visual_dialog_model.py:74-120, generate.py:183-211): one token per row and step
-through the decoder stack against per-layer K/V caches, the captured hipGraph form of the loop, and the perplexity re-score
-of the sampled answer.  `DecodeMixin` is the decode half of `engine.Engine`; it uses the engine's op helpers and schedule."""
+"""Answer decoding of the engine (models/visual_dialog_model.py:74-120, generate.py:183-211): one token per row and step
+through the decoder stack against per-layer K/V caches, in three modes -- `sample`, `beam_search`, `sample_ranked` -- that run
+through ONE driver (`_decode`: eager first call, then the captured hipGraph form of the loop), and the perplexity re-score of
+the sampled answer.  `DecodeMixin` is the decode half of `engine.Engine`; it uses the engine's op helpers and schedule."""
+import collections
+
 import torch
 
 from . import ops
 from . import _lib as _libmod
 from .storage import Act
 from ._lib import GstvdError, EPI_GELU
+
+
+class _Session(object):
+    """One decode call's state on fixed addresses.  An eager call builds one on the caller's tensors and drops it; a captured one
+    owns clones of the inputs and is kept in `Engine._decode_sessions`.
+      ins            the seven tensors the kernels read: (feats, loc, img_mask, ids, segs, att_mask, dec_ids)
+      bufs           the mode's buffers by name (all time-major): the ids `cur`, the mode's scores, the call's uniforms `u`, the
+                     n-gram history `hist`
+      st             `_decode_plan`'s state: encoder inputs, cross K/V, caches, the arena mark -- what `rescore_sampled` reuses
+      ret            what the mode's loop returned
+      g_enc, g_dec   the captured graphs of the encoder side and of the whole token loop; None on an eager call"""
+
+    def __init__(self, ins, bufs):
+        self.ins, self.bufs, self.st, self.ret, self.g_enc, self.g_dec = ins, bufs, None, None, None, None
+
+    def refresh(self, ins, u=None):
+        for dst, src in zip(self.ins, ins):
+            if dst is not None:
+                dst.copy_(src)
+        if u is not None:
+            self.bufs["u"].copy_(u)
+
+
+# What the three decode modes differ in.  reorder: a second set of self-attention caches (`_decode_plan`); keeps_state: the call
+# leaves `_last_decode` for `rescore_sampled`; buffers(Bn, K, L0, max_seq_len, dev) -> dict of static tensors; hist(h, K) -> the
+# n-gram history of the decoder rows from the B dialogs' `h` (None: the mode bans nothing); loop(engine, one_token, session, L0,
+# max_seq_len, K, P): the whole token loop on the session's buffers, free of host synchronisation -- eager issue and graph capture
+# run this same code.
+_Mode = collections.namedtuple("_Mode", "name reorder keeps_state buffers hist loop")
+
+
+def _sample_buffers(Bn, K, L0, max_seq_len, dev):
+    return dict(cur=torch.zeros(L0 + max_seq_len, Bn, dtype=torch.long, device=dev))      # time-major (see _sampling_step)
+
+
+def _sample_loop(eng, one_token, s, L0, max_seq_len, K, P):
+    """Every decoder position's stack and, from position L0 - 1 on (earlier ones only consume the given prefix), its sampling
+    step: filters, softmax, draw, append.  Returns the last logits."""
+    cur, u, hist = s.bufs["cur"], s.bufs["u"], s.bufs["hist"]
+    cur[:L0] = s.ins[6].t()
+    for t in range(L0 + max_seq_len - 1):
+        logits = one_token(cur[t], t)
+        if t >= L0 - 1:
+            eng._sampling_step(logits, cur, t + 1, hist, P, u[t - (L0 - 1)])
+    return logits
+
+
+def _beam_buffers(Bn, K, L0, max_seq_len, dev):
+    """Static state of a beam call: the time-major id buffer, the ping-pong (score, done) pairs, one parent row per generated
+    position, the step kernel's workspace and the state in front of the first step (s[b,0] = 0, s[b,j>0] = -inf)."""
+    init = torch.full((Bn, K), -float("inf"), dtype=torch.float32, device=dev)
+    init[:, 0] = 0.0
+    return dict(cur=torch.zeros(L0 + max_seq_len, Bn * K, dtype=torch.long, device=dev),
+                score=[torch.zeros(Bn, K, dtype=torch.float32, device=dev) for _ in range(2)],
+                done=[torch.zeros(Bn, K, dtype=torch.int32, device=dev) for _ in range(2)],
+                parent=torch.zeros(max_seq_len, Bn, K, dtype=torch.int32, device=dev),
+                ws=ops.beam_workspace(Bn, K, dev), init=init)
+
+
+def _beam_loop(eng, one_token, s, L0, max_seq_len, K, P):
+    """The prefix positions feed all K rows of a dialog alike; from position L0 - 1 on every token step is followed by the beam
+    step (gstvd_beam_step: token row t + 1 of the id buffer, parents, the other (score, done) pair) and, while another token step
+    follows, by the reorder of the self-attention caches into the OTHER cache set, which the next token step then appends to and
+    reads.  K = 1 keeps one cache set (its only parent is itself).  Returns the index of the final (score, done) pair."""
+    dc, bufs, dec_ids = eng.dec_cfg, s.bufs, s.ins[6]
+    cur, score, done = bufs["cur"], bufs["score"], bufs["done"]
+    Bn = dec_ids.shape[0]
+    cur[:L0] = dec_ids.t()[:, :, None].expand(L0, Bn, K).reshape(L0, Bn * K)
+    score[0].copy_(bufs["init"])
+    done[0].zero_()
+    steps, cset = L0 + max_seq_len - 1, 0
+    H, Umax = dc.hidden_size, s.st["Umax"]
+    for t in range(steps):
+        logits = one_token(cur[t], t, cset)
+        if t < L0 - 1:
+            continue
+        g = t - (L0 - 1)
+        ops.beam_step(logits, score[g & 1], done[g & 1], score[(g + 1) & 1], done[(g + 1) & 1], bufs["parent"][g], cur, t + 1,
+                      bufs["ws"], dc.eos_token_id, dc.pad_token_id)
+        if K > 1 and t + 1 < steps:
+            sets = s.st["QKVc"]
+            ops.beam_reorder([a.t.view(Bn * K, Umax, 3 * H) for a in sets[cset]],
+                             [a.t.view(Bn * K, Umax, 3 * H) for a in sets[1 - cset]], bufs["parent"][g], t, H)
+            cset = 1 - cset
+    return max_seq_len & 1
+
+
+def _ranked_buffers(Bn, S, L0, max_seq_len, dev):
+    return dict(cur=torch.zeros(L0 + max_seq_len, Bn * S, dtype=torch.long, device=dev),
+                lp=torch.zeros(max_seq_len, Bn * S, dtype=torch.float32, device=dev))
+
+
+def _ranked_loop(eng, one_token, s, L0, max_seq_len, S, P):
+    """The prefix goes to all S rows of a dialog alike; from position L0 - 1 on every token step is followed by ONE launch
+    (gstvd_sample_topk_scored) that draws token row t + 1 of the time-major id buffer `cur` and writes the drawn ids'
+    log-probabilities into row t - (L0 - 1) of the time-major buffer `lp`.  Returns the last logits."""
+    cur, lp, u, hist, dec_ids = s.bufs["cur"], s.bufs["lp"], s.bufs["u"], s.bufs["hist"], s.ins[6]
+    Bn = dec_ids.shape[0]
+    cur[:L0] = dec_ids.t()[:, :, None].expand(L0, Bn, S).reshape(L0, Bn * S)
+    for t in range(L0 + max_seq_len - 1):
+        logits = one_token(cur[t], t)
+        if t >= L0 - 1:
+            g = t - (L0 - 1)
+            ops.sample_topk_scored(logits, P["temperature"], P["top_k"], u[g], cur[t + 1], lp[g], None,
+                                   ngram=(hist, cur, t + 1, P["ngram"]) if P["ngram"] > 0 else None, top_p=P["top_p"])
+    return logits
+
+
+_SAMPLE = _Mode("sample", True, True, _sample_buffers, lambda h, K: h, _sample_loop)
+_BEAM = _Mode("beam", True, False, _beam_buffers, None, _beam_loop)
+_RANKED = _Mode("ranked", False, True, _ranked_buffers, lambda h, S: h.repeat_interleave(S, 0), _ranked_loop)
 
 
 class DecodeMixin(object):
@@ -36,12 +150,9 @@ class DecodeMixin(object):
             st["Umax"] = Umax
             # per-layer cache of the fused Q|K|V rows, [B, Umax, 3H]: the QKV GEMM of position t writes its output rows straight
             # into cache[:, t] (row stride Umax*3H), attention reads K / V from the same rows -- no append copies
-            if beams > 1 and reorder:
-                Dn = Bn * beams
-                st["QKVc"] = [[Act(self.buf(Dn * Umax, 3 * H), Dn * Umax, 3 * H) for _ in range(L)] for _ in range(2)]
-            else:
-                Dn = Bn * beams
-                st["QKVc"] = [Act(self.buf(Dn * Umax, 3 * H), Dn * Umax, 3 * H) for _ in range(L)]
+            Dn = Bn * beams
+            sets = [[Act(self.buf(Dn * Umax, 3 * H), Dn * Umax, 3 * H) for _ in range(L)] for _ in range(2 if beams > 1 and reorder else 1)]
+            st["QKVc"] = sets if len(sets) == 2 else sets[0]
             st["mark"] = self.arena.mark()
 
         def one_token(tok, t, cset=0):
@@ -125,41 +236,104 @@ class DecodeMixin(object):
         prob = torch.softmax(last, dim=-1)
         cur[pos] = decoding.draw_from_uniform(prob, u_row).view(-1)
 
-    def _decode_session(self, ins, L0, max_seq_len, P):
-        """hipGraph form of a decode call (generate.py's loop calls sample() with the same shapes and settings batch after
-        batch): static copies of the inputs, one captured graph for `encode` and ONE for the whole token loop -- every decoder
-        position's stack AND its sampling step (filters, softmax, draw, append), so that nothing of the loop is issued from
-        the host at replay (round 1-2 replayed one graph per position and ran ~25 small torch kernels per step eagerly in
-        between: the loop was bound by host issue).
-        Returns (refresh(ins, uniforms), run_encode(), run_tokens(), st, cur, last_logits)."""
-        static = tuple(x.clone() if x is not None else None for x in ins)
-        ids, segs, dec_ids = static[3], static[4], static[6]
-        Bn, dev = ids.shape[0], ids.device
-        steps = L0 + max_seq_len - 1
-        cur = torch.zeros(L0 + max_seq_len, Bn, dtype=torch.long, device=dev)      # time-major (see _sampling_step)
-        u_buf = torch.zeros(max_seq_len, Bn, dtype=torch.float32, device=dev)
-        encode, one_token, st = self._decode_plan(static, L0, max_seq_len)
+    def _decode_issue(self, mode, ins, L0, max_seq_len, K, P, u, static):
+        """Issues one decode call of `mode` on `ins` -> its _Session.  The ONLY function that opens decode captures.
+        static=False: eagerly, on the caller's tensors and uniforms; counts `decode_lib_calls_per_token` over the token loop.
+        static=True: the hipGraph form (generate.py's loop calls with the same shapes and settings batch after batch): clones of
+        the inputs, a static uniform buffer, one captured graph for `encode` (and the n-gram history) and ONE for the whole token
+        loop -- every position's decoder stack AND its tail (sampling step / beam step and cache reorder), so that nothing of the
+        loop is issued from the host at replay (round 1-2 replayed one graph per position and ran ~25 small torch kernels per
+        step eagerly in between: the loop was bound by host issue).  Nothing executes; one garbage collection for both captures,
+        the loop graph in the encoder graph's pool.  Both ways run the same `mode.loop`."""
+        if static:
+            ins = tuple(x.clone() if x is not None else None for x in ins)
+        ids, segs = ins[3], ins[4]
+        s = _Session(ins, mode.buffers(ids.shape[0], K, L0, max_seq_len, ids.device))
+        if u is not None:
+            s.bufs["u"] = torch.zeros_like(u) if static else u
+        encode, one_token, s.st = self._decode_plan(ins, L0, max_seq_len, beams=K, reorder=mode.reorder)
+
+        def head():
+            encode()
+            if mode.hist is not None:
+                s.bufs["hist"] = mode.hist(ids * (segs == 0).long(), K)
+
+        def loop():
+            s.ret = mode.loop(self, one_token, s, L0, max_seq_len, K, P)
+
+        if not static:
+            head()
+            calls0 = _libmod.N_CALLS[0]
+            loop()
+            self.decode_lib_calls_per_token = (_libmod.N_CALLS[0] - calls0) / float(L0 + max_seq_len - 1)
+            return s
         from .graph import capture, gc_quiet
         with gc_quiet():
-            g_enc = torch.cuda.CUDAGraph()
-            with capture(g_enc):
-                encode()
-                hist = ids * (segs == 0).long()
-            g_dec = torch.cuda.CUDAGraph()
-            with capture(g_dec, pool=g_enc.pool(), quiesce=False):
-                cur[:L0] = dec_ids.t()
-                for t in range(steps):
-                    logits = one_token(cur[t], t)
-                    if t >= L0 - 1:
-                        self._sampling_step(logits, cur, t + 1, hist, P, u_buf[t - (L0 - 1)])
+            s.g_enc = torch.cuda.CUDAGraph()
+            with capture(s.g_enc):
+                head()
+            s.g_dec = torch.cuda.CUDAGraph()
+            with capture(s.g_dec, pool=s.g_enc.pool(), quiesce=False):
+                loop()
+        return s
 
-        def refresh(new, uniforms):
-            for dst, src in zip(static, new):
-                if dst is not None:
-                    dst.copy_(src)
-            u_buf.copy_(uniforms)
+    def _decode(self, mode, tensors, max_seq_len, finish, K=1, P=None, key=(), uniforms=None, graph=True):
+        """The driver of `sample`, `beam_search` and `sample_ranked`: K decoder rows per dialog, P the sampling settings (None: the
+        mode draws nothing), `key` what else tells two sessions of the mode apart, `finish(session)` forms the call's results and
+        `self.last` from the session's buffers.  With params['amd_decode_graph'] (default on) and `graph`, the first call with a
+        signature issues eagerly -- which also initialises every lazily built table / attribute / arena chunk -- and is then
+        captured; later calls refresh the session's static tensors and replay its two graphs.  At most four sessions are kept."""
+        feats, loc, img_mask, ids, segs, att_mask, dec_ids = tensors
+        if segs is None:
+            segs = torch.zeros_like(ids)
+        ins = (feats, loc, img_mask, ids, segs, att_mask, dec_ids)
+        L0, Bn, u = dec_ids.shape[1], ids.shape[0], None
+        if P is not None and uniforms is None:
+            # the call's randomness, drawn ONCE from torch's default CUDA generator (eagerly: no generator state inside the
+            # captured graphs); every step then draws by inverse CDF -- the same distribution as the reference's
+            # torch.multinomial (whose stream is device specific anyway), and the same ids from eager issue and graph replay
+            u = torch.rand(max_seq_len, Bn * K, device=ids.device, dtype=torch.float32).clamp_min_(1e-12)
+        elif P is not None:
+            if uniforms.dim() != 2 or uniforms.shape[0] < max_seq_len or uniforms.shape[1] != Bn * K:
+                raise GstvdError("uniforms must be [max_seq_len = %d, decoder rows = %d] (one draw per step and decoder row: batch "
+                                 "times num_samples), got %s" % (max_seq_len, Bn * K, tuple(uniforms.shape)))
+            u = uniforms.to(ids.device, torch.float32)[:max_seq_len].contiguous()
+        sig = ((mode.name, L0, max_seq_len, K, tuple(sorted(P.items())) if P is not None else None) + tuple(key)
+               + tuple((tuple(x.shape), x.dtype) if x is not None else None for x in ins))
+        use_graph = graph and bool(self.model.params.get("amd_decode_graph", True))
+        # parameters edited since the last call (load_state_dict, an optimizer step): the captured graphs read the flat
+        # buffers / bf16 shadow, so bring those up to date OUTSIDE the graphs; a re-materialised buffer drops the sessions
+        self.prepare(ids.device)
+        s = self._decode_sessions.get(sig) if use_graph else None
+        replayed = s is not None
+        if replayed:
+            s.refresh(ins, u)
+            s.g_enc.replay()
+            s.g_dec.replay()
+        else:
+            s = self._decode_issue(mode, ins, L0, max_seq_len, K, P, u, False)
+        out = finish(s)
+        if use_graph and not replayed:
+            if len(self._decode_sessions) >= 4:
+                self._decode_sessions.clear()
+            self._decode_sessions[sig] = self._decode_issue(mode, ins, L0, max_seq_len, K, P, u, True)
+        # (after the capture: capturing runs the Python side of encode() again -- which rewinds the arena bookkeeping and drops
+        # this marker -- but executes nothing, so the eager call's encoder states are still what the arena holds.)  The encoder
+        # side of a sampling call (B rows: cross-attention K/V of all layers, masks) stays valid in the arena until the next
+        # engine call: `rescore_sampled` scores an answer against it without a second encoder pass.  Beam search leaves none:
+        # its K rows per dialog are not a state rescore_sampled could score an answer against.
+        self._last_decode = (s.st, Bn, self.arena) if mode.keeps_state else None
+        return out
 
-        return refresh, g_enc.replay, g_dec.replay, st, cur, logits
+    def _decode_rows(self, name, arg, value):
+        """The one range check of `num_beams` / `num_samples` (modules.py relies on it): K decoder rows per dialog, 1..ops.BEAM_MAX,
+        over a vocabulary the fused step kernels hold."""
+        K = int(value)
+        if not 1 <= K <= ops.BEAM_MAX:
+            raise GstvdError("%s: %s must be in 1..%d, got %r" % (name, arg, ops.BEAM_MAX, value))
+        if self.dec_cfg.vocab_size > ops.SAMPLE_MAX_VOCAB:
+            raise GstvdError("%s: vocabulary %d exceeds the kernel's %d" % (name, self.dec_cfg.vocab_size, ops.SAMPLE_MAX_VOCAB))
+        return K
 
     @torch.no_grad()
     def sample(self, feats, loc, img_mask, ids, segs, att_mask, dec_ids, temperature=1.0, top_k=0, top_p=0.0,
@@ -181,125 +355,18 @@ class DecodeMixin(object):
         if _.get("num_beams") is not None and int(_["num_beams"]) > 1:
             raise GstvdError("sample() draws one answer per row; num_beams = %d is beam search: call beam_search(...) or "
                              "model(..., num_beams=K)" % int(_["num_beams"]))
-        dc = self.dec_cfg
-        if segs is None:
-            segs = torch.zeros_like(ids)
-        ins = (feats, loc, img_mask, ids, segs, att_mask, dec_ids)
-        L0, Bn = dec_ids.shape[1], ids.shape[0]
+        dc, L0 = self.dec_cfg, dec_ids.shape[1]
         P = dict(temperature=float(temperature), top_k=int(top_k), top_p=float(top_p), ngram=int(ngram_blocking_size))
-        sig = (L0, max_seq_len, tuple(sorted(P.items()))) + tuple((tuple(x.shape), x.dtype) if x is not None else None for x in ins)
-        if uniforms is None:
-            # the call's randomness, drawn ONCE from torch's default CUDA generator (eagerly: no generator state inside the
-            # captured graphs); every step then draws by inverse CDF -- the same distribution as the reference's
-            # torch.multinomial (whose stream is device specific anyway), and the same ids from eager issue and graph replay
-            u = torch.rand(max_seq_len, Bn, device=ids.device, dtype=torch.float32).clamp_min_(1e-12)
-        else:
-            u = uniforms.to(ids.device, torch.float32)
-            if u.dim() != 2 or u.shape[0] < max_seq_len or u.shape[1] != Bn:
-                raise GstvdError("uniforms must be [max_seq_len = %d, batch = %d] (one draw per step and row), got %s"
-                                 % (max_seq_len, Bn, tuple(u.shape)))
-            u = u[:max_seq_len].contiguous()
-        use_graph = bool(self.model.params.get("amd_decode_graph", True)) and self._fused_sampling(P, dc.vocab_size)
-        # parameters edited since the last call (load_state_dict, an optimizer step): the captured graphs read the flat
-        # buffers / bf16 shadow, so bring those up to date OUTSIDE the graphs; a re-materialised buffer drops the sessions
-        self.prepare(ids.device)
-        sess = self._decode_sessions.get(sig) if use_graph else None
-        if sess is not None:
-            refresh, run_encode, run_tokens, dst, cur, last_logits = sess
-            refresh(ins, u)
-            run_encode()
-            run_tokens()
-            cur, logits = cur.clone(), last_logits
-        else:
-            run_encode, one_token, dst = self._decode_plan(ins, L0, max_seq_len)
-            run_encode()
-            hist = ids * (segs == 0).long()
-            cur = torch.zeros(L0 + max_seq_len, Bn, dtype=torch.long, device=ids.device)
-            cur[:L0] = dec_ids.t()
-            calls0 = _libmod.N_CALLS[0]
-            for t in range(L0 + max_seq_len - 1):
-                logits = one_token(cur[t], t)
-                if t >= L0 - 1:                            # (earlier positions only consume the given prefix)
-                    self._sampling_step(logits, cur, t + 1, hist, P, u[t - (L0 - 1)])
-            self.decode_lib_calls_per_token = (_libmod.N_CALLS[0] - calls0) / float(L0 + max_seq_len - 1)
-        self.last = dict(decode_logits=logits.float())    # last position's raw logits (tests / debugging)
-        # the encoder side of this call (cross-attention K/V of all layers, masks) stays valid in the arena until the next
-        # engine call: `rescore_sampled` scores the sampled answer against it without a second encoder pass
-        out = decoding.pad_after_eos(cur[L0:].t().contiguous(), dc.eos_token_id, dc.pad_token_id)
-        if use_graph and sess is None:
-            # first call with these shapes ran eagerly (it also initialised every lazily built table / attribute / arena
-            # chunk); capture now so the next batch replays
-            if len(self._decode_sessions) >= 4:
-                self._decode_sessions.clear()
-            self._decode_sessions[sig] = self._decode_session(ins, L0, max_seq_len, P)
-        # (after the capture: capturing runs the Python side of encode() again -- which rewinds the arena bookkeeping and drops
-        # this marker -- but executes nothing, so the eager call's encoder states are still what the arena holds)
-        self._last_decode = (dst, ids.shape[0], self.arena)
-        return out
 
-    # ------------------------------------------------------------------------------------------ beam search
-    def _beam_buffers(self, Bn, K, L0, max_seq_len, dev):
-        """Static state of a beam call: the time-major id buffer, the ping-pong (score, done) pairs, one parent row per generated
-        position, the step kernel's workspace and the state in front of the first step (s[b,0] = 0, s[b,j>0] = -inf)."""
-        init = torch.full((Bn, K), -float("inf"), dtype=torch.float32, device=dev)
-        init[:, 0] = 0.0
-        return dict(cur=torch.zeros(L0 + max_seq_len, Bn * K, dtype=torch.long, device=dev),
-                    score=[torch.zeros(Bn, K, dtype=torch.float32, device=dev) for _ in range(2)],
-                    done=[torch.zeros(Bn, K, dtype=torch.int32, device=dev) for _ in range(2)],
-                    parent=torch.zeros(max_seq_len, Bn, K, dtype=torch.int32, device=dev),
-                    ws=ops.beam_workspace(Bn, K, dev), init=init)
+        def finish(s):
+            # (a replayed session's id buffer is overwritten by the next call: hand out a copy)
+            cur = s.bufs["cur"].clone() if s.g_dec is not None else s.bufs["cur"]
+            self.last = dict(decode_logits=s.ret.float())    # last position's raw logits (tests / debugging)
+            return decoding.pad_after_eos(cur[L0:].t().contiguous(), dc.eos_token_id, dc.pad_token_id)
 
-    def _beam_loop(self, one_token, st, bufs, dec_ids, L0, max_seq_len, K):
-        """The whole beam loop on static buffers, free of host synchronisation (eager issue and graph capture run this same
-        code): the prefix positions feed all K rows of a dialog alike; from position L0 - 1 on every token step is followed by
-        the beam step (gstvd_beam_step: token row t + 1 of the id buffer, parents, the other (score, done) pair) and, while
-        another token step follows, by the reorder of the self-attention caches into the OTHER cache set, which the next token
-        step then appends to and reads.  K = 1 keeps one cache set (its only parent is itself).  Returns the index of the final
-        (score, done) pair."""
-        dc = self.dec_cfg
-        cur, score, done = bufs["cur"], bufs["score"], bufs["done"]
-        Bn = dec_ids.shape[0]
-        cur[:L0] = dec_ids.t()[:, :, None].expand(L0, Bn, K).reshape(L0, Bn * K)
-        score[0].copy_(bufs["init"])
-        done[0].zero_()
-        steps, cset = L0 + max_seq_len - 1, 0
-        H, Umax = dc.hidden_size, st["Umax"]
-        for t in range(steps):
-            logits = one_token(cur[t], t, cset)
-            if t < L0 - 1:
-                continue
-            g = t - (L0 - 1)
-            ops.beam_step(logits, score[g & 1], done[g & 1], score[(g + 1) & 1], done[(g + 1) & 1], bufs["parent"][g], cur, t + 1,
-                          bufs["ws"], dc.eos_token_id, dc.pad_token_id)
-            if K > 1 and t + 1 < steps:
-                sets = st["QKVc"]
-                ops.beam_reorder([a.t.view(Bn * K, Umax, 3 * H) for a in sets[cset]],
-                                 [a.t.view(Bn * K, Umax, 3 * H) for a in sets[1 - cset]], bufs["parent"][g], t, H)
-                cset = 1 - cset
-        return max_seq_len & 1
-
-    def _beam_session(self, ins, L0, max_seq_len, K):
-        """hipGraph form of a beam call, as `_decode_session` is of a sampling call: static copies of the inputs, one graph for
-        `encode` and ONE for the whole beam loop (every position's decoder stack, beam step and cache reorder)."""
-        static = tuple(x.clone() if x is not None else None for x in ins)
-        ids, dec_ids = static[3], static[6]
-        bufs = self._beam_buffers(ids.shape[0], K, L0, max_seq_len, ids.device)
-        encode, one_token, st = self._decode_plan(static, L0, max_seq_len, beams=K)
-        from .graph import capture, gc_quiet
-        with gc_quiet():
-            g_enc = torch.cuda.CUDAGraph()
-            with capture(g_enc):
-                encode()
-            g_dec = torch.cuda.CUDAGraph()
-            with capture(g_dec, pool=g_enc.pool(), quiesce=False):
-                fin = self._beam_loop(one_token, st, bufs, dec_ids, L0, max_seq_len, K)
-
-        def refresh(new):
-            for dst, src in zip(static, new):
-                if dst is not None:
-                    dst.copy_(src)
-
-        return refresh, g_enc.replay, g_dec.replay, bufs, fin
+        # (a vocabulary beyond the fused kernel's takes the torch filters, eagerly step by step: no captured token graph)
+        return self._decode(_SAMPLE, (feats, loc, img_mask, ids, segs, att_mask, dec_ids), max_seq_len, finish, P=P,
+                            uniforms=uniforms, graph=self._fused_sampling(P, dc.vocab_size))
 
     @torch.no_grad()
     def beam_search(self, feats, loc, img_mask, ids, segs, att_mask, dec_ids, num_beams=5, length_penalty=1.0, max_seq_len=18):
@@ -328,88 +395,23 @@ class DecodeMixin(object):
         self._refuse_maps("beam_search")
         from . import decoding
         dc = self.dec_cfg
-        K = int(num_beams)
-        if not 1 <= K <= ops.BEAM_MAX:
-            raise GstvdError("beam_search: num_beams must be in 1..%d, got %r" % (ops.BEAM_MAX, num_beams))
-        if dc.vocab_size > ops.SAMPLE_MAX_VOCAB:
-            raise GstvdError("beam_search: vocabulary %d exceeds the beam kernel's %d" % (dc.vocab_size, ops.SAMPLE_MAX_VOCAB))
+        K = self._decode_rows("beam_search", "num_beams", num_beams)
         if dc.num_hidden_layers > ops.BEAM_MAX_LAYERS:
             raise GstvdError("beam_search: at most %d decoder layers" % ops.BEAM_MAX_LAYERS)
-        if segs is None:
-            segs = torch.zeros_like(ids)
-        ins = (feats, loc, img_mask, ids, segs, att_mask, dec_ids)
         L0, Bn = dec_ids.shape[1], ids.shape[0]
-        sig = ("beam", L0, max_seq_len, K, float(length_penalty)) + tuple((tuple(x.shape), x.dtype) if x is not None else None for x in ins)
-        use_graph = bool(self.model.params.get("amd_decode_graph", True))
-        self.prepare(ids.device)
-        sess = self._decode_sessions.get(sig) if use_graph else None
-        if sess is not None:
-            refresh, run_encode, run_loop, bufs, fin = sess
-            refresh(ins)
-            run_encode()
-            run_loop()
-        else:
-            run_encode, one_token, st = self._decode_plan(ins, L0, max_seq_len, beams=K)
-            run_encode()
-            bufs = self._beam_buffers(Bn, K, L0, max_seq_len, ids.device)
-            calls0 = _libmod.N_CALLS[0]
-            fin = self._beam_loop(one_token, st, bufs, dec_ids, L0, max_seq_len, K)
-            self.decode_lib_calls_per_token = (_libmod.N_CALLS[0] - calls0) / float(L0 + max_seq_len - 1)
-        tok = bufs["cur"][L0:].view(max_seq_len, Bn, K)
-        seqs = decoding.beam_backtrace(tok, bufs["parent"])
-        out, scores, order = decoding.beam_finalize(seqs, bufs["score"][fin], dc.eos_token_id, dc.pad_token_id, length_penalty)
-        # (what the step kernel decided, unsorted, for tests / debugging: tokens and parents per step, summed log-probabilities)
-        self.last = dict(beam_tok=tok.clone(), beam_parent=bufs["parent"].clone(), beam_logp=bufs["score"][fin].clone(), beam_order=order)
-        if use_graph and sess is None:
-            if len(self._decode_sessions) >= 4:
-                self._decode_sessions.clear()
-            self._decode_sessions[sig] = self._beam_session(ins, L0, max_seq_len, K)
-        self._last_decode = None          # K rows per dialog: not a state rescore_sampled could score an answer against
-        return out, scores
 
-    # ------------------------------------------------------------------------------------------ sample and rank
-    def _ranked_loop(self, one_token, cur, lp, hist, dec_ids, L0, max_seq_len, S, P, u):
-        """The token loop of `sample_ranked` on static buffers, free of host synchronisation (eager issue and graph capture run
-        this same code): the prefix goes to all S rows of a dialog alike; from position L0 - 1 on every token step is followed
-        by ONE launch (gstvd_sample_topk_scored) that draws token row t + 1 of the time-major id buffer `cur` and writes the
-        drawn ids' log-probabilities into row t - (L0 - 1) of the time-major buffer `lp`.  Returns the last logits."""
-        Bn = dec_ids.shape[0]
-        cur[:L0] = dec_ids.t()[:, :, None].expand(L0, Bn, S).reshape(L0, Bn * S)
-        for t in range(L0 + max_seq_len - 1):
-            logits = one_token(cur[t], t)
-            if t >= L0 - 1:
-                g = t - (L0 - 1)
-                ops.sample_topk_scored(logits, P["temperature"], P["top_k"], u[g], cur[t + 1], lp[g], None,
-                                       ngram=(hist, cur, t + 1, P["ngram"]) if P["ngram"] > 0 else None, top_p=P["top_p"])
-        return logits
+        def finish(s):
+            bufs, fin = s.bufs, s.ret
+            tok = bufs["cur"][L0:].view(max_seq_len, Bn, K)
+            seqs = decoding.beam_backtrace(tok, bufs["parent"])
+            out, scores, order = decoding.beam_finalize(seqs, bufs["score"][fin], dc.eos_token_id, dc.pad_token_id, length_penalty)
+            # (what the step kernel decided, unsorted, for tests / debugging: tokens and parents per step, summed log-probabilities)
+            self.last = dict(beam_tok=tok.clone(), beam_parent=bufs["parent"].clone(), beam_logp=bufs["score"][fin].clone(),
+                             beam_order=order)
+            return out, scores
 
-    def _ranked_session(self, ins, L0, max_seq_len, S, P):
-        """hipGraph form of a `sample_ranked` call, as `_decode_session` is of a `sample` call: static copies of the inputs, one
-        graph for `encode` (and the expanded n-gram history) and ONE for the whole token loop with its scored draws."""
-        static = tuple(x.clone() if x is not None else None for x in ins)
-        ids, segs, dec_ids = static[3], static[4], static[6]
-        Dn, dev = ids.shape[0] * S, ids.device
-        cur = torch.zeros(L0 + max_seq_len, Dn, dtype=torch.long, device=dev)
-        lp = torch.zeros(max_seq_len, Dn, dtype=torch.float32, device=dev)
-        u_buf = torch.zeros(max_seq_len, Dn, dtype=torch.float32, device=dev)
-        encode, one_token, st = self._decode_plan(static, L0, max_seq_len, beams=S, reorder=False)
-        from .graph import capture, gc_quiet
-        with gc_quiet():
-            g_enc = torch.cuda.CUDAGraph()
-            with capture(g_enc):
-                encode()
-                hist = (ids * (segs == 0).long()).repeat_interleave(S, 0)
-            g_dec = torch.cuda.CUDAGraph()
-            with capture(g_dec, pool=g_enc.pool(), quiesce=False):
-                logits = self._ranked_loop(one_token, cur, lp, hist, dec_ids, L0, max_seq_len, S, P, u_buf)
-
-        def refresh(new, uniforms):
-            for dst, src in zip(static, new):
-                if dst is not None:
-                    dst.copy_(src)
-            u_buf.copy_(uniforms)
-
-        return refresh, g_enc.replay, g_dec.replay, st, cur, lp, logits
+        return self._decode(_BEAM, (feats, loc, img_mask, ids, segs, att_mask, dec_ids), max_seq_len, finish, K=K,
+                            key=(float(length_penalty),))
 
     @torch.no_grad()
     def sample_ranked(self, feats, loc, img_mask, ids, segs, att_mask, dec_ids, num_samples=4, length_penalty=1.0, temperature=1.0,
@@ -437,54 +439,20 @@ class DecodeMixin(object):
         self._refuse_maps("sample_ranked")
         from . import decoding
         dc = self.dec_cfg
-        S = int(num_samples)
-        if not 1 <= S <= ops.BEAM_MAX:
-            raise GstvdError("sample_ranked: num_samples must be in 1..%d, got %r" % (ops.BEAM_MAX, num_samples))
-        if dc.vocab_size > ops.SAMPLE_MAX_VOCAB:
-            raise GstvdError("sample_ranked: vocabulary %d exceeds the sampling kernel's %d" % (dc.vocab_size, ops.SAMPLE_MAX_VOCAB))
+        S = self._decode_rows("sample_ranked", "num_samples", num_samples)
         L0, Bn = dec_ids.shape[1], ids.shape[0]
-        Dn = Bn * S
-        if uniforms is not None and (uniforms.dim() != 2 or uniforms.shape[0] < max_seq_len or uniforms.shape[1] != Dn):
-            raise GstvdError("uniforms must be [max_seq_len = %d, batch * num_samples = %d] (one draw per step and decoder row), "
-                             "got %s" % (max_seq_len, Dn, tuple(uniforms.shape)))
-        if segs is None:
-            segs = torch.zeros_like(ids)
-        ins = (feats, loc, img_mask, ids, segs, att_mask, dec_ids)
         P = dict(temperature=float(temperature), top_k=int(top_k), top_p=float(top_p), ngram=int(ngram_blocking_size))
-        sig = ("ranked", L0, max_seq_len, S, tuple(sorted(P.items()))) + tuple((tuple(x.shape), x.dtype) if x is not None else None for x in ins)
-        if uniforms is None:
-            u = torch.rand(max_seq_len, Dn, device=ids.device, dtype=torch.float32).clamp_min_(1e-12)
-        else:
-            u = uniforms.to(ids.device, torch.float32)[:max_seq_len].contiguous()
-        use_graph = bool(self.model.params.get("amd_decode_graph", True))
-        self.prepare(ids.device)
-        sess = self._decode_sessions.get(sig) if use_graph else None
-        if sess is not None:
-            refresh, run_encode, run_tokens, dst, cur, lp, logits = sess
-            refresh(ins, u)
-            run_encode()
-            run_tokens()
-        else:
-            run_encode, one_token, dst = self._decode_plan(ins, L0, max_seq_len, beams=S, reorder=False)
-            run_encode()
-            hist = (ids * (segs == 0).long()).repeat_interleave(S, 0)
-            cur = torch.zeros(L0 + max_seq_len, Dn, dtype=torch.long, device=ids.device)
-            lp = torch.zeros(max_seq_len, Dn, dtype=torch.float32, device=ids.device)
-            calls0 = _libmod.N_CALLS[0]
-            logits = self._ranked_loop(one_token, cur, lp, hist, dec_ids, L0, max_seq_len, S, P, u)
-            self.decode_lib_calls_per_token = (_libmod.N_CALLS[0] - calls0) / float(L0 + max_seq_len - 1)
-        self.last = dict(decode_logits=logits.float())
-        out, scores, token_logp, order = decoding.rank_samples(cur[L0:].view(max_seq_len, Bn, S).permute(1, 2, 0),
-                                                               lp.view(max_seq_len, Bn, S).permute(1, 2, 0),
-                                                               dc.eos_token_id, dc.pad_token_id, length_penalty)
-        self.last["sample_order"] = order
-        if use_graph and sess is None:
-            if len(self._decode_sessions) >= 4:
-                self._decode_sessions.clear()
-            self._decode_sessions[sig] = self._ranked_session(ins, L0, max_seq_len, S, P)
-        # (as in sample(): the capture executes nothing, the eager call's encoder states are what the arena holds)
-        self._last_decode = (dst, Bn, self.arena)
-        return out, scores, token_logp
+
+        def finish(s):
+            self.last = dict(decode_logits=s.ret.float())
+            out, scores, token_logp, order = decoding.rank_samples(s.bufs["cur"][L0:].view(max_seq_len, Bn, S).permute(1, 2, 0),
+                                                                   s.bufs["lp"].view(max_seq_len, Bn, S).permute(1, 2, 0),
+                                                                   dc.eos_token_id, dc.pad_token_id, length_penalty)
+            self.last["sample_order"] = order
+            return out, scores, token_logp
+
+        return self._decode(_RANKED, (feats, loc, img_mask, ids, segs, att_mask, dec_ids), max_seq_len, finish, K=S, P=P,
+                            uniforms=uniforms)
 
     @torch.no_grad()
     def rescore_sampled(self, dec_ids, dec_mask=None, loss_reduction=False):

@@ -489,8 +489,6 @@ class EncoderDecoderModel(nn.Module):
         if int(ngram_blocking_size or 0) > 0:
             raise GstvdError("beam search does not support ngram_blocking_size > 0 (a per-beam history needs the back-pointers); "
                              "use the sampling branch for n-gram blocking")
-        if not 1 <= int(num_beams) <= 8:
-            raise GstvdError("num_beams must be in 1..8, got %r" % (num_beams,))
         return self.engine.beam_search(enc_image_features, enc_image_spatials, enc_image_mask, enc_input_ids, enc_segments,
                                        enc_attention_mask, dec_input_ids, num_beams=int(num_beams),
                                        length_penalty=float(length_penalty), max_seq_len=int(max_seq_len))
@@ -502,8 +500,6 @@ class EncoderDecoderModel(nn.Module):
         -> (sequences [B, S, max_seq_len] int64, scores [B, S] fp32 = sum of the drawn tokens' log-probabilities / len **
         length_penalty, token_logp [B, S, max_seq_len] fp32), each row's S = num_samples samples best first."""
         from ._lib import GstvdError
-        if not 1 <= int(num_samples) <= 8:
-            raise GstvdError("num_samples must be in 1..8, got %r" % (num_samples,))
         if _.get("num_beams") is not None and int(_["num_beams"]) > 1:
             raise GstvdError("num_samples and num_beams = %d exclude each other: sample-and-rank draws, beam search does not"
                              % int(_["num_beams"]))
@@ -549,10 +545,7 @@ class EncoderDecoderModel(nn.Module):
         num_beams = decoding_kwargs.get("num_beams")
         num_samples = decoding_kwargs.get("num_samples")
         if num_samples is not None:
-            from ._lib import GstvdError
-            if not 1 <= int(num_samples) <= 8:
-                raise GstvdError("num_samples must be in 1..8, got %r" % (num_samples,))
-            if int(num_samples) > 1:
+            if int(num_samples) != 1:                 # (out of range: Engine.sample_ranked refuses it)
                 seqs, _, _ = self.sample_ranked(enc_image_features, enc_image_spatials, enc_image_mask, enc_input_ids, enc_segments,
                                                 enc_attention_mask, dec_input_ids, **decoding_kwargs)
                 return seqs[:, 0].contiguous()
