@@ -205,6 +205,9 @@ SIGNATURES = {
     "gstvd_rows_argmax": (_i32, [_vp, _i64, _i64, _i64, _i32, _vp, _vp, _vp]),
     "gstvd_vocab_argmax_ws_bytes": (_i64, [_i64, _i64]),
     "gstvd_vocab_argmax": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _i32, _vp, _i64, _vp, _vp, _vp]),
+    "gstvd_topk_logp": (_i32, [_vp, _i64, _vp, _i64, _i64, _i64, _i32, _vp, _vp, _vp]),
+    "gstvd_distill_fwd": (_i32, [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _f32, _f32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gstvd_distill_bwd": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _f32, _f32, _i32, _vp, _i64, _vp]),
 }
 
 _STATUS = {-1: "GSTVD_E_DTYPE", -2: "GSTVD_E_SHAPE", -3: "GSTVD_E_ALIGN", -4: "GSTVD_E_NULL", -5: "GSTVD_E_UNSUPPORTED"}

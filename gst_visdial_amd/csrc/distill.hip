@@ -1,0 +1,265 @@
+// Soft pseudo-labels of the self-training loop (no reference counterpart; include/gstvd_hip.h states the rules in full): the K best
+// teacher tokens of every position with their log-probabilities (gstvd_topk_logp), and the student's loss against them mixed with
+// the hard-label cross entropy (gstvd_distill_fwd / gstvd_distill_bwd).  Conventions of loss.hip: one workgroup per logits row,
+// 4-element vector accesses, deterministic reductions, stats by loss_reduce.h's rule.
+#include "loss_reduce.h"
+#include "ce_row.h"
+#include <math.h>
+
+namespace {
+
+constexpr int KMAX = 16;
+
+// ---- teacher side ----------------------------------------------------------------------------------------------------------------
+constexpr int TNT = 1024, TNW = TNT / 64;
+constexpr int TVEC = 8;                                       // 4-vectors per thread: V <= 8 * 4 * 1024 (checked by the host entry)
+
+// (a, ia) stands in front of (b, ib): larger value, then smaller index (-inf == -inf falls through to the index)
+DEVFN bool before(float a, int ia, float b, int ib) { return a > b || (a == b && ia < ib); }
+
+// The row in registers as in beam.hip's phase A, read once in 4-vectors; K rounds of block arg-max, each behind the previous
+// round's winner.  Nothing is marked in the registers (a dynamic index into zr[] would send the row to scratch); slots at or past
+// V never qualify, whatever they hold.
+template <typename T>
+__global__ __launch_bounds__(TNT) void topk_logp_kernel(const T* logits, int64_t ldl, const float* lse, int V, int K, int64_t* ids,
+                                                        float* logp) {
+  __shared__ float smv[TNW];
+  __shared__ int smi[TNW];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t m = blockIdx.x;
+  const T* x = logits + m * ldl;
+  float zr[TVEC * 4];
+#pragma unroll
+  for (int j = 0; j < TVEC; ++j) {
+    const int c = (tid + j * TNT) * 4;
+    f32x4 v = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    if (c + 3 < V) {
+      v = ld4(x + c);
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (c + e < V) v[e] = to_f(x[c + e]);
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) zr[j * 4 + e] = v[e];
+  }
+  const float l = lse[m];
+  float pv = INFINITY, mine_v = -INFINITY;
+  int pi = -1, mine_i = 0;
+  for (int round = 0; round < K; ++round) {                   // uniform: every thread holds the same (pv, pi)
+    float bv = -INFINITY;
+    int bi = 0x7fffffff;
+#pragma unroll
+    for (int j = 0; j < TVEC; ++j) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int i = (tid + j * TNT) * 4 + e;
+        const float z = zr[j * 4 + e];
+        const bool ok = i < V && before(pv, pi, z, i) && before(z, i, bv, bi);
+        bv = ok ? z : bv;
+        bi = ok ? i : bi;
+      }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ov = __shfl_xor(bv, o, 64);
+      const int oi = __shfl_xor(bi, o, 64);
+      const bool t = before(ov, oi, bv, bi);
+      bv = t ? ov : bv;
+      bi = t ? oi : bi;
+    }
+    __syncthreads();                                          // (the previous round's reads of smv / smi are over)
+    if (lane == 0) { smv[wave] = bv; smi[wave] = bi; }
+    __syncthreads();
+    bv = smv[0]; bi = smi[0];
+#pragma unroll
+    for (int w = 1; w < TNW; ++w) {
+      const float ov = smv[w];
+      const int oi = smi[w];
+      const bool t = before(ov, oi, bv, bi);
+      bv = t ? ov : bv;
+      bi = t ? oi : bi;
+    }
+    if (bi >= V) { bv = -INFINITY; bi = V - 1; }              // (only a row with NaNs runs out of candidates: K <= V is checked)
+    if (tid == round) { mine_v = bv; mine_i = bi; }
+    pv = bv; pi = bi;
+  }
+  if (tid < K) {
+    ids[m * K + tid] = (int64_t)mine_i;
+    logp[m * K + tid] = mine_v - l;
+  }
+}
+
+// ---- student side ----------------------------------------------------------------------------------------------------------------
+// A token has a soft label when its first id is not negative and every one of its K ids lies in [0, V): one decision, taken the
+// same way by the forward and the backward, before any logit is read through an id.
+DEVFN bool soft_row_ok(const int64_t* sid, int K, int64_t V) {
+  bool ok = sid[0] >= 0;
+  for (int k = 0; k < K; ++k) ok = ok && sid[k] >= 0 && sid[k] < V;
+  return ok;
+}
+
+// q_k = softmax over the K entries of soft_logp * inv_tau, max-subtracted: e_k / sum with the sum formed serially k = 0 .. K - 1
+// wherever it is formed, so the forward and the backward hold the same q.  -> sum, max (q_k = expf(s_k - max) / sum)
+DEVFN void soft_q_norm(const float* sl, int K, float inv_tau, float& smax, float& z) {
+  smax = -INFINITY;
+  for (int k = 0; k < K; ++k) smax = fmaxf(smax, sl[k] * inv_tau);
+  z = 0.f;
+  for (int k = 0; k < K; ++k) z += expf(sl[k] * inv_tau - smax);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void distill_fwd_kernel(const T* logits, int64_t ldl, const int64_t* labels, const int64_t* soft_ids,
+                                                          const float* soft_logp, int64_t V, int K, int64_t ignore, float alpha,
+                                                          float inv_tau, const float* ce_loss, float* row_loss, float* row_kd,
+                                                          float* lse_tau) {
+  __shared__ float red[4];
+  const int64_t m = blockIdx.x;
+  const int64_t lab = labels[m];
+  const bool keep = !(lab == ignore || lab < 0 || lab >= V);
+  const int64_t* sid = soft_ids + m * K;
+  if (!(keep && soft_row_ok(sid, K, V))) {                    // block-uniform
+    if (threadIdx.x == 0) { row_loss[m] = ce_loss[m]; row_kd[m] = 0.f; lse_tau[m] = 0.f; }
+    return;
+  }
+  const T* x = logits + m * ldl;
+  const int64_t V4 = V & ~(int64_t)3;
+  float mx = -INFINITY;
+  for (int64_t c = threadIdx.x * 4; c < V4; c += 1024) {
+    f32x4 v = ld4(x + c);
+    mx = fmaxf(fmaxf(mx, fmaxf(v[0], v[1])), fmaxf(v[2], v[3]));
+  }
+  for (int64_t c = V4 + threadIdx.x; c < V; c += 256) mx = fmaxf(mx, to_f(x[c]));
+  mx = block_reduce(mx, red, true) * inv_tau;                 // inv_tau > 0: the maximum of the scaled row
+  float s = 0.f;
+  for (int64_t c = threadIdx.x * 4; c < V4; c += 1024) {
+    f32x4 v = ld4(x + c);
+    s += __expf(v[0] * inv_tau - mx) + __expf(v[1] * inv_tau - mx) + __expf(v[2] * inv_tau - mx) + __expf(v[3] * inv_tau - mx);
+  }
+  for (int64_t c = V4 + threadIdx.x; c < V; c += 256) s += __expf(to_f(x[c]) * inv_tau - mx);
+  s = block_reduce(s, red, false);
+  if (threadIdx.x == 0) {
+    const float lt = mx + logf(s);
+    const float* sl = soft_logp + m * K;
+    float smax, z;
+    soft_q_norm(sl, K, inv_tau, smax, z);
+    const float lz = logf(z);
+    float kd = 0.f;
+    for (int k = 0; k < K; ++k) {
+      const float sk = sl[k] * inv_tau - smax;
+      const float q = expf(sk) / z;
+      if (q > 0.f) kd += q * ((sk - lz) - (to_f(x[sid[k]]) * inv_tau - lt));     // (q == 0: the term is exactly 0, never 0 * inf)
+    }
+    const float tau = 1.f / inv_tau;
+    lse_tau[m] = lt;
+    row_kd[m] = kd;
+    row_loss[m] = alpha == 0.f ? ce_loss[m] : (1.f - alpha) * ce_loss[m] + alpha * (tau * tau) * kd;
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void distill_bwd_kernel(const T* logits, int64_t ldl, const int64_t* labels, const int64_t* soft_ids,
+                                                          const float* soft_logp, const float* lse, const float* lse_tau,
+                                                          const float* stats, const float* gscale, int64_t V, int K, int64_t ignore,
+                                                          float alpha, float inv_tau, T* dl, int64_t ldd) {
+  __shared__ float sq[KMAX];
+  __shared__ int64_t si[KMAX];
+  const int64_t m = blockIdx.x;
+  const int64_t lab = labels[m];
+  const bool keep = !(lab == ignore || lab < 0 || lab >= V);
+  float gs = gscale ? gscale[0] : 1.f;
+  gs /= stats[1];
+  const T* x = logits + m * ldl;
+  T* d = dl + m * ldd;
+  const int64_t* sid = soft_ids + m * K;
+  if (!(keep && alpha != 0.f && soft_row_ok(sid, K, V))) {    // block-uniform: the cross entropy's own row, bit for bit
+    ce_bwd_row(x, d, lab, keep, lse[m], gs, V, ldd);
+    return;
+  }
+  if (threadIdx.x < K) {
+    const float* sl = soft_logp + m * K;
+    float smax, z;
+    soft_q_norm(sl, K, inv_tau, smax, z);
+    sq[threadIdx.x] = expf(sl[threadIdx.x] * inv_tau - smax) / z;
+    si[threadIdx.x] = sid[threadIdx.x];
+  }
+  __syncthreads();
+  const float l = lse[m], lt = lse_tau[m];
+  const float wc = 1.f - alpha, wk = alpha * (1.f / inv_tau);
+  for (int64_t c = threadIdx.x * 4; c < ldd; c += 1024) {
+    f32x4 o = {0.f, 0.f, 0.f, 0.f};
+    if (c < V) {
+      f32x4 v = {0.f, 0.f, 0.f, 0.f}, qs = {0.f, 0.f, 0.f, 0.f};
+      if (c + 3 < V) {
+        v = ld4(x + c);
+      } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          if (c + e < V) v[e] = to_f(x[c + e]);
+      }
+      for (int k = 0; k < K; ++k) {                           // duplicate ids count as separate entries: their q add up, k ascending
+        const int64_t off = si[k] - c;
+        if (off >= 0 && off < 4) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) qs[e] += off == e ? sq[k] : 0.f;
+        }
+      }
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (c + e < V)
+          o[e] = gs * (wc * (__expf(v[e] - l) - ((c + e) == lab ? 1.f : 0.f)) + wk * (__expf(v[e] * inv_tau - lt) - qs[e]));
+    }
+    st4(d + c, o);
+  }
+}
+
+}  // namespace
+
+// ---- C ABI -----------------------------------------------------------------------------------------------------------------------
+extern "C" int gstvd_topk_logp(const void* logits, int64_t ldl, const float* lse, int64_t M, int64_t V, int64_t K, int32_t dtype,
+                               int64_t* ids, float* logp, gstvd_stream_t stream) {
+  if (!logits || !lse || !ids || !logp) return GSTVD_E_NULL;
+  if (M <= 0 || V <= 0 || (ldl % 4) || ldl < V || K < 1 || K > KMAX || K > V) return GSTVD_E_SHAPE;
+  if (dtype != GSTVD_BF16 && dtype != GSTVD_F32) return GSTVD_E_DTYPE;
+  if (ce_misaligned(logits, dtype)) return GSTVD_E_ALIGN;
+  if (V > TVEC * 4 * TNT) return GSTVD_E_UNSUPPORTED;         // a row lives in 32 registers per thread
+  hipStream_t s = (hipStream_t)stream;
+  GSTVD_FOR_DTYPE(dtype, T, hipLaunchKernelGGL(topk_logp_kernel<T>, dim3((unsigned)M), dim3(TNT), 0, s, (const T*)logits, ldl, lse, (int)V, (int)K, ids, logp));
+  GSTVD_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int gstvd_distill_fwd(const void* logits, int64_t ldl, const int64_t* labels, const int64_t* soft_ids, const float* soft_logp,
+                                 int64_t M, int64_t V, int64_t K, int64_t ignore_index, float alpha, float inv_tau, int32_t dtype,
+                                 const float* ce_row_loss, float* row_loss, float* row_kd, float* lse_tau, float* stats_out,
+                                 gstvd_stream_t stream) {
+  if (!logits || !labels || !soft_ids || !soft_logp || !ce_row_loss || !row_loss || !row_kd || !lse_tau || !stats_out) return GSTVD_E_NULL;
+  if (M <= 0 || V <= 0 || (ldl % 4) || ldl < V || K < 1 || K > KMAX || !(alpha >= 0.f && alpha <= 1.f) || !(inv_tau > 0.f) || isinf(inv_tau))
+    return GSTVD_E_SHAPE;
+  if (dtype != GSTVD_BF16 && dtype != GSTVD_F32) return GSTVD_E_DTYPE;
+  if (ce_misaligned(logits, dtype)) return GSTVD_E_ALIGN;
+  hipStream_t s = (hipStream_t)stream;
+  GSTVD_FOR_DTYPE(dtype, T, hipLaunchKernelGGL(distill_fwd_kernel<T>, dim3((unsigned)M), dim3(256), 0, s, (const T*)logits, ldl, labels, soft_ids, soft_logp, V, (int)K,
+                                               ignore_index, alpha, inv_tau, ce_row_loss, row_loss, row_kd, lse_tau));
+  GSTVD_LAUNCH_CHECK();
+  hipLaunchKernelGGL(row_loss_reduce_kernel, dim3(1), dim3(256), 0, s, (const float*)row_loss, labels, ignore_index, 0, M, stats_out);   // the cross entropy's count, by its rule
+  GSTVD_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int gstvd_distill_bwd(const void* logits, int64_t ldl, const int64_t* labels, const int64_t* soft_ids, const float* soft_logp,
+                                 const float* lse, const float* lse_tau, const float* stats, const float* gscale, int64_t M, int64_t V,
+                                 int64_t K, int64_t ignore_index, float alpha, float inv_tau, int32_t dtype, void* dlogits, int64_t ldd,
+                                 gstvd_stream_t stream) {
+  if (!logits || !labels || !soft_ids || !soft_logp || !lse || !lse_tau || !stats || !dlogits) return GSTVD_E_NULL;
+  if (M <= 0 || V <= 0 || (ldl % 4) || (ldd % 4) || ldl < V || ldd < V || K < 1 || K > KMAX || !(alpha >= 0.f && alpha <= 1.f) ||
+      !(inv_tau > 0.f) || isinf(inv_tau))
+    return GSTVD_E_SHAPE;
+  if (dtype != GSTVD_BF16 && dtype != GSTVD_F32) return GSTVD_E_DTYPE;
+  if (ce_misaligned(logits, dtype) || ce_misaligned(dlogits, dtype)) return GSTVD_E_ALIGN;
+  hipStream_t s = (hipStream_t)stream;
+  GSTVD_FOR_DTYPE(dtype, T, hipLaunchKernelGGL(distill_bwd_kernel<T>, dim3((unsigned)M), dim3(256), 0, s, (const T*)logits, ldl, labels, soft_ids, soft_logp, lse, lse_tau,
+                                               stats, gscale, V, (int)K, ignore_index, alpha, inv_tau, (T*)dlogits, ldd));
+  GSTVD_LAUNCH_CHECK();
+  return 0;
+}

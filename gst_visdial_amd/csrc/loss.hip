@@ -2,6 +2,7 @@
 // casts, the dropout-mask probe used by tests, and the fused AdamW (pytorch_transformers 1.2.0 semantics).
 // All HBM-bound: 16-byte vector accesses, one workgroup per logits row, deterministic reductions.
 #include "loss_reduce.h"
+#include "ce_row.h"
 #include <math.h>
 
 template <typename T>
@@ -30,27 +31,6 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const T* logits, int64_t ld
     lse_out[m] = lse;
     const int64_t lab = labels[m];
     row_loss[m] = (lab == ignore || lab < 0 || lab >= V) ? 0.f : lse - to_f(x[lab]);
-  }
-}
-
-// One row of dlogits = (softmax - onehot) * gs, columns V..ldd zero; `keep` false: the whole row zero.  Shared by the mean form
-// and the per-row form below, so the two agree to the last bit wherever their scales do.
-template <typename T>
-DEVFN void ce_bwd_row(const T* x, T* d, int64_t lab, bool keep, float l, float gs, int64_t V, int64_t ldd) {
-  for (int64_t c = threadIdx.x * 4; c < ldd; c += 1024) {
-    f32x4 o = {0.f, 0.f, 0.f, 0.f};
-    if (keep) {
-      if (c + 3 < V) {
-        f32x4 v = ld4(x + c);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = (__expf(v[e] - l) - ((c + e) == lab ? 1.f : 0.f)) * gs;
-      } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          if (c + e < V) o[e] = (__expf(to_f(x[c + e]) - l) - ((c + e) == lab ? 1.f : 0.f)) * gs;
-      }
-    }
-    st4(d + c, o);
   }
 }
 
@@ -292,9 +272,6 @@ extern "C" int gstvd_vl_split(const void* d_enc, int64_t B, int64_t R, int64_t T
 // (entry points added without a signature change do not bump it: gstvd_rows_* / gstvd_kl_*, gstvd_ln_kernel_name)
 extern "C" int gstvd_abi_version(void) { return 9; }
 extern "C" const char* gstvd_build_arch(void) { return "gfx950"; }
-
-// The CE entries read logits (and write dlogits) in 4-element vectors: 16 bytes of fp32, 8 bytes of bf16
-static bool ce_misaligned(const void* p, int32_t dtype) { return ((uintptr_t)p & (dtype == GSTVD_BF16 ? 7 : 15)) != 0; }
 
 extern "C" int gstvd_ce_fwd(const void* logits, int64_t ldl, const int64_t* labels, int64_t M, int64_t V, int64_t ignore_index,
                             int32_t dtype, float* row_loss, float* lse, float* stats, gstvd_stream_t stream) {

@@ -873,9 +873,51 @@ class Engine(DecodeMixin, DiscMixin, RankMixin):
         ce = dict(lab=lab, row_loss=row_loss, lse=lse, stats=stats, Md=Md, V=V, pad=dc.pad_token_id)
         return (stats[2] if mean else row_loss), logits.t.view(rows, U, self.flat.Vp)[:, :, :V], ce
 
-    def step(self, feats, loc, img_mask, ids, segs, att_mask, dec_ids, dec_mask, labels, loss_reduction=True):
-        """EncoderDecoderModel.forward, train/eval branch -> (loss, logits)."""
+    def _soft_labels(self, soft, dec_ids, loss_reduction):
+        """Validation of `step`'s soft labels (dec_soft_ids, dec_soft_logp, alpha, temperature), before anything is launched ->
+        None or a dict with the [B * U, K] tensors on the device."""
+        if soft is None or (soft[0] is None and soft[1] is None):
+            return None
+        sid, slp, alpha, temperature = soft
+        if sid is None or slp is None:
+            raise GstvdError("dec_soft_ids and dec_soft_logp go together: both or neither")
+        alpha, temperature = float(alpha), float(temperature)
+        if not 0.0 <= alpha <= 1.0:
+            raise GstvdError("distill_alpha = %r outside [0, 1]" % alpha)
+        if not (temperature > 0.0 and temperature != float("inf")):
+            raise GstvdError("distill_temperature = %r must be positive and finite" % temperature)
+        Bn, U = dec_ids.shape
+        if sid.dim() != 3 or tuple(sid.shape[:2]) != (Bn, U) or sid.shape != slp.shape or not 1 <= sid.shape[2] <= ops.DISTILL_MAX_K:
+            raise GstvdError("dec_soft_ids / dec_soft_logp must both be [B = %d, U = %d, K <= %d], got %s and %s"
+                             % (Bn, U, ops.DISTILL_MAX_K, tuple(sid.shape), tuple(slp.shape)))
+        if not loss_reduction:
+            raise GstvdError("soft labels with loss_reduction=False: the distillation loss is the mean over the kept tokens")
+        if dec_ids.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise GstvdError("soft labels under a stream capture: the distillation step is issued eagerly")
+        dev = dec_ids.device
+        K = sid.shape[2]
+        return dict(ids=sid.to(device=dev, dtype=torch.int64).contiguous().view(-1, K),
+                    logp=slp.to(device=dev, dtype=torch.float32).contiguous().view(-1, K), alpha=alpha, temperature=temperature)
+
+    def _distill(self, logits, ce, soft):
+        """The distillation loss behind `_ce` on the same logits (gstvd_distill_fwd) -> the mean over the kept tokens; `ce` gains
+        what the backward reads."""
+        Md = ce["Md"]
+        row_l, row_kd, lse_tau, stats = self.vec(Md), self.vec(Md), self.vec(Md), self.vec(4)
+        ops.distill_fwd(logits.t, ce["lab"], soft["ids"], soft["logp"], Md, ce["V"], soft["alpha"], soft["temperature"], ce["row_loss"],
+                        row_l, row_kd, lse_tau, stats, ignore_index=ce["pad"])
+        ce.update(soft=soft, lse_tau=lse_tau, row_kd=row_kd, ce_stats=ce["stats"], stats=stats, row_loss=row_l, ce_row_loss=ce["row_loss"])
+        return stats[2]
+
+    def step(self, feats, loc, img_mask, ids, segs, att_mask, dec_ids, dec_mask, labels, loss_reduction=True, soft=None, soft_top_k=None):
+        """EncoderDecoderModel.forward, train/eval branch -> (loss, logits).  `soft`: None or (dec_soft_ids [B, U, K],
+        dec_soft_logp [B, U, K], alpha, temperature) -- the loss is then the distillation loss ("Soft
+        pseudo-labels"); only the launch that fills the logits' gradient differs in its backward.  soft_top_k = K (the teacher's side,
+        without gradients): -> (loss, logits, (ids [B, U, K], logp [B, U, K], labels [B, U]))."""
         record = torch.is_grad_enabled()
+        soft = self._soft_labels(soft, dec_ids, loss_reduction)
+        if soft_top_k is not None and (record or soft is not None or self.model.training):
+            raise GstvdError("soft_top_k is the teacher's side: eval(), torch.no_grad() and no soft labels of its own")
         self._begin(ids.device, record, maps_ok=True)
         if labels is None:
             labels = self._shift_labels(dec_ids)
@@ -887,6 +929,10 @@ class Engine(DecodeMixin, DiscMixin, RankMixin):
         enc = self.fusion(xt, xv, I)
         y, logits = self.decoder(enc, I)
         loss_raw, lv, ce = self._ce(logits, labels, I["B"], I["U"], loss_reduction)
+        if soft_top_k is not None:                                     # (no-grad, eval: EncoderDecoderModel.soft_labels sees to it)
+            return loss_raw.clone(), lv.to(torch.float32, copy=True), self._topk_soft(logits, ce, I["B"], I["U"], soft_top_k)
+        if soft is not None:
+            loss_raw = self._distill(logits, ce, soft)
         st = dict(ce, I=I, logits=logits, mean=bool(loss_reduction), tape=self.tape, inputs_only=self._inputs_only)
         self.last = dict(enc_t=xt, enc_v=xv, enc=enc, dec_hidden=y, logits=logits, lse=ce["lse"], row_loss=ce["row_loss"])
         if record:
@@ -921,7 +967,12 @@ class Engine(DecodeMixin, DiscMixin, RankMixin):
                 self._backward_begin()
             logits = st["logits"]
             logits.g = self.buf(st["Md"], flat.Vp)
-            if st["mean"]:
+            if st.get("soft") is not None:
+                gs = gloss.reshape(1).float().contiguous() if gloss is not None else None
+                so = st["soft"]
+                ops.distill_bwd(logits.t, st["lab"], so["ids"], so["logp"], st["lse"], st["lse_tau"], st["stats"], gs, st["Md"], st["V"],
+                                so["alpha"], so["temperature"], logits.g, ignore_index=st["pad"])
+            elif st["mean"]:
                 gs = gloss.reshape(1).float().contiguous() if gloss is not None else None
                 ops.ce_bwd(logits.t, st["lab"], st["lse"], st["stats"], gs, True, st["Md"], st["V"], logits.g, ignore_index=st["pad"])
             else:

@@ -455,12 +455,23 @@ class DecodeMixin(object):
                             uniforms=uniforms)
 
     @torch.no_grad()
-    def rescore_sampled(self, dec_ids, dec_mask=None, loss_reduction=False):
+    def _topk_soft(self, logits, ce, rows, U, top_k):
+        """The teacher's soft labels of a teacher-forced pass: the top_k best tokens of every position with their log-probabilities
+        (gstvd_topk_logp on the pass's logits, before the arena is rewound) -> (ids [rows, U, K] int64, logp [rows, U, K] fp32,
+        labels [rows, U] int64), tensors of their own."""
+        K = int(top_k)
+        if not 1 <= K <= ops.DISTILL_MAX_K:
+            raise GstvdError("soft_top_k = %d outside 1..%d" % (K, ops.DISTILL_MAX_K))
+        ids, logp = ops.topk_logp(logits.t, ce["lse"], ce["Md"], ce["V"], K)
+        return ids.view(rows, U, K), logp.view(rows, U, K), ce["lab"].view(rows, U).clone()
+
+    def rescore_sampled(self, dec_ids, dec_mask=None, loss_reduction=False, soft_top_k=None):
         """The "ppl trick" of generate.py:183-211 fused onto the decode call that produced the answer: ONE teacher-forced
         decoder pass over `dec_ids` against the encoder states / cross-attention K/V that the last `sample()` call left in
         the arena (same context by construction: the answer was sampled from it) -- no second encoder run, no second K/V
         projection.  Same conventions as the reference's labels=None branch (visual_dialog_decoder.py:53-57): labels are
-        the ids shifted left, `dec_ids` has [SEP] -> [PAD] in place.  Returns (loss, logits) like `step`."""
+        the ids shifted left, `dec_ids` has [SEP] -> [PAD] in place.  Returns (loss, logits) like `step`; with soft_top_k = K
+        also the pass's soft labels: (loss, logits, (ids [rows, U, K], logp [rows, U, K], labels [rows, U]))."""
         ld = self._last_decode
         if ld is None or ld[2] is not self.arena or ld[1] != dec_ids.shape[0]:
             raise GstvdError("rescore_sampled: no decode state of a matching sample() call to reuse")
@@ -475,6 +486,8 @@ class DecodeMixin(object):
         I["dec_ids"] = dec_ids.contiguous().view(-1)
         I["dmask"] = dec_mask.float().contiguous() if dec_mask is not None else None
         _, logits = self.decoder(None, I, kv=st["kv"])
-        loss, lv, _ = self._ce(logits, labels, Bn, U, loss_reduction)
+        loss, lv, ce = self._ce(logits, labels, Bn, U, loss_reduction)
         self._last_decode = None                  # the decode scratch behind the mark has been overwritten
+        if soft_top_k is not None:
+            return loss.clone(), lv.to(torch.float32, copy=True), self._topk_soft(logits, ce, Bn, U, soft_top_k)
         return loss.clone(), lv.to(torch.float32, copy=True)

@@ -43,23 +43,34 @@ def append_to_context(ctx_ids, ctx_len, new_ids, sep_id, segments=None, segment_
 
 
 @torch.no_grad()
-def answer_perplexity(model, enc_kwargs, ans_ids, reuse_decode_state=False):
+def answer_perplexity(model, enc_kwargs, ans_ids, reuse_decode_state=False, soft_top_k=None):
     """generate.py:176-201.  `ans_ids` is mutated like the reference mutates it ([SEP] -> [PAD]); returns (ppl, ans_len).
     reuse_decode_state=True: `ans_ids` was just sampled by `model` from exactly `enc_kwargs` (nothing ran on the model in
     between) -- the teacher-forced pass then reuses that call's encoder states and cross-attention K/V
-    (Engine.rescore_sampled) instead of running the encoder a second time, which is what the reference does."""
+    (Engine.rescore_sampled) instead of running the encoder a second time, which is what the reference does.
+    soft_top_k = K: the scoring pass's soft labels come back as a third value, (ids [rows, U, K], logp [rows, U, K], labels
+    [rows, U]) -- the K best teacher tokens of every position (Engine.rescore_sampled / EncoderDecoderModel.soft_labels)."""
+    soft = None
     if reuse_decode_state:
-        loss, _ = model.engine.rescore_sampled(ans_ids, (ans_ids != 0).float(), loss_reduction=False)
+        out = model.engine.rescore_sampled(ans_ids, (ans_ids != 0).float(), loss_reduction=False, soft_top_k=soft_top_k)
+        loss = out[0]
+        soft = out[2] if soft_top_k is not None else None
     else:
         params = model.params
         mode = params["mode"]
-        params["mode"] = "train"
+        params["mode"] = "train" if soft_top_k is None else "eval"      # (soft_labels refuses a 'train' mode; the step is the same)
         try:
-            loss, _ = model(dec_input_ids=ans_ids, dec_attention_mask=(ans_ids != 0).float(), loss_reduction=False, **enc_kwargs)
+            if soft_top_k is not None:
+                loss, _, soft = model.soft_labels(dec_input_ids=ans_ids, dec_attention_mask=(ans_ids != 0).float(), loss_reduction=False,
+                                                  top_k=soft_top_k, **enc_kwargs)
+            else:
+                loss, _ = model(dec_input_ids=ans_ids, dec_attention_mask=(ans_ids != 0).float(), loss_reduction=False, **enc_kwargs)
         finally:
             params["mode"] = mode
     ans_len = (ans_ids != 0).sum(-1)
     loss = loss.reshape(ans_ids.shape[0], ans_ids.shape[1]).sum(-1) / ans_len
+    if soft_top_k is not None:
+        return torch.exp(loss), ans_len, soft
     return torch.exp(loss), ans_len
 
 

@@ -526,11 +526,35 @@ class EncoderDecoderModel(nn.Module):
         return model_attention_maps(self.engine, enc_image_features, enc_image_spatials, enc_image_mask, enc_input_ids, enc_segments,
                                     enc_attention_mask, dec_input_ids, dec_attention_mask, dec_labels, True, select, heads)
 
+    def soft_labels(self, enc_image_features=None, enc_image_spatials=None, enc_image_mask=None, enc_image_target=None,
+                    enc_image_label=None, enc_next_sentence_labels=None, enc_input_ids=None, enc_segments=None,
+                    enc_sep_indices=None, enc_mlm_labels=None, enc_attention_mask=None, dec_input_ids=None,
+                    dec_attention_mask=None, dec_labels=None, loss_reduction=True, top_k=8):
+        """The teacher's side of the soft pseudo-labels: the eval-mode teacher-forced forward of any rows, without gradients ->
+        (loss, logits, (ids [B, U, K], logp [B, U, K], labels [B, U])) with (loss, logits) as `forward` returns them and, per
+        position, the K = top_k (1..16) most likely tokens (equal logits: the smaller id first) with their fp32 log-probabilities
+        and the labels the pass was scored against.  Needs .eval() and a mode without 'train'."""
+        from ._lib import GstvdError
+        mode = self.params["mode"]
+        if "train" in mode or self.training:
+            raise GstvdError("soft_labels(mode=%r, training=%s): the teacher runs in eval mode (model.eval(), a mode without 'train')"
+                             % (mode, self.training))
+        with torch.no_grad():
+            return self.engine.step(enc_image_features, enc_image_spatials, enc_image_mask, enc_input_ids, enc_segments,
+                                    enc_attention_mask, dec_input_ids, dec_attention_mask, dec_labels, loss_reduction,
+                                    soft_top_k=int(top_k))
+
     def forward(self, enc_image_features=None, enc_image_spatials=None, enc_image_mask=None, enc_image_target=None,
                 enc_image_label=None, enc_next_sentence_labels=None, enc_input_ids=None, enc_segments=None,
                 enc_sep_indices=None, enc_mlm_labels=None, enc_attention_mask=None, dec_input_ids=None,
-                dec_attention_mask=None, dec_labels=None, loss_reduction=True, **decoding_kwargs):
-        """Generation modes: `num_beams` = K > 1 among the decoding keywords decodes by beam search and returns each row's best
+                dec_attention_mask=None, dec_labels=None, loss_reduction=True, dec_soft_ids=None, dec_soft_logp=None,
+                distill_alpha=0.5, distill_temperature=1.0, **decoding_kwargs):
+        """Train / eval modes with `dec_soft_ids` / `dec_soft_logp` [B, U, K] (the teacher's soft labels, `soft_labels` /
+        `Engine.rescore_sampled(soft_top_k=K)`; ids < 0 in entry 0: the token has none): the loss is the mean over the kept tokens
+        of (1 - a) * ce + a * tau^2 * KL(q || softmax(logits / tau)), a = distill_alpha on tokens with a soft label and 0 elsewhere,
+        tau = distill_temperature, q = softmax of the K teacher log-probabilities / tau; differentiable like the plain loss.
+        Without them nothing new is launched.
+        Generation modes: `num_beams` = K > 1 among the decoding keywords decodes by beam search and returns each row's best
         hypothesis as LongTensor [B, 18] -- type and padding of the sampling branch.  `temperature`, `top_k` and `top_p` are
         accepted and ignored there (beam search ranks raw log-probabilities); `length_penalty` (default 1.0) is honoured;
         `ngram_blocking_size` > 0 with beams raises (a per-beam history needs the back-pointers).  `num_beams` absent or 1: the
@@ -540,8 +564,10 @@ class EncoderDecoderModel(nn.Module):
         and padding; together with `num_beams` > 1 it raises.  `num_samples` absent or 1: the sampling branch, untouched."""
         mode = self.params["mode"]
         if "train" in mode or "eval" in mode:
+            soft = None if dec_soft_ids is None and dec_soft_logp is None else (dec_soft_ids, dec_soft_logp, distill_alpha,
+                                                                                  distill_temperature)
             return self.engine.step(enc_image_features, enc_image_spatials, enc_image_mask, enc_input_ids, enc_segments,
-                                    enc_attention_mask, dec_input_ids, dec_attention_mask, dec_labels, loss_reduction)
+                                    enc_attention_mask, dec_input_ids, dec_attention_mask, dec_labels, loss_reduction, soft=soft)
         num_beams = decoding_kwargs.get("num_beams")
         num_samples = decoding_kwargs.get("num_samples")
         if num_samples is not None:

@@ -803,6 +803,83 @@ def ce_bwd_rows(logits, labels, lse, g, M, V, dlogits, ignore_index=0):
     _prof_end(e0, "ce_bwd_rows", 0.0, float(M) * V * (logits.element_size() + dlogits.element_size()), (M, V))
 
 
+DISTILL_MAX_K = 16             # entries of a soft label (gstvd_topk_logp / gstvd_distill_*)
+TOPK_MAX_VOCAB = 32 * 1024     # a teacher row lives in 32 registers per thread
+
+
+def _soft_pair(who, soft_ids, soft_logp, M):
+    """The [M, K] soft labels of `M` logits rows, validated -> K."""
+    if soft_ids.dtype != torch.int64 or soft_logp.dtype != torch.float32 or not soft_ids.is_contiguous() or not soft_logp.is_contiguous():
+        raise L.GstvdError("%s: soft_ids (int64) and soft_logp (fp32) must be contiguous" % who)
+    if soft_ids.dim() < 1 or soft_ids.shape != soft_logp.shape or soft_ids.numel() == 0 or soft_ids.numel() // soft_ids.shape[-1] != M:
+        raise L.GstvdError("%s: soft_ids and soft_logp must both be [%d rows, K], got %s and %s"
+                           % (who, M, tuple(soft_ids.shape), tuple(soft_logp.shape)))
+    K = soft_ids.shape[-1]
+    if not 1 <= K <= DISTILL_MAX_K:
+        raise L.GstvdError("%s: K = %d outside 1..%d" % (who, K, DISTILL_MAX_K))
+    return K
+
+
+def _distill_scalars(who, alpha, temperature):
+    alpha, temperature = float(alpha), float(temperature)
+    if not 0.0 <= alpha <= 1.0:
+        raise L.GstvdError("%s: alpha = %r outside [0, 1]" % (who, alpha))
+    if not (temperature > 0.0 and temperature != float("inf")):
+        raise L.GstvdError("%s: temperature = %r must be positive and finite" % (who, temperature))
+    return alpha, 1.0 / temperature
+
+
+def topk_logp(logits, lse, M, V, K, ids=None, logp=None):
+    """(ids [M, K] int64, logp [M, K] fp32): the K best tokens of every row of logits [M, ld >= V] under (value descending, smaller
+    id first) and their log-probabilities x[id] - lse[m] (gstvd_topk_logp); lse as ce_fwd saved it."""
+    lib = L.load()
+    K = int(K)
+    if not 1 <= K <= DISTILL_MAX_K:
+        raise L.GstvdError("topk_logp: K = %d outside 1..%d" % (K, DISTILL_MAX_K))
+    if lse.dtype != torch.float32 or not lse.is_contiguous() or lse.numel() < M:
+        raise L.GstvdError("topk_logp: lse must be a contiguous fp32 vector of at least %d entries" % M)
+    ids = torch.empty(M, K, dtype=torch.int64, device=logits.device) if ids is None else ids
+    logp = torch.empty(M, K, dtype=torch.float32, device=logits.device) if logp is None else logp
+    _soft_pair("topk_logp", ids, logp, M)
+    if ids.shape[-1] != K:
+        raise L.GstvdError("topk_logp: outputs hold %d entries per row, K = %d" % (ids.shape[-1], K))
+    e0 = _prof_begin()
+    L.check("gstvd_topk_logp", lib.gstvd_topk_logp(_p(logits), logits.stride(-2), _p(lse), M, V, K, dt(logits), _p(ids), _p(logp), _stream()))
+    _prof_end(e0, "topk_logp", 0.0, float(M) * V * logits.element_size(), (M, V, K))
+    return ids, logp
+
+
+def distill_fwd(logits, labels, soft_ids, soft_logp, M, V, alpha, temperature, ce_row_loss, row_loss, row_kd, lse_tau, stats,
+                ignore_index=0):
+    """The per-token loss (1 - a) * ce + a * tau^2 * KL(q || softmax(x / tau)) against the [M, K] soft labels and its stats
+    (gstvd_distill_fwd), after ce_fwd on the same logits and labels (`ce_row_loss` is its row_loss)."""
+    lib = L.load()
+    K = _soft_pair("distill_fwd", soft_ids, soft_logp, M)
+    alpha, inv_tau = _distill_scalars("distill_fwd", alpha, temperature)
+    for name, t in (("ce_row_loss", ce_row_loss), ("row_loss", row_loss), ("row_kd", row_kd), ("lse_tau", lse_tau)):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < M:
+            raise L.GstvdError("distill_fwd: %s must be a contiguous fp32 vector of at least %d entries" % (name, M))
+    e0 = _prof_begin()
+    L.check("gstvd_distill_fwd", lib.gstvd_distill_fwd(_p(logits), logits.stride(-2), _p(labels), _p(soft_ids), _p(soft_logp), M, V, K,
+                                                       ignore_index, alpha, inv_tau, dt(logits), _p(ce_row_loss), _p(row_loss),
+                                                       _p(row_kd), _p(lse_tau), _p(stats), _stream()))
+    _prof_end(e0, "distill_fwd", 0.0, float(M) * V * logits.element_size(), (M, V, K))
+
+
+def distill_bwd(logits, labels, soft_ids, soft_logp, lse, lse_tau, stats, gscale, M, V, alpha, temperature, dlogits, ignore_index=0):
+    """dlogits of distill_fwd's mean loss in one launch (gstvd_distill_bwd); a token without a soft label gets ce_bwd's row."""
+    lib = L.load()
+    K = _soft_pair("distill_bwd", soft_ids, soft_logp, M)
+    alpha, inv_tau = _distill_scalars("distill_bwd", alpha, temperature)
+    if dlogits.dtype != logits.dtype:
+        raise L.GstvdError("distill_bwd: logits and dlogits must share one dtype")
+    e0 = _prof_begin()
+    L.check("gstvd_distill_bwd", lib.gstvd_distill_bwd(_p(logits), logits.stride(-2), _p(labels), _p(soft_ids), _p(soft_logp), _p(lse),
+                                                       _p(lse_tau), _p(stats), _p(gscale), M, V, K, ignore_index, alpha, inv_tau,
+                                                       dt(logits), _p(dlogits), dlogits.stride(-2), _stream()))
+    _prof_end(e0, "distill_bwd", 0.0, float(M) * V * (logits.element_size() + dlogits.element_size()), (M, V, K))
+
+
 def fgsm_step(x, g, eps, out=None):
     """out = x + eps * sign(g) over contiguous fp32 tensors of one size (gstvd_fgsm_step); `out` None: a new tensor, `out` may be x."""
     lib = L.load()

@@ -26,7 +26,7 @@ _IMAGE_KEYS = (("enc_image_feat", "enc_image_features"), ("enc_image_loc", "enc_
 
 @torch.no_grad()
 def generate_dialogs(q_model, a_model, batch, num_rounds=10, sep_id=102, q_kwargs=None, a_kwargs=None, q_uniforms=None,
-                     a_uniforms=None):
+                     a_uniforms=None, soft_top_k=None):
     """`num_rounds` question / answer rounds for every row of `batch` -- `dialog_round`'s `state` dict (enc_image_features,
     enc_image_spatials, enc_image_mask, enc_input_ids, enc_segments, enc_input_len, dec_input_ids, dec_attention_mask on the models'
     device; the text tensors are updated in place, like `dialog_round`'s).  Per round: question, append, answer,
@@ -34,7 +34,9 @@ def generate_dialogs(q_model, a_model, batch, num_rounds=10, sep_id=102, q_kwarg
     is round r's `uniforms=` keyword.  No host synchronisation inside the loop; one read of the kernel's `full` flags behind it
     (RuntimeError "context already full ..." if a row had no room for its [SEP], where the reference raises per row).
     Returns a dict: questions, answers [B, R, U] int64 (the answers as they stand after the perplexity pass: [SEP] -> [PAD]),
-    ppl [B, R] fp32, abnormal [B] bool, and the final context enc_input_ids, enc_segments, enc_input_len."""
+    ppl [B, R] fp32, abnormal [B] bool, and the final context enc_input_ids, enc_segments, enc_input_len.
+    soft_top_k = K: also the teacher's soft labels of the perplexity pass -- soft_ids int64 / soft_logp fp32 [B, R, U, K] (the K
+    best tokens of every answer position, gstvd_topk_logp) and soft_tgt int64 [B, R, U], the labels that pass was scored against."""
     q_kwargs = dict(temperature=0.7, top_k=7, top_p=0.0, ngram_blocking_size=4) if q_kwargs is None else dict(q_kwargs)
     a_kwargs = dict(temperature=0.7, top_k=7, top_p=0.0, ngram_blocking_size=0) if a_kwargs is None else dict(a_kwargs)
     ids, segs, lens = batch["enc_input_ids"], batch["enc_segments"], batch["enc_input_len"]
@@ -49,7 +51,7 @@ def generate_dialogs(q_model, a_model, batch, num_rounds=10, sep_id=102, q_kwarg
     att = (ids != 0).float()                                # kept by the kernel from here on
     abnormal = torch.zeros(B, dtype=torch.int32, device=dev)
     full = torch.zeros(B, dtype=torch.int32, device=dev)
-    questions = answers = ppls = None
+    questions = answers = ppls = soft_ids = soft_logp = soft_tgt = None
     for r in range(R):
         enc = dict(enc_image_features=batch["enc_image_features"], enc_image_spatials=batch["enc_image_spatials"],
                    enc_image_mask=batch["enc_image_mask"], enc_input_ids=ids, enc_segments=segs, enc_attention_mask=att)
@@ -58,7 +60,16 @@ def generate_dialogs(q_model, a_model, batch, num_rounds=10, sep_id=102, q_kwarg
         ques = q_model(dec_input_ids=batch["dec_input_ids"], dec_attention_mask=batch["dec_attention_mask"], **qk, **enc)
         ops.context_append(ids, lens, ques, sep_id, abnormal, full, att_mask=att)
         ans = a_model(dec_input_ids=batch["dec_input_ids"], dec_attention_mask=batch["dec_attention_mask"], **ak, **enc)
-        ppl, _ = answer_perplexity(a_model, enc, ans, reuse_decode_state=True)
+        if soft_top_k is None:
+            ppl, _ = answer_perplexity(a_model, enc, ans, reuse_decode_state=True)
+        else:
+            ppl, _, soft = answer_perplexity(a_model, enc, ans, reuse_decode_state=True, soft_top_k=soft_top_k)
+            if soft_ids is None:
+                K = soft[0].shape[-1]
+                soft_ids = torch.zeros(B, R, ans.shape[1], K, dtype=torch.long, device=dev)
+                soft_logp = torch.zeros(B, R, ans.shape[1], K, dtype=torch.float32, device=dev)
+                soft_tgt = torch.zeros(B, R, ans.shape[1], dtype=torch.long, device=dev)
+            soft_ids[:, r], soft_logp[:, r], soft_tgt[:, r] = soft
         ops.context_append(ids, lens, ans, sep_id, abnormal, full, segments=segs, segment_value=1, att_mask=att)
         if questions is None:
             questions = torch.zeros(B, R, ques.shape[1], dtype=torch.long, device=dev)
@@ -67,8 +78,41 @@ def generate_dialogs(q_model, a_model, batch, num_rounds=10, sep_id=102, q_kwarg
         questions[:, r], answers[:, r], ppls[:, r] = ques, ans, ppl
     if R > 0 and bool(full.any()):                          # the loop's one host synchronisation
         raise RuntimeError("context already full: cannot place [SEP] (rows %s)" % full.nonzero().flatten().tolist())
-    return dict(questions=questions, answers=answers, ppl=ppls, abnormal=abnormal != 0, enc_input_ids=ids, enc_segments=segs,
-                enc_input_len=lens)
+    out = dict(questions=questions, answers=answers, ppl=ppls, abnormal=abnormal != 0, enc_input_ids=ids, enc_segments=segs,
+               enc_input_len=lens)
+    if soft_top_k is not None:
+        out.update(soft_ids=soft_ids, soft_logp=soft_logp, soft_tgt=soft_tgt)
+    return out
+
+
+def align_soft_labels(soft_ids, soft_logp, soft_tgt, dec_labels):
+    """The teacher's soft labels on the student's decoder rows, decided on whatever device the tensors live on without a host
+    synchronisation.  soft_ids / soft_logp [..., Ut, K], soft_tgt [..., Ut] (the labels of the teacher's pass), dec_labels
+    [..., Ud] (the student's).  Teacher position i serves train position i.  A row's soft labels are used only if
+    soft_tgt[..., i] == dec_labels[..., i] at EVERY position with dec_labels != 0 (a position >= Ut with a label fails the row:
+    the teacher never scored it); otherwise, and at positions >= Ut, the row gets ids = -1, logp = 0 and trains on its hard labels
+    alone.  -> (dec_soft_ids int64, dec_soft_logp fp32) [..., Ud, K]."""
+    Ut, K = soft_ids.shape[-2:]
+    Ud = dec_labels.shape[-1]
+    if soft_ids.shape != soft_logp.shape or soft_tgt.shape != soft_ids.shape[:-1] or soft_tgt.shape[:-1] != dec_labels.shape[:-1]:
+        raise GstvdError("align_soft_labels: soft_ids / soft_logp [..., U, K], soft_tgt [..., U] and dec_labels [..., Ud] do not "
+                         "belong together: %s %s %s %s" % (tuple(soft_ids.shape), tuple(soft_logp.shape), tuple(soft_tgt.shape),
+                                                          tuple(dec_labels.shape)))
+    n = min(Ut, Ud)
+    lead = tuple(dec_labels.shape[:-1])
+    tgt = dec_labels.new_zeros(lead + (Ud,))
+    tgt[..., :n] = soft_tgt[..., :n]
+    scored = torch.zeros(Ud, dtype=torch.bool, device=dec_labels.device)
+    scored[:n] = True
+    ok = (((tgt == dec_labels) & scored) | (dec_labels == 0)).all(-1)                   # [...]: the row's alignment holds
+    use = ok[..., None] & scored                                                          # [..., Ud]
+    ids = soft_ids.new_full(lead + (Ud, K), -1)
+    logp = soft_logp.new_zeros(lead + (Ud, K))
+    ids[..., :n, :] = soft_ids[..., :n, :]
+    logp[..., :n, :] = soft_logp[..., :n, :]
+    ids = torch.where(use[..., None], ids, torch.full_like(ids, -1))
+    logp = torch.where(use[..., None], logp, torch.zeros_like(logp))
+    return ids, logp
 
 
 def image_noise(feats, image_mask, u_img, mask_prob):
@@ -87,7 +131,8 @@ def dialog_train_batch(dialogs, caption_ids, image, params, u_tok=None, u_img=No
     params: select_data, threshold, mask_prob, max_seq_len, max_utt_len.  u_tok fp32 [B, R, max_seq_len] / u_img [B, 37]: the
     uniforms of the [MASK] noise and of the image noise; None: drawn from torch's generator (mask_prob == 0 needs none); False:
     never drawn (the call then raises if mask_prob > 0).  image_label / image_target are dead inputs of the enc_dec path and are
-    not produced."""
+    not produced.  Dialogs generated with soft_top_k carry the teacher's soft labels: the batch then has dec_soft_ids / dec_soft_logp
+    [B, R, 1, Ud, K] (`align_soft_labels`), which `step.forward` hands to the student."""
     ques, ans, ppl = dialogs["questions"], dialogs["answers"], dialogs["ppl"]
     mask_prob = float(params["mask_prob"])
     T, Ud = int(params["max_seq_len"]), int(params.get("max_utt_len", 25))
@@ -121,4 +166,7 @@ def dialog_train_batch(dialogs, caption_ids, image, params, u_tok=None, u_img=No
     out["enc_hist_len"] = rows["enc_hist_len"].unsqueeze(2)
     out["enc_next_sentence_labels"] = torch.full((B, R, 1), -1, dtype=torch.long, device=dev)
     out["enc_image_feat"], out["enc_image_loc"], out["enc_image_mask"] = feats, img["enc_image_loc"], img["enc_image_mask"]
+    if dialogs.get("soft_ids") is not None:
+        sid, slp = align_soft_labels(dialogs["soft_ids"], dialogs["soft_logp"], dialogs["soft_tgt"], rows["dec_labels"])
+        out["dec_soft_ids"], out["dec_soft_logp"] = sid.unsqueeze(2), slp.unsqueeze(2)
     return out

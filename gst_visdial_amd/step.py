@@ -13,6 +13,7 @@ import contextlib
 import torch
 
 _TEXT_KEYS = ("enc_input_ids", "enc_segments", "enc_att_mask", "dec_input_ids", "dec_att_mask")
+_SOFT_KEYS = ("dec_soft_ids", "dec_soft_logp")            # the teacher's soft labels (selftrain.dialog_train_batch), optional
 
 
 def select_rows(batch, params, sample_indices=None, generator=None):
@@ -35,6 +36,10 @@ def select_rows(batch, params, sample_indices=None, generator=None):
         out = {k: v[sample_indices] for k, v in flat.items()}
         if train:
             out["dec_labels"] = labels[sample_indices]
+        for k in _SOFT_KEYS:                              # [B, rounds, 1, U, K] -> [rows, U, K], like any decoder tensor
+            if batch.get(k) is not None:
+                v = batch[k]
+                out[k] = v.reshape((-1,) + tuple(v.shape[-2:]))[sample_indices.to(v.device)]
         for k, tail in (("enc_image_feat", 2), ("enc_image_loc", 2), ("enc_image_mask", 1)):
             v = batch[k]
             if v.dim() == tail + 1:                       # unexpanded [B, ...]: row r -> dialog r // rows_per_dialog
@@ -191,14 +196,15 @@ def prefetch(loader, params, stager, generator=None):
         yield stager.upload(pending)
 
 
-def forward(model, batch, params, sample_indices=None, generator=None, stager=None):
+def forward(model, batch, params, sample_indices=None, generator=None, stager=None, distill_alpha=0.5, distill_temperature=1.0):
     """lm_loss, lm_scores = forward(model, batch, params)  -- drop-in for train_gen.forward.
-    `stager` (a PinnedStager): rows go through pinned memory and the copy stream instead of pageable synchronous copies."""
+    `stager` (a PinnedStager): rows go through pinned memory and the copy stream instead of pageable synchronous copies.
+    A batch that carries dec_soft_ids / dec_soft_logp trains on the distillation loss under distill_alpha / distill_temperature."""
     rows, _ = select_rows(batch, params, sample_indices, generator)
-    return forward_rows(model, rows, params, stager)
+    return forward_rows(model, rows, params, stager, distill_alpha, distill_temperature)
 
 
-def forward_rows(model, rows, params, stager=None):
+def forward_rows(model, rows, params, stager=None, distill_alpha=0.5, distill_temperature=1.0):
     dev = params["device"]
     if all((not torch.is_tensor(v)) or v.is_cuda for v in rows.values()):
         pass                                          # already staged (prefetch)
@@ -206,11 +212,15 @@ def forward_rows(model, rows, params, stager=None):
         rows = stager.get(stager.put(rows))
     else:
         rows = {k: v.to(dev) for k, v in rows.items()}
+    soft = {}
+    if rows.get("dec_soft_ids") is not None or rows.get("dec_soft_logp") is not None:
+        soft = dict(dec_soft_ids=rows.get("dec_soft_ids"), dec_soft_logp=rows.get("dec_soft_logp"), distill_alpha=distill_alpha,
+                    distill_temperature=distill_temperature)
     loss, scores = model(
         enc_image_features=rows["enc_image_feat"], enc_image_spatials=rows["enc_image_loc"],
         enc_image_mask=rows["enc_image_mask"], enc_input_ids=rows["enc_input_ids"], enc_segments=rows["enc_segments"],
         enc_attention_mask=rows["enc_att_mask"], dec_input_ids=rows["dec_input_ids"],
-        dec_attention_mask=rows["dec_att_mask"], dec_labels=rows.get("dec_labels"))
+        dec_attention_mask=rows["dec_att_mask"], dec_labels=rows.get("dec_labels"), **soft)
     if "train" in params["mode"]:
         loss = loss.mean()
     return loss, scores

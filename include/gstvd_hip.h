@@ -637,6 +637,43 @@ int64_t gstvd_vocab_argmax_ws_bytes(int64_t n, int64_t V);
 int gstvd_vocab_argmax(const void* X, int64_t ldx, const void* W, int64_t ldw, const float* bias, int64_t n, int64_t V, int64_t H,
                        int32_t dtype, void* ws, int64_t ws_bytes, int64_t* idx, float* val, gstvd_stream_t s);
 
+/* ---- soft pseudo-labels of the self-training loop (entry points added, no signature changed: ABI stays 9) ------------------------
+ * The reference closes its self-training loop through JSON text and hands the student one sampled token per position; this is the
+ * build's own rule.  The teacher hands over the K best tokens of every position with their log-probabilities (sparse: 12 K bytes
+ * per token), the student trains on the hard-label cross entropy mixed with the KL divergence to that distribution.
+ *
+ * topk_logp (teacher): per row m of logits [M, ldl >= V] (GSTVD_F32 or GSTVD_BF16) with lse[m] as gstvd_ce_fwd saved it:
+ *   ids [M, K] int64, logp [M, K] fp32 (dense), logp = x[id] - lse[m] in fp32; the K largest entries of the row under the total order
+ *   (value descending, then smaller id), best first; -inf logits take part in the same order, so a row with fewer than K finite
+ *   values ends in -inf entries.  Inputs are assumed free of NaN (a NaN never wins).  The row is read once and lives in registers.
+ *   K < 1, K > 16 or K > V: GSTVD_E_SHAPE; V > 32768: GSTVD_E_UNSUPPORTED; ldl, alignment and dtype as the cross-entropy entries.
+ *
+ * distill_fwd (student), after gstvd_ce_fwd on the same logits and labels, whose row_loss it takes as ce_row_loss:
+ *   a token is KEPT exactly when the cross entropy keeps it (label != ignore_index and inside [0, V)); a kept token HAS A SOFT LABEL
+ *   when soft_ids[m, 0] >= 0 and every one of its K ids lies in [0, V) (no logit is ever read through an id outside it).
+ *   Kept with a soft label:  q = softmax_k(soft_logp[m, :] * inv_tau) over the K entries (fp32, max-subtracted),
+ *     lse_tau[m] = logsumexp_v(x[m, v] * inv_tau) over the full vocabulary,
+ *     row_kd[m]  = sum_k q_k * (log q_k - (x[m, id_k] * inv_tau - lse_tau[m])), terms with q_k == 0 exactly 0;
+ *   elsewhere row_kd[m] = lse_tau[m] = 0.  Duplicate ids in one row count as separate entries.
+ *   row_loss[m] = (1 - a_m) * ce_row_loss[m] + a_m * tau^2 * row_kd[m], a_m = alpha where the token has a soft label, 0 otherwise
+ *   (a_m == 0: ce_row_loss[m] itself, bit for bit);  stats_out = [sum of row_loss, rows with label != ignore_index, their quotient]
+ *   by the cross entropy's reduction, so stats_out[1] is its stats[1].  soft_ids [M, K] int64, soft_logp [M, K] fp32, dense.
+ *   1 <= K <= 16, 0 <= alpha <= 1, 0 < inv_tau < inf, else GSTVD_E_SHAPE; ldl, alignment, dtype as the cross-entropy entries.
+ *
+ * distill_bwd: ONE launch writes dlogits [M, ldd] once; gs = gscale[0] (NULL: 1), count = stats[1]:
+ *   d[m, v] = gs / count * ( (1 - a_m) * (softmax(x)[v] - [v == label]) + a_m * tau * (softmax(x / tau)[v] - sum_k q_k [v == id_k]) )
+ *   columns V..ldd-1 zero filled, rows that are not kept stored as zeros; a token with a_m == 0 goes through the cross entropy's own
+ *   row routine: its row is the bits gstvd_ce_bwd's mean form writes.  lse as gstvd_ce_fwd saved it, lse_tau as distill_fwd did. */
+int gstvd_topk_logp(const void* logits, int64_t ldl, const float* lse, int64_t M, int64_t V, int64_t K, int32_t dtype, int64_t* ids,
+                    float* logp, gstvd_stream_t s);
+int gstvd_distill_fwd(const void* logits, int64_t ldl, const int64_t* labels, const int64_t* soft_ids, const float* soft_logp,
+                      int64_t M, int64_t V, int64_t K, int64_t ignore_index, float alpha, float inv_tau, int32_t dtype,
+                      const float* ce_row_loss, float* row_loss, float* row_kd, float* lse_tau, float* stats_out, gstvd_stream_t s);
+int gstvd_distill_bwd(const void* logits, int64_t ldl, const int64_t* labels, const int64_t* soft_ids, const float* soft_logp,
+                      const float* lse, const float* lse_tau, const float* stats, const float* gscale, int64_t M, int64_t V,
+                      int64_t K, int64_t ignore_index, float alpha, float inv_tau, int32_t dtype, void* dlogits, int64_t ldd,
+                      gstvd_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
