@@ -12,6 +12,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libgstvd_hip.so")
 ABI_VERSION = 9
 
 F32, BF16 = 0, 1
+COS_TOPK_AUTO, COS_TOPK_MANY, COS_TOPK_FEW = 0, 1, 2
 EPI_BIAS, EPI_ADD, EPI_GELU, EPI_DGELU, EPI_DROPOUT = 1, 2, 4, 8, 16
 EPI_COLSUM, EPI_COLSUM_ACC = 32, 64
 EPI_ADAMW = 128
@@ -130,6 +131,16 @@ class DialogRowsDesc(C.Structure):
                 ("select_data", _i32), ("reserved_", _i32)]
 
 
+class SubseqReplaceDesc(C.Structure):
+    """gstvd_subseq_replace_t: id-level substitutions inside one utterance of every context row, one launch."""
+    _fields_ = [("ids", _vp), ("ld_ids", _i64), ("out_ids", _vp), ("ld_out", _i64), ("n_replaced", _vp),
+                ("row_ptr", _vp), ("subs", _vp), ("pieces", _vp), ("cont", _vp), ("n_vocab", _i64),
+                ("cls", _i64), ("sep", _i64), ("pad", _i64),
+                ("segments", _vp), ("ld_seg", _i64), ("start_seg", _vp), ("ld_start", _i64),
+                ("sep_indices", _vp), ("ld_sep", _i64), ("att_mask", _vp), ("ld_att", _i64),
+                ("n", _i32), ("T", _i32), ("n_subs", _i32), ("n_pieces", _i32), ("max_sep", _i32), ("reserved_", _i32)]
+
+
 class ColsumEntry(C.Structure):
     _fields_ = [("partial", _vp), ("out", _vp * 3), ("nblk", _i64), ("stride", _i64), ("H", _i64),
                 ("nvec", _i32), ("accumulate", _i32 * 3), ("blk0", _i32)]
@@ -207,6 +218,10 @@ SIGNATURES = {
     "gstvd_vocab_argmax": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _i32, _vp, _i64, _vp, _vp, _vp]),
     "gstvd_topk_logp": (_i32, [_vp, _i64, _vp, _i64, _i64, _i64, _i32, _vp, _vp, _vp]),
     "gstvd_distill_fwd": (_i32, [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _f32, _f32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gstvd_cos_topk_route": (_i32, [_i64, _i64]),
+    "gstvd_cos_topk_ws_bytes": (_i64, [_i64, _i64, _i32]),
+    "gstvd_cos_topk": (_i32, [_vp, _i64, _i64, _i64, _vp, _i64, _i32, _f32, _i32, _vp, _i64, _vp, _vp, _vp]),
+    "gstvd_subseq_replace": (_i32, [C.POINTER(SubseqReplaceDesc), _vp]),
     "gstvd_distill_bwd": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _f32, _f32, _i32, _vp, _i64, _vp]),
 }
 

@@ -17,8 +17,17 @@ What differs from the script, none of it in the numbers it defines:
 LM and scores the options on the filled-in context.  The masked LM is not part of this package's weights: the caller builds a
 `mlm.MaskedLMFiller` from a BertForMaskedLM state dict and passes it as `textattack=` (or params["textattack"]).  The filled
 chunk is row 0 repeated, so when its segments and attention masks are also one row repeated it is scored with ONE encoder pass
-(score_candidates), where the reference runs 100.  Without a filler `random_token` raises, as `coreference` always does: that
-one needs counter-fitted word vectors and host-side string work (utils/text_attack.py), neither of which is here.
+(score_candidates), where the reference runs 100.  Without a filler `random_token` raises.
+
+`coreference` (evaluate_gen_attack.py:167-206, utils/text_attack.py:58-100) replaces, in the round that carries the relevance
+scores, the words of the chunk's coreference dependencies by their nearest counter-fitted neighbour inside the utterances of
+their dialog round, on row 0, and repeats that row over the chunk.  Neither the word vectors nor a tokenizer are part of this
+package: the caller builds a `synonyms.CorefSubstituter` (a `SynonymTable` of the vectors -- nearest neighbours by a fused
+product + top-K kernel, never the V x V matrix -- and its tokenizer's word -> wordpiece-ids map) and passes it as `coref=` (or
+params["coref"]); the substitution runs on token ids on the device.  By default only the ids change, as in the reference
+(segments, separator positions and mask stay as loaded); a substituter built with refresh=True recomputes them from the new ids.
+Without a substituter `coreference` raises; a masked-LM filler is not one.  INTEGRATION.md lists the departures from the
+reference's string-level substitution.
 """
 import contextlib
 
@@ -122,26 +131,49 @@ def _filled_ids(filler, batch):
     return filler.fill(ids, _flat(batch["enc_segments"], 1), _flat(batch["enc_att_mask"], 1), rows=filler.host_rows(ids[:1]))
 
 
-def forward_attack(model, batch, params, epsilon=1.0, inputs_only=True, textattack=None):
-    """The `fgsm` and `random_token` branches of evaluate_gen_attack.forward (evaluate_gen_attack.py:28-165, 209-226) -> lm_scores
-    [rows, U, vocab].  `batch`: one chunk of the eval loader's rows (host tensors) with its dialog's `round_id` and
-    `gt_relevance`.  `textattack`: the masked-LM filler of `random_token` (mlm.MaskedLMFiller, or anything with its `fill` and
-    `host_rows`); also read from params["textattack"]."""
+def _substituter(params, coref):
+    return coref if coref is not None else params.get("coref")
+
+
+def _coref_context(sub, batch):
+    """coreference: what the attacked round's chunk feeds the encoder instead of the loader's tensors -- {model keyword: [1, .]
+    device tensor}, row 0 with the substitutions made (text_attack.py:63, 90: the caller repeats it over the chunk).  No
+    dependencies: nothing changes (text_attack.py:66), {} is returned.  The loader's tensors are not written."""
+    dep = batch.get("coref_dependency")
+    if not dep:
+        return {}
+    ids = _flat(batch["enc_input_ids"], 1)
+    if getattr(sub, "refresh", False):
+        out = sub.attack_row(ids, dep, refresh=True, segments=_flat(batch["enc_segments"], 1))
+        return dict(zip(("enc_input_ids", "enc_segments", "enc_sep_indices", "enc_attention_mask"), out))
+    return {"enc_input_ids": sub.attack_row(ids, dep)}
+
+
+def forward_attack(model, batch, params, epsilon=1.0, inputs_only=True, textattack=None, coref=None):
+    """The branches of evaluate_gen_attack.forward (evaluate_gen_attack.py:28-226) -> lm_scores [rows, U, vocab].  `batch`: one
+    chunk of the eval loader's rows (host tensors) with its dialog's `round_id` and `gt_relevance` and, for `coreference`, the
+    chunk's `coref_dependency` ({round: word}).  `textattack`: the masked-LM filler of `random_token` (mlm.MaskedLMFiller, or
+    anything with its `fill` and `host_rows`); also read from params["textattack"].  `coref`: the substituter of `coreference`
+    (synonyms.CorefSubstituter, or anything with its `attack_row`); also read from params["coref"]."""
     attack = params.get("attack")
     filler = _filler(params, textattack)
-    if attack == "coreference" or (attack == "random_token" and filler is None):
+    sub = _substituter(params, coref)
+    if (attack == "coreference" and sub is None) or (attack == "random_token" and filler is None):
         raise NotImplementedError(
             "attack=%r is a text attack (utils/text_attack.py): it needs a pretrained BertForMaskedLM, the counter-fitted word "
             "vectors (cos_sim_counter_fitting, cos_sim_idx2word, cos_sim_word2idx)%s, none of which this package carries.  "
             "Only attack='fgsm' is implemented without further inputs; attack='random_token' runs once a masked-LM filler is "
-            "supplied as textattack= (gst_visdial_amd.mlm.MaskedLMFiller, loaded from a BertForMaskedLM state dict)"
+            "supplied as textattack= (gst_visdial_amd.mlm.MaskedLMFiller, loaded from a BertForMaskedLM state dict).  "
+            "attack='coreference' runs once a substituter is supplied as coref= (gst_visdial_amd.synonyms.CorefSubstituter: a "
+            "SynonymTable built from the word vectors and the tokenizer's word -> wordpiece-ids map)"
             % (attack, " and the coreference dependencies" if attack == "coreference" else ""))
-    if attack not in ("fgsm", "random_token"):
-        raise NotImplementedError("attack=%r: no such attack (the reference has 'fgsm', 'coreference', 'random_token'; only "
-                                  "'fgsm' and, with a filler, 'random_token' are implemented)" % (attack,))
+    if attack not in ("fgsm", "random_token", "coreference"):
+        raise NotImplementedError("attack=%r: no such attack (the reference has 'fgsm', 'coreference', 'random_token'; 'fgsm' "
+                                  "is implemented as it stands, 'random_token' with a filler, 'coreference' with a substituter)" % (attack,))
     dev = params["device"]
     text = attack == "random_token"
-    hit = (not text) and attacked_round(batch)                   # on the host tensors: no device round trip
+    this_round = (not text) and attacked_round(batch)            # on the host tensors: no device round trip
+    hit = attack == "fgsm" and this_round
     kw = dict.fromkeys(_MODEL_KEYS)
     kw.update(enc_input_ids=_filled_ids(filler, batch).to(dev) if text else _flat(batch["enc_input_ids"], 1).to(dev), enc_segments=_flat(batch["enc_segments"], 1).to(dev),
               enc_sep_indices=_flat(batch["enc_sep_indices"], 1).to(dev), enc_mlm_labels=_flat(batch["enc_mlm_labels"], 1).to(dev),
@@ -152,6 +184,10 @@ def forward_attack(model, batch, params, epsilon=1.0, inputs_only=True, textatta
               enc_image_mask=_flat(batch["enc_image_mask"], 1).to(dev))
     if hit:
         kw["enc_image_features"] = fgsm_features(model, kw, batch["gt_relevance"], epsilon, inputs_only=inputs_only)
+    if attack == "coreference" and this_round:                   # only the round that carries the relevance scores is attacked
+        rows = kw["enc_input_ids"].shape[0]
+        for k, v in _coref_context(sub, batch).items():
+            kw[k] = v.to(dev).repeat(rows, 1)
     _, lm_scores = model(**kw)
     return lm_scores
 
@@ -160,10 +196,11 @@ def _same_context(batch, keys=("enc_input_ids", "enc_segments", "enc_att_mask"))
     return all(bool((batch[k] == batch[k][:1]).all()) for k in keys)
 
 
-def score_chunk(model, item, params, epsilon, textattack=None):
+def score_chunk(model, item, params, epsilon, textattack=None, coref=None):
     """Scores [rows] of one chunk: the script's lines 321-333 for the round FGSM attacks, one encoder pass for any other.
     random_token: every chunk is filled in; the filled context is row 0 repeated, so it takes the one-pass route whenever the
-    chunk's segments and attention masks are one row repeated too (they are in the eval loader's chunks)."""
+    chunk's segments and attention masks are one row repeated too (they are in the eval loader's chunks).  coreference: the
+    attacked round's context is row 0 repeated as well and takes the same route under the same condition."""
     dev = params["device"]
     core = _core(model)
     ids = item["dec_input_ids"]
@@ -174,10 +211,24 @@ def score_chunk(model, item, params, epsilon, textattack=None):
         else:
             many = False
             item = dict(item, enc_input_ids=_filled_ids(filler, item)[:1])
+    elif params.get("attack") == "coreference":
+        sub = _substituter(params, coref)
+        if sub is None:
+            many = True                                       # (forward_attack raises, naming what is missing)
+        elif not (attacked_round(item) and item.get("coref_dependency")):
+            many = not _same_context(item)                    # not attacked: scored as evaluate.py scores it
+        elif not _same_context(item, ("enc_segments", "enc_att_mask")):
+            many = True
+        else:
+            many = False
+            new = _coref_context(sub, item)
+            item = dict(item, enc_input_ids=new["enc_input_ids"])
+            if "enc_segments" in new:
+                item.update(enc_segments=new["enc_segments"], enc_att_mask=new["enc_attention_mask"])
     else:
         many = attacked_round(item) or not _same_context(item)
     if many:
-        forward_attack(model, item, params, epsilon, textattack=textattack)
+        forward_attack(model, item, params, epsilon, textattack=textattack, coref=coref)
         last = core.engine.last          # the second forward's logits and their log-sum-exp, still in the arena
         scores = torch.empty(ids.shape[0], dtype=torch.float32, device=dev)
         ops.answer_scores(last["logits"].t, last["lse"], ids.to(dev).contiguous(), ids.shape[0], ids.shape[1], scores)
@@ -189,14 +240,22 @@ def score_chunk(model, item, params, epsilon, textattack=None):
 
 
 @torch.no_grad()
-def evaluate_attack(model, dataloader, params, epsilon=1.0, mode="vd_eval_val", textattack=None):
-    """The loop of evaluate_gen_attack.evaluate (evaluate_gen_attack.py:233-369) for attack='fgsm' and, with a masked-LM filler
-    (`textattack=` or params["textattack"]), attack='random_token': chunks of 100 option rows, the metrics of metrics.py;
-    -> (ranks_json, metrics) as evaluate.evaluate returns them."""
-    if params.get("attack") != "fgsm" and not (params.get("attack") == "random_token" and _filler(params, textattack) is not None):
+def evaluate_attack(model, dataloader, params, epsilon=1.0, mode="vd_eval_val", textattack=None, coref=None, coref_dependency=None):
+    """The loop of evaluate_gen_attack.evaluate (evaluate_gen_attack.py:233-369) for attack='fgsm', with a masked-LM filler
+    (`textattack=` or params["textattack"]) attack='random_token', and with a substituter (`coref=` or params["coref"])
+    attack='coreference': chunks of 100 option rows, the metrics of metrics.py; -> (ranks_json, metrics) as evaluate.evaluate
+    returns them.  `coref_dependency`: the reference's dependency file, indexed [dialog]['coreference'][chunk] with the dialogs
+    numbered in the loader's order (evaluate_gen_attack.py:318-319); a chunk's entry is a {round: word} dict, possibly empty."""
+    attack = params.get("attack")
+    ready = attack == "fgsm" or (attack == "random_token" and _filler(params, textattack) is not None) \
+        or (attack == "coreference" and _substituter(params, coref) is not None)
+    if not ready:
         forward_attack(model, {}, params)           # raises, naming what is missing
+    if attack == "coreference" and coref_dependency is None:
+        raise ValueError("evaluate_attack: attack='coreference' needs coref_dependency= (per dialog, per chunk, a {round: word} dict)")
     sparse, ndcg, ranks_json = SparseGTMetrics(), NDCG(), []
     model.eval()
+    dialog_no = 0
     for batch in dataloader:
         ids = batch["enc_input_ids"]
         Bd, rounds, options = ids.shape[0], ids.shape[1], ids.shape[2]
@@ -216,7 +275,10 @@ def evaluate_attack(model, dataloader, params, epsilon=1.0, mode="vd_eval_val", 
                 item["enc_image_mask"] = batch["enc_image_mask"][d:d + 1].expand(ROWS_PER_CALL, -1)
                 item["round_id"] = batch["round_id"][d:d + 1]
                 item["gt_relevance"] = batch["gt_relevance"][d]
-                out.append(score_chunk(model, item, params, epsilon, textattack=textattack))
+                if attack == "coreference":
+                    item["coref_dependency"] = coref_dependency[dialog_no + d]["coreference"][j]
+                out.append(score_chunk(model, item, params, epsilon, textattack=textattack, coref=coref))
+        dialog_no += Bd
         scores = torch.cat(out, 0).view(Bd, rounds, options)
         if mode == "vd_eval_val":
             sparse.observe(scores, batch["gt_option_inds"])

@@ -1585,3 +1585,138 @@ def gemm_ln_ok(M, N, H, dtype):
     # one round of the chip: two workgroups (16 rows x 128 columns) fit a CU; beyond 512 the second round doubles the launch
     # (N = 3072 at 400 rows: 22 us forward / 38 us backward against 23 / 26 us for the two separate kernels)
     return ((M + 15) // 16) * ((N + 127) // 128) <= 512
+
+
+# ---- coreference text attack: nearest neighbours by cosine, id-level substitution --------------------------------------------
+COS_TOPK_ROUTES = {"many": L.COS_TOPK_MANY, "few": L.COS_TOPK_FEW}
+COS_TOPK_CENSUS = {"many": 0, "few": 0}      # launches per route so far (the tests' census that both routes ran)
+SUBSEQ_MAX_PIECES = 16
+
+
+def cos_topk_route(n, V):
+    """The route gstvd_cos_topk takes for n source rows when none is forced: "many" or "few"."""
+    return "many" if L.load().gstvd_cos_topk_route(n, V) == L.COS_TOPK_MANY else "few"
+
+
+def cos_topk_ws_bytes(n, V, K):
+    return int(L.load().gstvd_cos_topk_ws_bytes(n, V, K))
+
+
+def cos_topk(ehat, src=None, K=10, threshold=0.5, route=None, V=None, D=None, idx=None, val=None, ws=None):
+    """(idx int32 [n, K], val fp32 [n, K]): per source row the K best targets t != src[r] of the unit rows ehat[:V, :D] (fp32,
+    dense rows, row stride a multiple of 4) with dot >= threshold, larger value first, then the smaller index; unused slots
+    idx -1 / val 0 (gstvd_cos_topk; the rule is stated in include/gstvd_hip.h).  src int32 [n] on the device, or None: every row of
+    the table is a source.  threshold None or -inf: no cut.  route None (chosen from n), "many" or "few": both return the same
+    bits.  idx / val / ws (uint8, at least cos_topk_ws_bytes(n, V, K) bytes, "few" only): the caller's buffers, else allocated."""
+    lib = L.load()
+    if not isinstance(ehat, torch.Tensor) or ehat.dtype != torch.float32 or ehat.dim() != 2 or ehat.stride(1) != 1:
+        raise L.GstvdError("cos_topk: ehat must be fp32 [V, D] with dense rows")
+    V = ehat.shape[0] if V is None else int(V)
+    D = ehat.shape[1] if D is None else int(D)
+    if not (1 <= V <= ehat.shape[0]) or not (1 <= D <= ehat.shape[1]):
+        raise L.GstvdError("cos_topk: V = %d, D = %d do not lie inside ehat %s" % (V, D, tuple(ehat.shape)))
+    if src is None:
+        n = V
+    else:
+        if src.dtype != torch.int32 or src.dim() != 1 or not src.is_contiguous():
+            raise L.GstvdError("cos_topk: src must be a contiguous int32 vector")
+        n = src.numel()
+    K = int(K)
+    if route not in (None, "many", "few"):
+        raise L.GstvdError("cos_topk: route must be None, 'many' or 'few' (got %r)" % (route,))
+    idx = torch.empty(n, K, dtype=torch.int32, device=ehat.device) if idx is None else idx
+    val = torch.empty(n, K, dtype=torch.float32, device=ehat.device) if val is None else val
+    if (idx.dtype != torch.int32 or val.dtype != torch.float32 or tuple(idx.shape) != (n, K) or tuple(val.shape) != (n, K)
+            or not idx.is_contiguous() or not val.is_contiguous()):
+        raise L.GstvdError("cos_topk: idx (int32) and val (fp32) must be contiguous [%d, %d]" % (n, K))
+    if n == 0:
+        return idx, val
+    name = route if route is not None else cos_topk_route(n, V)
+    nbytes = 0
+    if name == "few":
+        need = cos_topk_ws_bytes(n, V, K)
+        if ws is None:
+            ws = torch.empty(max(need, 8), dtype=torch.uint8, device=ehat.device)
+        nbytes = ws.numel() * ws.element_size()
+    else:
+        ws = None
+    thr = float("-inf") if threshold is None else float(threshold)
+    e0 = _prof_begin()
+    L.check("gstvd_cos_topk", lib.gstvd_cos_topk(_p(ehat), ehat.stride(0) if ehat.shape[0] > 1 else max(ehat.stride(0), D), V, D,
+                                                 _p(src), n, K, thr, COS_TOPK_ROUTES[name], _p(ws), nbytes, _p(idx), _p(val),
+                                                 _stream()))
+    _prof_end(e0, "cos_topk_" + name, 2.0 * n * V * D, float(V) * D * 4, (n, V, D, K))
+    COS_TOPK_CENSUS[name] += 1
+    return idx, val
+
+
+def pack_substitutions(plans, device):
+    """The CSR form gstvd_subseq_replace reads, from `plans`: per row a list of (utterance, a ids, b ids).  Checked on the host:
+    1 <= len(a), len(b) <= 16 and a non-negative utterance.  -> (row_ptr int32 [n + 1], subs int32 [S, 4], pieces int64) on
+    `device`."""
+    row_ptr, subs, pieces = [0], [], []
+    for r, plan in enumerate(plans):
+        for u, a, b in plan:
+            a, b = [int(x) for x in a], [int(x) for x in b]
+            if int(u) < 0 or not (1 <= len(a) <= SUBSEQ_MAX_PIECES) or not (1 <= len(b) <= SUBSEQ_MAX_PIECES):
+                raise L.GstvdError("subseq_replace: row %d: utterance %r with %d -> %d pieces (an utterance >= 0 and 1..%d pieces "
+                                   "on either side are needed)" % (r, u, len(a), len(b), SUBSEQ_MAX_PIECES))
+            subs.append([int(u), len(pieces), len(a), len(b)])
+            pieces.extend(a + b)
+        row_ptr.append(len(subs))
+    return (torch.tensor(row_ptr, dtype=torch.int32).to(device),
+            torch.tensor(subs, dtype=torch.int32).reshape(-1, 4).to(device),
+            torch.tensor(pieces, dtype=torch.int64).to(device))
+
+
+def subseq_replace(ids, plans, cls=101, sep=102, pad=0, cont=None, out=None, n_replaced=None, segments=None, sep_indices=None,
+                   att_mask=None, start_seg=None):
+    """(out_ids int64 [n, T], n_replaced int32 [n]): the substitutions of `plans` applied to the context rows ids int64 [n, T], one
+    launch, one workgroup per row (gstvd_subseq_replace; the rule is stated in include/gstvd_hip.h).  plans: per row a list of
+    (utterance, a ids, b ids), or what pack_substitutions returned.  cont: uint8 [vocab] on the device, 1 for a "##" piece (None:
+    no word-boundary condition).  segments int64 [n, T], sep_indices int64 [n, max_sep], att_mask fp32 [n, T]: written when given,
+    recomputed from out_ids; start_seg int64 [n] (row stride free): each row's first segment (None: 0).  ids is never written."""
+    who = "subseq_replace"
+    lib = L.load()
+    _rows_i64(who, "ids", ids)
+    n, T = ids.shape
+    row_ptr, subs, pieces = plans if isinstance(plans, tuple) else pack_substitutions(plans, ids.device)
+    if row_ptr.dtype != torch.int32 or row_ptr.numel() != n + 1 or subs.dtype != torch.int32 or pieces.dtype != torch.int64 \
+            or not (row_ptr.is_contiguous() and subs.is_contiguous() and pieces.is_contiguous()) or subs.numel() % 4:
+        raise L.GstvdError("%s: row_ptr int32 [%d], subs int32 [S, 4] and pieces int64 are needed" % (who, n + 1))
+    out = torch.empty(n, T, dtype=torch.int64, device=ids.device) if out is None else _rows_i64(who, "out", out, T)
+    n_replaced = torch.empty(n, dtype=torch.int32, device=ids.device) if n_replaced is None else _flag_vec(who, "n_replaced", n_replaced, n, torch.int32)
+    if out.shape[0] != n:
+        raise L.GstvdError("%s: out must be [%d, %d]" % (who, n, T))
+    if n == 0:
+        return out, n_replaced
+    d = L.SubseqReplaceDesc()
+    d.ids, d.ld_ids, d.out_ids, d.ld_out, d.n_replaced = _p(ids), max(ids.stride(0), T), _p(out), max(out.stride(0), T), _p(n_replaced)
+    d.row_ptr, d.subs, d.pieces = _p(row_ptr), (_p(subs) if subs.numel() else None), (_p(pieces) if pieces.numel() else None)
+    d.n_subs, d.n_pieces = subs.numel() // 4, pieces.numel()
+    if cont is not None:
+        if cont.dtype != torch.uint8 or cont.dim() != 1 or not cont.is_contiguous() or cont.numel() < 1:
+            raise L.GstvdError("%s: cont must be a contiguous uint8 vector over the vocabulary" % who)
+        d.cont, d.n_vocab = _p(cont), cont.numel()
+    d.cls, d.sep, d.pad = int(cls), int(sep), int(pad)
+    if segments is not None:
+        if _rows_i64(who, "segments", segments, T).shape[0] != n:
+            raise L.GstvdError("%s: segments must be [n, T]" % who)
+        d.segments, d.ld_seg = _p(segments), max(segments.stride(0), T)
+    if att_mask is not None:
+        if _rows_i64(who, "att_mask", att_mask, T, torch.float32).shape[0] != n:
+            raise L.GstvdError("%s: att_mask must be [n, T]" % who)
+        d.att_mask, d.ld_att = _p(att_mask), max(att_mask.stride(0), T)
+    if sep_indices is not None:
+        if _rows_i64(who, "sep_indices", sep_indices).shape[0] != n:
+            raise L.GstvdError("%s: sep_indices must be [n, max_sep]" % who)
+        d.sep_indices, d.ld_sep, d.max_sep = _p(sep_indices), max(sep_indices.stride(0), sep_indices.shape[1]), sep_indices.shape[1]
+    if start_seg is not None:
+        if start_seg.dtype != torch.int64 or start_seg.dim() != 1 or start_seg.numel() != n:
+            raise L.GstvdError("%s: start_seg must be int64 [n]" % who)
+        d.start_seg, d.ld_start = _p(start_seg), start_seg.stride(0)
+    d.n, d.T = n, T
+    e0 = _prof_begin()
+    L.check("gstvd_subseq_replace", lib.gstvd_subseq_replace(C.byref(d), _stream()))
+    _prof_end(e0, "subseq_replace", 0.0, 16.0 * n * T, (n, T))
+    return out, n_replaced

@@ -674,6 +674,66 @@ int gstvd_distill_bwd(const void* logits, int64_t ldl, const int64_t* labels, co
                       int64_t K, int64_t ignore_index, float alpha, float inv_tau, int32_t dtype, void* dlogits, int64_t ldd,
                       gstvd_stream_t s);
 
+/* ---- coreference text attack (utils/text_attack.py:58-116; entry points added, no signature changed: ABI stays 9) ---------------
+ * cos_topk: the K nearest neighbours by cosine of n source rows of a table of UNIT rows, without the V x V matrix the reference
+ * stores.  Ehat fp32 [>= V, ld >= D] row-major; src int32 [n], or NULL: source r is row r and n must equal V.
+ *   idx int32 [n, K], val fp32 [n, K] (dense): row r holds the K best targets t in [0, V), t != src[r], with
+ *   dot(Ehat[src[r]], Ehat[t]) >= threshold, under ONE total order -- the larger value first, equal values to the SMALLER index (the
+ *   order of the vocabulary arg-max above) -- best first; unused slots hold idx = -1, val = 0.  threshold = -inf: no cut.  A source
+ *   index outside [0, V) reads no memory and gives a row of unused slots.  Inputs are assumed finite.  Columns D..ld-1 and rows at
+ *   or beyond V are never read.
+ * The products run on the f32-input MFMA (exact fp32, one rounding per product).  A pair's D products are added in one fixed order
+ * (k = 16 s + 4 g + e: s ascending, then e = 0..3, then g = 0..3) on both routes, so both return the same bits:
+ *   GSTVD_COS_TOPK_MANY: a workgroup owns 32 source rows and streams all V targets past them, keeping every row's running K best;
+ *                        the workspace is not used (ws may be NULL);
+ *   GSTVD_COS_TOPK_FEW : the targets are split over workgroups; every split leaves a partial list per row in `ws`
+ *                        (gstvd_cos_topk_ws_bytes(n, V, K) bytes, 8-byte aligned), a second launch merges them;
+ *   GSTVD_COS_TOPK_AUTO: gstvd_cos_topk_route(n, V) -- MANY from 16384 source rows on, where its workgroups alone fill the chip.
+ * No atomics, every output element is written once, the result does not depend on the order workgroups finish in.
+ * Refused before the launch: a null Ehat / idx / val, or ws on the FEW route (GSTVD_E_NULL); n < 1, V < 1, D < 1, ld < D, K outside
+ * 1..16, src NULL with n != V, a NaN threshold, an unknown route, ws_bytes below the helper's answer (GSTVD_E_SHAPE); D > 512 (the
+ * source rows of a workgroup live in LDS; 300, the counter-fitted vectors' width, fits), V or n > 2^30 (GSTVD_E_UNSUPPORTED); D or
+ * ld no multiple of 4, Ehat not 16-byte aligned (GSTVD_E_ALIGN). */
+enum { GSTVD_COS_TOPK_AUTO = 0, GSTVD_COS_TOPK_MANY = 1, GSTVD_COS_TOPK_FEW = 2 };
+int32_t gstvd_cos_topk_route(int64_t n, int64_t V);
+int64_t gstvd_cos_topk_ws_bytes(int64_t n, int64_t V, int32_t K);
+int gstvd_cos_topk(const float* Ehat, int64_t ld, int64_t V, int64_t D, const int32_t* src, int64_t n, int32_t K, float threshold,
+                   int32_t route, void* ws, int64_t ws_bytes, int32_t* idx, float* val, gstvd_stream_t s);
+
+/* subseq_replace: substitutions of wordpiece id sequences inside one utterance of a context row, all rows in one launch, one
+ * workgroup per row; the attack's substitute_word (utils/text_attack.py:93-100) on ids instead of decoded text.
+ * Row r's substitutions are subs[row_ptr[r] .. row_ptr[r + 1]) (row_ptr int32 [n + 1]); substitution i is the four int32
+ * subs[4 i ..] = (u, off, La, Lb): inside utterance u replace a = pieces[off .. off + La) by b = pieces[off + La .. off + La + Lb)
+ * (pieces int64 [n_pieces]), 1 <= La, Lb <= 16.  An entry outside these bounds is skipped, never read through.
+ *  1. a row's substitutions apply in order, each to the result of the one before;
+ *  2. utterance u is the tokens strictly between the u-th and the (u + 1)-th `sep` of the row as it stands; for u = 0 the left
+ *     boundary is position 0 (where `cls` stands; the position is the boundary whatever it holds).  Fewer than u + 1 separators:
+ *     the substitution does nothing;
+ *  3. matches are taken left to right, greedy, non-overlapping, wholly inside the utterance.  With cont (uint8 [n_vocab], 1 for a
+ *     "##" continuation piece; ids outside [0, n_vocab) count as 0) a match also needs cont[first matched token] == 0 and the token
+ *     behind the match to be the utterance's end or a piece with cont == 0;
+ *  4. every match is replaced by b, the tail shifts, tokens pushed past T are dropped, a shorter row is filled with `pad`;
+ *  5. out_ids int64 [n, ld_out >= T] and n_replaced int32 [n] (matches replaced, all substitutions of the row) are always written;
+ *  6. segments int64, sep_indices int64 [n, ld_sep >= max_sep], att_mask fp32 are written when non-NULL, recomputed from out_ids
+ *     by encode_input's rules (utils/data_utils.py:41-71): segments[q] = start_seg[r * ld_start] (NULL: 0) XOR (number of
+ *     separators in front of q, mod 2), 0 on pads; sep_indices = the first max_sep separator positions, then 0; att_mask =
+ *     (out_ids != pad).
+ * No atomics, no workspace, every output element written once; ids is never written (ids == out_ids is refused).
+ * Refused before the launch: null ids / out_ids / n_replaced / row_ptr, null subs or pieces with n_subs > 0 (GSTVD_E_NULL); n < 1,
+ * T < 1, a row stride below its row, cont with n_vocab < 1, sep_indices with max_sep < 1 (GSTVD_E_SHAPE); T > 1024
+ * (GSTVD_E_UNSUPPORTED). */
+typedef struct {
+  const int64_t* ids; int64_t ld_ids;
+  int64_t* out_ids; int64_t ld_out; int32_t* n_replaced;
+  const int32_t* row_ptr; const int32_t* subs; const int64_t* pieces;
+  const uint8_t* cont; int64_t n_vocab;
+  int64_t cls; int64_t sep; int64_t pad;
+  int64_t* segments; int64_t ld_seg; const int64_t* start_seg; int64_t ld_start;
+  int64_t* sep_indices; int64_t ld_sep; float* att_mask; int64_t ld_att;
+  int32_t n; int32_t T; int32_t n_subs; int32_t n_pieces; int32_t max_sep; int32_t reserved_;
+} gstvd_subseq_replace_t;
+int gstvd_subseq_replace(const gstvd_subseq_replace_t* a, gstvd_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
