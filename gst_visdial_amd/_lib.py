@@ -141,6 +141,18 @@ class SubseqReplaceDesc(C.Structure):
                 ("n", _i32), ("T", _i32), ("n_subs", _i32), ("n_pieces", _i32), ("max_sep", _i32), ("reserved_", _i32)]
 
 
+class DiscRowsDesc(C.Structure):
+    """gstvd_disc_rows_t: N rows of the discriminative model from token-id pools, one launch."""
+    _fields_ = [("cap", _vp), ("ld_cap", _i64), ("ques", _vp), ("ans", _vp), ("ld_utt", _i64), ("opts", _vp), ("ld_opt", _i64),
+                ("gt_index", _vp), ("dense_scores", _vp), ("row_dialog", _vp), ("row_round", _vp), ("row_slot", _vp),
+                ("u_tok", _vp), ("ld_u", _i64), ("u_neg", _vp),
+                ("tokens", _vp), ("segments", _vp), ("mask", _vp), ("att", _vp), ("ld_row", _i64),
+                ("sep_indices", _vp), ("ld_sep", _i64), ("hist_len", _vp), ("neg_option", _vp), ("nsp_labels", _vp),
+                ("mask_prob", C.c_double), ("cls", _i64), ("sep", _i64), ("mask_id", _i64), ("N", _i64),
+                ("D", _i32), ("R", _i32), ("O", _i32), ("U", _i32), ("Lc", _i32), ("T", _i32), ("S", _i32),
+                ("tot_rounds", _i32), ("num_options", _i32), ("train", _i32)]
+
+
 class ColsumEntry(C.Structure):
     _fields_ = [("partial", _vp), ("out", _vp * 3), ("nblk", _i64), ("stride", _i64), ("H", _i64),
                 ("nvec", _i32), ("accumulate", _i32 * 3), ("blk0", _i32)]
@@ -222,6 +234,7 @@ SIGNATURES = {
     "gstvd_cos_topk_ws_bytes": (_i64, [_i64, _i64, _i32]),
     "gstvd_cos_topk": (_i32, [_vp, _i64, _i64, _i64, _vp, _i64, _i32, _f32, _i32, _vp, _i64, _vp, _vp, _vp]),
     "gstvd_subseq_replace": (_i32, [C.POINTER(SubseqReplaceDesc), _vp]),
+    "gstvd_disc_rows": (_i32, [C.POINTER(DiscRowsDesc), _vp]),
     "gstvd_distill_bwd": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _f32, _f32, _i32, _vp, _i64, _vp]),
 }
 

@@ -83,6 +83,16 @@ DEVFN float wave_sum(float v) {
   v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x143, 0xc, 0xf, false));  // row_bcast:31 into rows 2, 3
   return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
 }
+// Inclusive prefix sum over the 64 lanes: lane i receives v_0 + .. + v_i (the separator positions of the row builders in dialog.hip
+// and disc_rows.hip: lane i holds len_i + 1).
+DEVFN int wave_scan_incl(int v, int lane) {
+#pragma unroll
+  for (int o = 1; o < WAVE; o <<= 1) {
+    const int up = __shfl_up(v, o, WAVE);
+    if (lane >= o) v += up;
+  }
+  return v;
+}
 // Reductions over the four 16-lane rows of a wave (lanes l, l^16, l^32, l^48), result in every lane: two gfx950 lane swaps
 // inside the VALU instead of two dependent ds_bpermute round trips (~100 cycles each) through the LDS crossbar.
 //   v_permlane16_swap a, b: rows 1, 3 of a <-> rows 0, 2 of b;   v_permlane32_swap a, b: rows 2, 3 of a <-> rows 0, 1 of b.

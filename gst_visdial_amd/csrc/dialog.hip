@@ -85,12 +85,7 @@ __global__ __launch_bounds__(WAVE) void dialog_rows_kernel(gstvd_dialog_rows_t a
     else { for (int c = 0; c < cap; ++c) len += is_special(a, src[c]) ? 0 : 1; }
   }
   // ---- inclusive scan of len + 1: the running position of utterance i's [SEP] (position 0 is [CLS])
-  int sep_pos = lane < n_utt ? len + 1 : 0;
-#pragma unroll
-  for (int o = 1; o < WAVE; o <<= 1) {
-    const int up = __shfl_up(sep_pos, o, WAVE);
-    if (lane >= o) sep_pos += up;
-  }
+  const int sep_pos = wave_scan_incl(lane < n_utt ? len + 1 : 0, lane);
   const int total = __shfl(sep_pos, WAVE - 1, WAVE) + 1;      // untruncated row length
   int64_t* e_ids = a.enc_ids + row * a.ld_enc;
   int64_t* e_seg = a.enc_seg + row * a.ld_enc;

@@ -6,10 +6,14 @@ and the same metrics.  Two things differ, neither changes a result:
   * the image tensors are expanded to one row per option by INDEXING the per-dialog tensors chunk by chunk, not by the
     reference's 100x `.expand(...).contiguous()` copy of the whole batch (evaluate_disc.py:52-58);
   * the ranking probability softmax(nsp_scores, 1)[:, 0] comes out of the head kernel itself (Engine.nsp_scores).
+A batch that carries token-id pools instead of the loader's text tensors (`opts` present, `tokens` absent: disc_rows.is_pooled) has
+its rows built on the device, chunk by chunk (disc_rows.eval_item) or for the sampled train rows (disc_rows.train_batch); a batch
+with `tokens` takes the path below unchanged.
 Index work (sequence lengths, masks, chunk bounds, the row -> dialog map) is integer-exact torch code, restated bit for bit by
 tests/test_disc_cpu.py."""
 import torch
 
+from . import disc_rows
 from .metrics import SparseGTMetrics, NDCGBatchSum, scores_to_ranks
 
 
@@ -55,7 +59,7 @@ def _prepare(item, params):
     features = f.view(-1, f.shape[-2], f.shape[-1]).to(dev)
     spatials = l.view(-1, l.shape[-2], l.shape[-1]).to(dev)
     image_mask = m.view(-1, m.shape[-1]).to(dev)
-    att = sequence_mask(sequence_lengths(sep_indices, hist_len), tokens.shape[1])
+    att = item["att"] if "att" in item else sequence_mask(sequence_lengths(sep_indices, hist_len), tokens.shape[1])
     return tokens, features, spatials, sep_indices, segments, mask, att, image_mask
 
 
@@ -92,8 +96,9 @@ def train_rows(batch, params):
 def _forward_train(encoder, batch, params):
     """Train branch of train_disc.forward: sampled rows -> the encoder's three losses -> means, coefficients, their sum."""
     dev = params["device"]
-    r = {k: (v.to(dev) if torch.is_tensor(v) else v) for k, v in train_rows(batch, params).items()}
-    att = sequence_mask(sequence_lengths(r["sep_indices"], r["hist_len"]), r["tokens"].shape[1])
+    rows = disc_rows.train_batch_of(batch, params) if disc_rows.is_pooled(batch) else train_rows(batch, params)
+    r = {k: (v.to(dev) if torch.is_tensor(v) else v) for k, v in rows.items()}
+    att = r["att"] if "att" in r else sequence_mask(sequence_lengths(r["sep_indices"], r["hist_len"]), r["tokens"].shape[1])
     lm_loss, img_loss, nsp_loss, nsp_scores, lm_scores, _, _ = encoder(
         r["tokens"], r["image_feat"], r["image_loc"], sep_indices=r["sep_indices"], token_type_ids=r["segments"],
         masked_lm_labels=r["mask"], attention_mask=att, next_sentence_label=r["next_sentence_labels"],
@@ -111,6 +116,9 @@ def forward_disc(encoder, item, params):
     over all tokens are not materialised; modules.VisualDialogEncoder)."""
     if "train" in params["mode"]:
         return _forward_train(encoder, item, params)
+    if disc_rows.is_pooled(item):                           # every [dialog, round, option] row of the pools, built on the device
+        D, R = item["ques"].shape[:2]
+        item = disc_rows.eval_item(item, 0, D * R * int(params["num_options"]), params)
     tokens, features, spatials, sep_indices, segments, mask, att, image_mask = _prepare(item, params)
     _, _, _, nsp_scores, lm_scores, _, _ = encoder(tokens, features, spatials, sep_indices=sep_indices, token_type_ids=segments,
                                                    masked_lm_labels=mask, attention_mask=att, image_attention_mask=image_mask)
@@ -131,12 +139,17 @@ def chunk_item(batch, dialog_of_row, start, end):
 @torch.no_grad()
 def score_batch(encoder, batch, params, rows_per_call=200):
     """-> softmax(nsp_scores, 1)[:, 0] of every answer option, [dialogs, rounds, options] fp32 on the device."""
-    B, rounds, options = batch["tokens"].shape[:3]
-    dialog_of_row = option_rows_to_dialog(B, rounds, options)
+    pooled = disc_rows.is_pooled(batch)
+    if pooled:
+        (B, rounds), options = batch["ques"].shape[:2], int(params["num_options"])
+    else:
+        B, rounds, options = batch["tokens"].shape[:3]
+        dialog_of_row = option_rows_to_dialog(B, rounds, options)
     mod = _module(encoder)
     out = []
     for s, e in chunk_bounds(B * rounds * options, rows_per_call):
-        tokens, features, spatials, _, segments, _, att, image_mask = _prepare(chunk_item(batch, dialog_of_row, s, e), params)
+        item = disc_rows.eval_item(batch, s, e, params) if pooled else chunk_item(batch, dialog_of_row, s, e)
+        tokens, features, spatials, _, segments, _, att, image_mask = _prepare(item, params)
         out.append(mod.nsp_scores(tokens, features, spatials, segments, att, image_mask)[1])
     return torch.cat(out, 0).view(B, rounds, options)
 
@@ -152,9 +165,13 @@ def evaluate_disc(encoder, dataloader, params, eval_batch_size=None, rows_per_ca
     for batch in dataloader:
         output = score_batch(encoder, batch, params, rows_per_call).cpu()
         if mode == "vd_eval_val":
-            sparse.observe(output, batch["gt_option_inds"])
-            rid = batch["round_id"].squeeze(1)
-            ndcg.observe(output[torch.arange(output.size(0)), rid - 1, :], batch["gt_relevance"])
+            if disc_rows.is_pooled(batch):
+                gt_option_inds, gt_relevance = disc_rows.eval_targets(batch, params)
+            else:
+                gt_option_inds, gt_relevance = batch["gt_option_inds"], batch["gt_relevance"]
+            sparse.observe(output, gt_option_inds)
+            rid = batch["round_id"].cpu().squeeze(1)
+            ndcg.observe(output[torch.arange(output.size(0)), rid - 1, :], gt_relevance)
         else:
             ranks = scores_to_ranks(output).squeeze(1)
             for i in range(output.shape[0]):

@@ -1187,6 +1187,102 @@ def dialog_rows(cap, ques, ans, ppl, T, Ud, select_data, threshold, mask_prob, v
     return res
 
 
+DISC_MAX_OPTIONS = 100         # options of a round gstvd_disc_rows covers (two ballots)
+_DISC_OUT = (("tokens", torch.int64, "T"), ("segments", torch.int64, "T"), ("mask", torch.int64, "T"), ("att", torch.float32, "T"),
+             ("sep_indices", torch.int64, "S"))
+_DISC_VEC = (("hist_len", torch.int64, 1), ("neg_option", torch.int32, 1), ("nsp_labels", torch.float32, 2))
+
+
+def disc_rows(cap, ques, ans, opts, gt_index, row_dialog, row_round, row_slot, T, tot_rounds, num_options, train, mask_prob=0.0,
+              u_tok=None, u_neg=None, dense_scores=None, cls=101, sep=102, mask=103, S=DIALOG_MAX_SEP, out=None):
+    """N rows of the discriminative model from token-id pools in one launch (gstvd_disc_rows; the rule -- the loader of
+    dataloader/dataloader_visdial_disc.py on token ids -- is stated in include/gstvd_hip.h).
+    Pools, int64 and 0-padded: cap [D, Lc <= 64] (dense rows), ques / ans [D, R, U <= 64], opts [D, R, O <= 100, U] (row stride
+    free, everything else dense), gt_index [D, R]; dense_scores float64 [D, R, O] or None.  row_dialog / row_round / row_slot
+    int32 [N].  `train`: False -- slot k is option k of the eval order (ground truth first); True -- slot 0 is the ground-truth
+    answer, any other slot a negative drawn with u_neg fp32 [N].  u_tok fp32 [N, T] (dense rows), required when mask_prob > 0.
+    Returns a dict: tokens, segments, mask int64 [N, T], att fp32 [N, T], sep_indices int64 [N, S], hist_len int64 [N], neg_option
+    int32 [N] and, in train mode, nsp_labels fp32 [N, 2].  `out`: a dict of caller-owned tensors to write into instead (the four
+    [N, T] arrays 2-D views of one row stride, sep_indices a 2-D view, the rest contiguous)."""
+    who = "disc_rows"
+    for name, t, nd in (("ques", ques, 3), ("ans", ans, 3), ("opts", opts, 4), ("gt_index", gt_index, 2)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.dim() != nd:
+            raise L.GstvdError("%s: %s must be an int64 tensor of %d dimensions" % (who, name, nd))
+    D, R, U = ques.shape
+    O = opts.shape[2]
+    T, S, train = int(T), int(S), bool(train)
+    if tuple(ans.shape) != (D, R, U) or tuple(opts.shape) != (D, R, O, U) or tuple(gt_index.shape) != (D, R):
+        raise L.GstvdError("%s: ques / ans [D, R, U], opts [D, R, O, U] and gt_index [D, R] do not belong together: %s %s %s %s"
+                           % (who, tuple(ques.shape), tuple(ans.shape), tuple(opts.shape), tuple(gt_index.shape)))
+    _rows_i64(who, "cap", cap)
+    if not (ques.is_contiguous() and ans.is_contiguous() and gt_index.is_contiguous()):
+        raise L.GstvdError("%s: ques, ans and gt_index must be contiguous" % who)
+    so = opts.stride()
+    if D * R * O > 0 and ((U > 1 and so[3] != 1) or so[2] < U or (O > 1 and so[1] != O * so[2]) or (R > 1 and so[0] != R * O * so[2])):
+        raise L.GstvdError("%s: opts must have dense rows of one stride (got strides %s)" % (who, so))
+    Lc = cap.shape[1]
+    if cap.shape[0] != D or D < 1 or not 1 <= U <= DIALOG_MAX_UTT or not 1 <= Lc <= DIALOG_MAX_UTT or T < 2:
+        raise L.GstvdError("%s: cap [D >= 1, Lc], 1 <= U, Lc <= %d and T >= 2 (got D %d, U %d, Lc %d, T %d)"
+                           % (who, DIALOG_MAX_UTT, D, U, Lc, T))
+    if R < 1 or 2 * R + 1 > S or S > 64:
+        raise L.GstvdError("%s: %d rounds give %d separators, more than max_sep_len = %d allows (2R + 1 <= S <= 64)" % (who, R, 2 * R + 1, S))
+    tot_rounds, num_options = int(tot_rounds), int(num_options)
+    if not 2 <= num_options <= O <= DISC_MAX_OPTIONS or tot_rounds < 1:
+        raise L.GstvdError("%s: 2 <= num_options <= O <= %d and tot_rounds >= 1 (got num_options %d, O %d, tot_rounds %d)"
+                           % (who, DISC_MAX_OPTIONS, num_options, O, tot_rounds))
+    if not isinstance(row_dialog, torch.Tensor) or row_dialog.dim() != 1:
+        raise L.GstvdError("%s: row_dialog must be an int32 vector" % who)
+    N = row_dialog.numel()
+    for name, t in (("row_dialog", row_dialog), ("row_round", row_round), ("row_slot", row_slot)):
+        _flag_vec(who, name, t, N, torch.int32)
+    mask_prob = float(mask_prob)
+    if u_tok is None and mask_prob > 0.0:
+        raise L.GstvdError("%s: mask_prob = %g needs u_tok, one uniform per row position [N, T]" % (who, mask_prob))
+    if u_tok is not None and _rows_i64(who, "u_tok", u_tok, T, torch.float32).shape[0] != N:
+        raise L.GstvdError("%s: u_tok must be fp32 [N = %d, T = %d]" % (who, N, T))
+    if train:
+        if u_neg is None:
+            raise L.GstvdError("%s: train mode needs u_neg, one uniform per row [N]" % who)
+        _flag_vec(who, "u_neg", u_neg, N, torch.float32)
+    if dense_scores is not None and (not isinstance(dense_scores, torch.Tensor) or dense_scores.dtype != torch.float64
+                                     or tuple(dense_scores.shape) != (D, R, O) or not dense_scores.is_contiguous()):
+        raise L.GstvdError("%s: dense_scores must be a contiguous float64 [D, R, O] tensor" % who)
+    dims = dict(T=T, S=S)
+    vec = [v for v in _DISC_VEC if train or v[0] != "nsp_labels"]
+    if out is None:
+        _p(ques)
+        o = {k: torch.empty(N, dims[c], dtype=dtp, device=ques.device) for k, dtp, c in _DISC_OUT}
+        for k, dtp, w in vec:
+            o[k] = torch.empty((N,) if w == 1 else (N, w), dtype=dtp, device=ques.device)
+    else:
+        o = out
+        for k, dtp, c in _DISC_OUT:
+            if _rows_i64(who, "out[%s]" % k, o[k], dims[c], dtp).shape[0] != N:
+                raise L.GstvdError("%s: out[%s] must have N = %d rows" % (who, k, N))
+        for k, dtp, w in vec:
+            t = o[k]
+            if not isinstance(t, torch.Tensor) or t.dtype != dtp or tuple(t.shape) != ((N,) if w == 1 else (N, w)) or not t.is_contiguous():
+                raise L.GstvdError("%s: out[%s] must be a contiguous %s tensor of %d x %d" % (who, k, str(dtp).replace("torch.", ""), N, w))
+        if len(set(o[k].stride(0) for k in ("tokens", "segments", "mask", "att"))) != 1:
+            raise L.GstvdError("%s: tokens, segments, mask and att must share one row stride" % who)
+    d = L.DiscRowsDesc()
+    d.cap, d.ld_cap, d.ques, d.ans, d.ld_utt = _p(cap), max(cap.stride(0), Lc), _p(ques), _p(ans), U
+    d.opts, d.ld_opt, d.gt_index, d.dense_scores = _p(opts), max(so[2], U), _p(gt_index), _p(dense_scores)
+    d.row_dialog, d.row_round, d.row_slot = _p(row_dialog), _p(row_round), _p(row_slot)
+    d.u_tok, d.ld_u, d.u_neg = _p(u_tok), (max(u_tok.stride(0), T) if u_tok is not None else 0), _p(u_neg) if train else None
+    d.tokens, d.segments, d.mask, d.att = _p(o["tokens"]), _p(o["segments"]), _p(o["mask"]), _p(o["att"])
+    d.ld_row, d.sep_indices, d.ld_sep = max(o["tokens"].stride(0), T), _p(o["sep_indices"]), max(o["sep_indices"].stride(0), S)
+    d.hist_len, d.neg_option, d.nsp_labels = _p(o["hist_len"]), _p(o["neg_option"]), _p(o["nsp_labels"]) if train else None
+    d.mask_prob, d.cls, d.sep, d.mask_id, d.N = mask_prob, int(cls), int(sep), int(mask), N
+    d.D, d.R, d.O, d.U, d.Lc, d.T, d.S = D, R, O, U, Lc, T, S
+    d.tot_rounds, d.num_options, d.train = tot_rounds, num_options, int(train)
+    lib = L.load()
+    e0 = _prof_begin()
+    L.check("gstvd_disc_rows", lib.gstvd_disc_rows(C.byref(d), _stream()))
+    _prof_end(e0, "disc_rows", 0.0, N * (T * 28.0 + S * 8.0), (N, T))
+    return o
+
+
 FUSION = {"mul": 0, "sum": 1}
 
 

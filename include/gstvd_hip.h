@@ -734,6 +734,66 @@ typedef struct {
 } gstvd_subseq_replace_t;
 int gstvd_subseq_replace(const gstvd_subseq_replace_t* a, gstvd_stream_t s);
 
+/* ---- discriminative rows (entry point added, no signature changed: ABI stays 9) ------------------------------------------------
+ * gstvd_disc_rows: N rows of the discriminative (enc_only) model -- what dataloader/dataloader_visdial_disc.py builds per dialog
+ * with a tokenizer and Python lists (train rows :125-288, eval rows :299-401) through utils/data_utils.py:34-71 (encode_input) --
+ * from token-id pools, in ONE launch without atomics, workspace, allocation or host synchronisation (capture-safe).  Every output
+ * element is written exactly once: nothing needs zeroing in front.
+ * Pools (int64, 0-padded, no [CLS] / [SEP] inside): cap [D, Lc] (row stride ld_cap); ques, ans [D, R, U] (row stride ld_utt
+ * between the D * R rows; ans = the ground-truth answers); opts [D, R, O, U] (row stride ld_opt between the D * R * O rows);
+ * gt_index int64 [D, R]; dense_scores double [D, R, O] or NULL.  An utterance is the entries in front of the row's first 0 (all of
+ * them when there is none); it may be empty and then contributes a lone [SEP].
+ * Row list: row_dialog, row_round, row_slot int32 [N].  Uniforms: u_tok fp32 [N, T] (row stride ld_u; may be NULL when
+ * mask_prob == 0), u_neg fp32 [N] (train mode).
+ * Outputs over the N rows: tokens, segments, mask int64 [N, T] and att fp32 [N, T] (one row stride ld_row, in elements of each);
+ * sep_indices int64 [N, S] (ld_sep); hist_len int64 [N]; neg_option int32 [N]; nsp_labels fp32 [N, 2] (contiguous).
+ *   Row (d, j, x): the utterances caption, q0, a0, ..., q(j-1), a(j-1), qj, x -- 2j + 3 of them.
+ *   pruneRounds (:84-93) with tot_rounds: j + 2 > tot_rounds drops the first 2j + 3 - 2 * tot_rounds utterances and the row starts at
+ *     segment 0; otherwise nothing is dropped and it starts at segment 1.  hist_len = (utterances kept) - 1.
+ *   encode_input: [CLS] opens the row, every utterance is followed by [SEP], the segment flips after every utterance ([CLS] and each
+ *     [SEP] carry their utterance's segment), the row is cut at T (which may lose the last [SEP], or more) and padded with 0
+ *     (segments 0, mask -1).  sep_indices: the running separator positions, 0-padded to S, NOT cut at T.
+ *   att[t] = (t < sep_indices[hist_len] + 1): train_disc.py:97-99 (sequence_mask of the row's untruncated length).
+ *   [MASK] noise: an utterance token at position p < T is masked iff (double)u_tok[r, p] < mask_prob (strict, in double): tokens =
+ *     mask_id and mask = the original id (no 80 / 10 / 10 rule); everything else has mask = -1.
+ *   Eval mode (train == 0; :299-326): x = option c of round j with c = gt if slot == 0, else the (slot - 1)-th index of
+ *     {0..O-1} \ {gt} in increasing order; 0 <= slot < num_options.  neg_option[r] = c; nsp_labels is not touched (may be NULL).
+ *   Train mode (train != 0; :125-183, 218-246):
+ *     slot 0: x = ans[d, j];  neg_option = -1;  nsp_labels = [1, 0].
+ *     slot >= 1: a negative.  Candidates C = the first num_options - 1 indices of {0..O-1} \ {gt}.
+ *       tot_len = len(cap) + 2 + sum over k <= j of (len q_k + 1 + len a_k + 1) -- the loader's running length, which counts the
+ *       ground-truth answer of round j although the negative replaces it (kept as it is).  c in C is feasible iff
+ *       T >= tot_len + len(opt_c) + 1.  With F = the feasible candidates in increasing order and u = u_neg[r]:
+ *         F not empty:  c = F[min(floor((double)u * |F|), |F| - 1)], x = opt_c whole;
+ *         F empty:      c = C[min(floor((double)u * |C|), |C| - 1)], x = the first len(a_j) tokens of opt_c
+ *       (a negative index counts as 0).  The loader's random.choice / remove loop draws c from the same distribution -- the first
+ *       feasible element of a uniform random permutation of C, or its last element when none is feasible -- from another stream.
+ *       neg_option = c;  nsp_labels = [0, 1], or with dense_scores [(float)s, (float)(1.0 - s)], s = dense_scores[d, j, c], the
+ *       subtraction in double (torch.tensor([score, 1.0 - score]), :240-243).
+ *   A row whose d, j or slot is out of range, or whose gt_index[d, j] is outside [0, O), reads no pool: it is written as padding
+ *     (tokens, segments, att, sep_indices, hist_len 0; mask -1; neg_option -1; nsp_labels [0, 0]).
+ * Limits: 1 <= U, Lc <= 64; R >= 1 and 2R + 1 <= S <= 64 (S = 25, the loader's max_sep_len: R <= 12); 2 <= num_options <= O <= 100;
+ * tot_rounds >= 1; T >= 2.  Refused before the launch, nothing written: a null required pointer, mask_prob > 0 without u_tok, train
+ * mode without u_neg or nsp_labels (GSTVD_E_NULL); a shape outside the limits, N < 0 or above 2^31 - 1, a row stride below its row
+ * (GSTVD_E_SHAPE). */
+typedef struct {
+  const int64_t* cap; int64_t ld_cap;
+  const int64_t* ques; const int64_t* ans; int64_t ld_utt;
+  const int64_t* opts; int64_t ld_opt;
+  const int64_t* gt_index; const double* dense_scores;
+  const int32_t* row_dialog; const int32_t* row_round; const int32_t* row_slot;
+  const float* u_tok; int64_t ld_u; const float* u_neg;
+  int64_t* tokens; int64_t* segments; int64_t* mask; float* att; int64_t ld_row;
+  int64_t* sep_indices; int64_t ld_sep; int64_t* hist_len;
+  int32_t* neg_option; float* nsp_labels;
+  double mask_prob;
+  int64_t cls; int64_t sep; int64_t mask_id;
+  int64_t N;
+  int32_t D; int32_t R; int32_t O; int32_t U; int32_t Lc; int32_t T; int32_t S;
+  int32_t tot_rounds; int32_t num_options; int32_t train;
+} gstvd_disc_rows_t;
+int gstvd_disc_rows(const gstvd_disc_rows_t* a, gstvd_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
