@@ -226,7 +226,7 @@ __global__ __launch_bounds__(ROWS_NT, 4) void gemm_rows_kernel(GemmP p, RowPro r
     }
   }
   if (PRO == 2 && nt < 3 && r.partial) {
-    // column partials of this 64-row block: column tile 0 -> sum dy * xhat (dgamma), 1 -> sum dy (dbeta), 2 -> sum dx (dbias)
+    // column partials of this 16-row block: column tile 0 -> sum dy * xhat (dgamma), 1 -> sum dy (dbeta), 2 -> sum dx (dbias)
     // eight per-wave vectors through four 3 KB slabs, in a fixed order (no LDS atomics: run-to-run bit identity): waves 4-7
     // park theirs, waves 0-3 add them to their own and park the sums, then all threads add the four slabs
     float* mine = scratch + (wave & 3) * HS;

@@ -95,8 +95,10 @@ __global__ __launch_bounds__(256) void gemv16_ln_kernel(GemmP p, LnIn ln) {
     bt[u][0] = kin[u] ? *(const f32x4*)(ln.beta + k) : zf;
     bt[u][1] = kin[u] ? *(const f32x4*)(ln.beta + k + 4) : zf;
   }
-  // row statistics in ONE reduction round (sum and sum of squares together; fp32, var = E[x^2] - mean^2 clamped at 0: the
-  // rows are residual-stream activations, |mean| is far below the spread, nothing cancels) -- two barriers instead of four
+  // row statistics in ONE reduction round (sum and sum of squares together; fp32, var = E[x^2] - mean^2 clamped at 0) -- two
+  // barriers instead of four.  The cancellation grows with (1 + r^2), r = |mean| / std of a row; measured on random bf16 rows up
+  // to r = 16 at K = 200 and K = 1024: y_out stays within one bf16 ulp of LayerNorm in float64, within 0.001 ulp at r = 0.2 and r = 4
+  // (tests/test_lnfold_exact_gpu.py, the noise rows).  Beyond r = 16 nothing is measured.
   float s1 = 0.f, s2 = 0.f;
 #pragma unroll
   for (int u = 0; u < UNR; ++u)

@@ -17,10 +17,6 @@ GELU_TOL = {torch.float32: 2e-5, torch.bfloat16: 1.2e-2}       # test_ops_gpu.py
 # Kernels of the library that no case of the table names, each with its reason and the test that covers it.  None of them is
 # reachable through gstvd_gemm, gstvd_gemm_splitk or gstvd_gemm_grouped.
 EXEMPT = {
-    "gemv16_ln_kernel": "own entry point (gstvd_gemv_ln), LayerNorm is not exact arithmetic: "
-                        "test_ops_gpu.py::test_decode_layernorm_folded_into_the_linear",
-    "gemm_rows_kernel": "own entry points (gstvd_gemm_ln_fwd / _bwd), LayerNorm prologue: "
-                        "test_ops_gpu.py::test_gemm_ln_fwd_matches_ln_then_gemm, test_gemm_ln_bwd_matches_ln_bwd_then_gemm",
     "gemm_pc256_grouped_adamw_kernel": "own entry point (gstvd_gemm_grouped_adamw), AdamW epilogue is not exact arithmetic: "
                                        "test_fused_update_gpu.py (identity with the unfused path, which this file anchors)",
 }
@@ -33,8 +29,13 @@ def grouped_kernel(lay, out):
 
 
 def check_census(symbols):
-    """Every GEMM kernel instantiation of the built library is named by exactly one kernel name of the tables, or is exempt."""
-    named = sorted(set(c.kernel for c in E.CASES) | set(grouped_kernel(*g) for g in GROUPED))
+    """Every GEMM kernel instantiation of the built library is named by exactly one kernel name of the tables, or is exempt.
+    The LayerNorm-folded kernels (gemm_rows_kernel, gemv16_ln_kernel: own entry points) are named by the table of
+    tests/exact_lnfold.py and run by tests/test_lnfold_exact_gpu.py."""
+    import exact_lnfold
+    folded = exact_lnfold.kernel_names()
+    assert len(folded) == 18
+    named = sorted(set(c.kernel for c in E.CASES) | set(grouped_kernel(*g) for g in GROUPED) | set(folded))
     reached, lines = set(), []
     for s in symbols:
         hits = [n for n in named if n in s]
@@ -42,7 +43,9 @@ def check_census(symbols):
         assert len(hits) + len(ex) == 1, "%s: named by %r, exempt as %r" % (s, hits, ex)
         reached.update(hits)
         n = sum(1 for c in E.CASES if c.kernel in s)
+        nf = [c.id for c in exact_lnfold.CASES if c.kernel in s]
         lines.append("%-100s %s" % (s, ("%d case(s), e.g. %s" % (n, next(c.id for c in E.CASES if c.kernel in s))) if n
+                                    else ("%d case(s) of exact_lnfold, e.g. %s" % (len(nf), nf[0])) if nf
                                     else ("grouped launch" if hits else "EXEMPT: " + EXEMPT[ex[0]])))
     print("\n".join(lines))
     assert reached == set(named), "kernels named by a case but absent from the library: %r" % sorted(set(named) - reached)
@@ -100,7 +103,7 @@ def test_gemm_exact(c):
 def test_census_every_gemm_kernel_of_the_library_is_named_by_a_case_or_exempt():
     """Lists the GEMM kernel instantiations the built library carries and the case that reaches each (run with -s to see it).
     test_gemm_exact / test_grouped_* assert per case that the named kernel is the launched one."""
-    assert set(EXEMPT) <= {"gemv16_ln_kernel", "gemm_rows_kernel", "gemm_pc256_grouped_adamw_kernel"}
+    assert set(EXEMPT) <= {"gemm_pc256_grouped_adamw_kernel"}
     check_census(E.library_gemm_kernels(E.lib_path()))
 
 
