@@ -1,5 +1,6 @@
-"""Exact layer of the attention tests: a route table, canary / poison windows and five families of
-inputs whose results are known exactly, so that ONE mis-handled key, dropout draw, mask term or address shows.
+"""Exact layer of the attention tests: a route table, canary / poison windows and eight families of
+inputs whose results are known exactly (J: to a derived rounding bound), so that ONE mis-handled key, dropout draw, mask term,
+address, dK term or softmax rescale shows.
 
   A  route table: every case names the forward and the backward kernel it expects (the library is asked, ops.attn_kernel_symbol)
   B  windows: outputs in canary allocations, inputs in NaN-poisoned ones, padded leading dimensions (exact_gemm.Window)
@@ -8,6 +9,11 @@ inputs whose results are known exactly, so that ONE mis-handled key, dropout dra
   E  invariances, bit for bit (mask None vs ones, contents of masked / later keys, appended masked keys, permutations, keep bits)
   F  the dropout mask each consumer applied, recovered element by element from its own outputs with indicator operands
   G  a batch row whose keys are ALL masked (the additive mask then cancels in the softmax: softmax of the raw scores)
+  H  uniform attention with Q and K on disjoint columns: every score still 0, but dK = dS^T Q is nonzero and bit-exact
+  I  subset attention: C with j bits of the code left out -> 2^j keys tie at score 0, P = 2^-j there; O, dV, dQ and dK bit-exact
+  J  graded ("tent") rows: running maxima that move by 0.5 per tile, different rows of a wave at different updates -- the
+     online-softmax rescale with factors between 0 and 1, every element judged against float64 within a first-order rounding bound
+H, I, J run on an explicit power-of-two softmax scale (Problem(scale=)), so integer operands give exact scores at every head size.
 
 Plain helper module: no fixtures, no hooks.  Every check takes a *backend* -- an object with `device`, `run(problem)` (forward,
 and backward when the case has one, on the problem's windows) and `keep(problem)` (the dropout keep mask [B, nh, Lq, Lk] of that
@@ -202,8 +208,9 @@ class Problem(object):
     delta and the keep bits inside canary allocations; leading dimensions nh * d + 8 or + 16 (by `seed`), guard rows around
     every operand.  Tensors are addressed as [B, L, nh, d] (statistics [B, nh, Lq], key mask [B / kv_group, Lk])."""
 
-    def __init__(self, c, device, seed=0, key_mask=True):
+    def __init__(self, c, device, seed=0, key_mask=True, scale=None):
         self.c, self.device, self.seed = c, device, seed
+        self.scale_arg, self.scale = scale, scale32(c.d) if scale is None else float(scale)    # None: the descriptor's default, fl32(1 / sqrt(d))
         dt, H = DT[c.dtype], c.nh * c.d
         pad = 8 if seed % 2 == 0 else 16
         self.Bkv = c.B // c.kv_group
@@ -287,12 +294,13 @@ class Problem(object):
                     assert nn == 0, "%s: %s: %d NaN(s) in the result (something outside an operand was read)" % (name, tag, nn)
 
 
-def launch(be, c, inp, seed=0, name=None):
+def launch(be, c, inp, seed=0, name=None, scale=None):
     """One launch of case `c` on backend `be` with the inputs `inp` (Q, K, V, dO as [B, L, nh, d] float tensors, key_mask or
-    None): windows built, backend run, windows checked.  Returns (outputs, keep mask or None)."""
+    None) and the softmax scale `scale` (None: the descriptor's default): windows built, backend run, windows checked.  Returns
+    (outputs, keep mask or None)."""
     name = name or c.id
     km = inp.get("key_mask")
-    p = Problem(c, be.device, seed, key_mask=km is not None)
+    p = Problem(c, be.device, seed, key_mask=km is not None, scale=scale)
     p.set(**{k: v for k, v in inp.items() if v is not None and (k != "dO" or c.has_bwd or c.bwd == "refuse")})
     be.run(p)
     p.assert_windows(name)
@@ -319,25 +327,31 @@ def allowed_keys(c, km, device):
     return a
 
 
-def reference(c, inp, keep):
+def reference(c, inp, keep, scale=None, P=None, O_stored=None):
     """float64 attention with the kernels' conventions: the additive mask term is added ONCE (key mask or causal mask or both),
-    dropout keeps with factor 1 / (1 - p), delta = rowsum(dO * O) with O as stored (rounded to the operand type)."""
+    dropout keeps with factor 1 / (1 - p), delta = rowsum(dO * O) with O as stored (rounded to the operand type; `O_stored`: the
+    O a launch wrote).  `scale`: the softmax scale (None: scale32(d)).  `P`: the probabilities [B, nh, Lq, Lk], where a
+    construction knows them exactly (no softmax is formed then, and no LSE returned)."""
     dev = inp["Q"].device
     Q, K, V = inp["Q"].double(), inp["K"].double().repeat_interleave(c.kv_group, 0), inp["V"].double().repeat_interleave(c.kv_group, 0)
-    sc = scale32(c.d)
-    al = allowed_keys(c, inp.get("key_mask"), dev)
-    s = torch.einsum("bqhd,bkhd->bhqk", Q, K) * sc + torch.where(al, 0.0, c.neg).double()
-    m = s.max(-1, keepdim=True).values
-    e = torch.exp(s - m)
-    l = e.sum(-1, keepdim=True)
-    P = e / l
-    r = dict(P=P, LSE=(m + torch.log(l)).squeeze(-1))
+    sc = scale32(c.d) if scale is None else float(scale)
+    if P is None:
+        al = allowed_keys(c, inp.get("key_mask"), dev)
+        s = torch.einsum("bqhd,bkhd->bhqk", Q, K) * sc + torch.where(al, 0.0, c.neg).double()
+        m = s.max(-1, keepdim=True).values
+        e = torch.exp(s - m)
+        l = e.sum(-1, keepdim=True)
+        P = e / l
+        r = dict(P=P, S=s, LSE=(m + torch.log(l)).squeeze(-1))
+    else:
+        r = dict(P=P)
+    r["scale"] = sc
     f = (keep.double() / (1.0 - c.p)) if keep is not None else torch.ones_like(P)
     Pd = r["Pd"] = P * f
     r["O"] = torch.einsum("bhqk,bkhd->bqhd", Pd, V)
     if inp.get("dO") is not None and c.has_bwd:
         dO = inp["dO"].double()
-        Os = r["O"].float().to(DT[c.dtype]).double()
+        Os = r["O"].float().to(DT[c.dtype]).double() if O_stored is None else O_stored.double()
         r["delta"] = (dO * Os).sum(-1).permute(0, 2, 1)
         dP = torch.einsum("bqhd,bkhd->bhqk", dO, V)
         dS = r["dS"] = P * (dP * f - r["delta"][..., None]) * sc
@@ -781,6 +795,414 @@ def check_all_masked_row(be, c, seed=0, out=None):
         for nme in ("dQ", "dK", "dV"):
             assert_close(got[nme][1:], ref[nme][1:], 4 * TOL[dt], "%s: other rows %s" % (c.id, nme), out)
             assert_close(got[nme][0], ref[nme][0], G_BOUND + 4 * TOL[dt], "%s: masked row %s" % (c.id, nme), out)
+
+
+# ---------------------------------------------------------------------------------------------- exact sums
+def unit_of(x):
+    """The largest power of two of which every element of the float64 tensor is a multiple (1.0 for an all-zero tensor)."""
+    nz = x[x != 0]
+    if nz.numel() == 0:
+        return 1.0
+    m, e = torch.frexp(nz)
+    mi = (m.abs() * 2.0 ** 53).to(torch.int64)
+    low = (mi & -mi).double()                                                  # the lowest set bit of the 53-bit significand
+    return float((torch.log2(low) + e.double() - 53).min().exp2())
+
+
+def sum_is_exact(eq, a, b):
+    """The fp32 sums einsum(eq, a, b) are exact in ANY order of additions: every term is a multiple of unit_of(a) * unit_of(b) and
+    the sum of the terms' magnitudes -- which bounds every partial sum -- stays below 2^24 of these units."""
+    peak = float(torch.einsum(eq, a.abs(), b.abs()).max())
+    return peak < 2.0 ** 24 * unit_of(a) * unit_of(b)
+
+
+def sums_are_exact(c, ref, inp):
+    """sum_is_exact for the four products of one launch (O, dV, dQ, dK) from the float64 intermediates of reference()."""
+    x = lambda n: inp[n].double().repeat_interleave(c.kv_group, 0) if n in ("K", "V") else inp[n].double()
+    return (sum_is_exact("bhqk,bkhd->bqhd", ref["Pd"], x("V")) and sum_is_exact("bhqk,bqhd->bkhd", ref["Pd"], x("dO"))
+            and sum_is_exact("bhqk,bkhd->bqhd", ref["dS"], x("K")) and sum_is_exact("bhqk,bqhd->bkhd", ref["dS"], x("Q")))
+
+
+# ---------------------------------------------------------------------------------------------- H. uniform attention, dK != 0
+H_SCALE = 2.0 ** -3
+
+
+def disjoint_inputs(c, gen, dev):
+    """The operands of family H: K in [-3, 3] on the columns [0, d / 2), Q in {-2, -1, 1, 2} on the columns [d / 2, d) -- every
+    score is exactly 0 --, V in {-1, 0, 1}, dO = +-1 in one column per row."""
+    Bkv, h = c.B // c.kv_group, c.d // 2
+    K = integers((Bkv, c.Lk, c.nh, c.d), 3, gen, torch.float32, dev)
+    K[..., h:] = 0
+    Q = (torch.randint(0, 2, (c.B, c.Lq, c.nh, c.d), generator=gen, device=dev).float() * 2 - 1) * (1 + torch.randint(0, 2, (c.B, c.Lq, c.nh, c.d), generator=gen, device=dev).float())
+    Q[..., :h] = 0
+    V = integers((Bkv, c.Lk, c.nh, c.d), 1, gen, torch.float32, dev)
+    col = torch.randint(0, c.d, (c.B, c.Lq, c.nh, 1), generator=gen, device=dev)
+    dO = torch.zeros(c.B, c.Lq, c.nh, c.d, device=dev).scatter_(-1, col, torch.randint(0, 2, col.shape, generator=gen, device=dev).float() * 2 - 1)
+    return dict(Q=Q, K=K, V=V, dO=dO)
+
+
+def pow2_mask(c, gen, dev, seed):
+    """check_uniform's key mask: a power-of-two number of allowed keys per row (None where Lk is one and the seed says so)."""
+    pow2 = 1 << (c.Lk.bit_length() - 1)
+    if pow2 == c.Lk and c.Lk > 1 and seed % 2:
+        pow2 //= 2
+    return make_mask(c, gen, dev, allowed=pow2) if (pow2 < c.Lk or seed % 3 == 0) else None
+
+
+def disjoint_must_be_exact(c):
+    """The mode check_uniform_dk MUST reach, from the table alone.  With the explicit scale 2^-3 no head size needs a rounding:
+    wherever every query sees a power-of-two number of keys (no causal mask, or one query) fp32 is bit-exact at d = 32, 64 and
+    128; bf16 without dropout and with n <= 128 keys too (uniform_must_be_exact's argument: V and dO are family D's, and the
+    scale only moves the exponent of dS).  None: the data decide (bf16 with dropout or 256 keys) or the tolerance applies."""
+    if not c.has_bwd or (c.causal and c.Lq > 1):
+        return None
+    return "exact" if c.dtype == "f32" or (c.p == 0 and c.Lk < 256) else None
+
+
+def check_uniform_dk(be, c, seed=0, out=None):
+    """Family D with Q and K on disjoint halves of the head dimension (disjoint_inputs) and the explicit scale 2^-3: every score
+    is exactly 0 as with Q = 0, so P, O, LSE, dV and delta are check_uniform's, but dK = dS^T Q is nonzero in the Q columns (and
+    dQ = dS K lives in the K columns).  Where every query sees a power-of-two number of keys, the bf16 operands formed on the
+    device (P * fac, dS; and the stored O) are exact (guarded on the float64 intermediates) and every partial sum of the four
+    products stays below 2^24 units (sums_are_exact), dQ, dK, dV and delta are bit-equal to the float64 reference at every head
+    size; disjoint_must_be_exact() names the cases for which that MUST hold.  Elsewhere: 4 x TOL, as for D -- but dV and delta stay
+    bit-equal wherever P * fac and O are exact (only dS carries the ninth bit).  Returns the mode."""
+    dev, dt = be.device, DT[c.dtype]
+    gen = generator(6000 + seed, dev)
+    km = pow2_mask(c, gen, dev, seed)
+    inp = dict(disjoint_inputs(c, gen, dev), key_mask=km)
+    got, keep = launch(be, c, inp, seed, c.id + ": uniform, disjoint columns", scale=H_SCALE)
+    ref = reference(c, inp, keep, scale=H_SCALE)
+    assert_all_zero(torch.einsum("bqhd,bkhd->bhqk", inp["Q"], inp["K"].repeat_interleave(c.kv_group, 0)), c.id + ": disjoint scores")
+    n = allowed_keys(c, km, dev).sum(-1)
+    assert int(n.min()) >= 1
+    all_pow2 = bool(((n & (n - 1)) == 0).all())
+    # O as check_uniform asserts it: fl32(sum of the kept allowed V rows) * fl32(1 / n) -- the reference itself for n a power of two
+    al = allowed_keys(c, km, dev)
+    f = (keep.double() / (1.0 - c.p)) if keep is not None else torch.ones((), dtype=torch.float64, device=dev)
+    ssum = torch.einsum("bhqk,bkhd->bqhd", (al.double() * f).expand(c.B, c.nh, c.Lq, c.Lk), inp["V"].double().repeat_interleave(c.kv_group, 0))
+    want_O = (ssum.float() * (1.0 / n.float()).permute(0, 2, 1)[..., None]).double()
+    if all_pow2:
+        assert_bit_equal(got["O"], want_O, c.id + ": disjoint O")
+        assert_bit_equal(got["O"], ref["O"], c.id + ": disjoint O")
+    else:
+        assert_within_one_ulp(got["O"], want_O, c.id + ": disjoint O")
+    assert_close(got["LSE"], torch.log(n.double()).expand(c.B, c.nh, c.Lq), 2 * TOL[F32], c.id + ": disjoint LSE")
+    if not c.has_bwd:
+        return "forward"
+    half = all_pow2 and sums_are_exact(c, ref, inp) and (dt == F32 or (fits(ref["Pd"], BF16) and fits(ref["O"], BF16)))
+    exact = half and (dt == F32 or fits(ref["dS"], BF16))
+    for nme in ("delta", "dV", "dQ", "dK"):
+        if exact or (half and nme in ("delta", "dV")):                         # (P * fac and O exact: dV and delta are, whatever dS holds)
+            assert_bit_equal(got[nme], ref[nme], "%s: disjoint %s" % (c.id, nme))
+        elif nme != "delta":
+            assert_close(got[nme], ref[nme], 4 * TOL[dt], "%s: disjoint %s" % (c.id, nme))
+    if exact:
+        assert int((got["dK"] != 0).sum()) > 0 or int(n.max()) < 4, c.id + ": the construction gave dK = 0"      # (one key: dP * fac - delta cancels)
+    mode = "exact" if exact else "tol"
+    must = disjoint_must_be_exact(c)
+    assert must is None or mode == must, "%s: disjoint-column backward was checked as %r, the construction promises %r" % (c.id, mode, must)
+    if out:
+        out("%s: disjoint-column backward checked as %s" % (c.id, mode))
+    return mode
+
+
+# ---------------------------------------------------------------------------------------------- I. subset attention
+I_SCALE = 2.0 ** -2
+
+
+I_MIN_TIED = {False: 0.5, True: 0.25}     # by `causal`: the first 2^(t - j) <= seen / 2 rows of a causal case cannot reach a second member of a spread subset
+
+
+def keys_in_sight(c):
+    """The most keys a query of the case may see: Lk, or min(Lq, Lk) under the causal mask."""
+    return min(c.Lq, c.Lk) if c.causal else c.Lk
+
+
+def subset_params(c, seed):
+    """(nb, j, kind, free, masked, reps) of check_subset for a case and seed, each dealt by a digit of its own: nb code bits, j in
+    1..3 free bits, low or high, the bit positions `free` as a mask, a key mask or none, reps columns per bit (2 * nb * reps
+    columns are used: code and bias).  High: the j bits just below 2^t, t = floor(log2(Lk)) -- the subsets of all keys below 2^t
+    are whole whatever Lk is (the TOP bits of the code would give classes of 6 or 7 keys at Lk = 200); under the causal mask t
+    comes from the keys the last query sees."""
+    nb, t = max(1, (c.Lk - 1).bit_length()), keys_in_sight(c).bit_length() - 1
+    j = min(1 + seed % 3, t)
+    kind = ("low", "high")[(seed // 3) % 2]
+    reps = c.d // (2 * nb)
+    assert reps >= 1 and 512 * reps * I_SCALE >= 104
+    return nb, j, kind, ((1 << j) - 1) << (0 if kind == "low" else t - j), (seed // 6) % 3 != 2, reps
+
+
+def check_subset(be, c, seed=0, out=None):
+    """Family C with ties.  K[k] = the +-16 binary code of k over nb bits x reps columns, then nb * reps bias columns of +16
+    (signs flipped per (row, head, column) as in C).  Q[q] = the code of sel(q) with j bit positions zeroed -- the j low bits, or
+    the j high bits, by the seed -- and -16 in the first (nb - j) * reps bias columns: Q . K[k] = -512 reps * (number of kept bits
+    in which k differs from sel), so with the explicit scale 2^-2 the 2^j keys that agree with sel on the kept bits tie at a
+    score of exactly 0 and every other key is at least 128 lower (asserted): exp underflows to an exact 0 there, P = 1 / count on
+    the tied keys, LSE = log(count).  Low free bits: 2^j adjacent keys; high free bits (subset_params): keys 2^(t - j) apart,
+    spread over the tiles, chunks and key-owning waves -- equal maxima meet across chunk borders.  The key mask (by the seed)
+    takes whole subsets in or out.  sel(q) is drawn among the keys whose subset, as Lk, the key mask and the causal mask leave it
+    to that query, holds 2, 4 or 8 keys; a query that draws another key (one time in ten, or where it has no such key: the
+    first rows under the causal mask) points at it alone (j = 0 for that query, the whole code kept).  So every count IS a
+    power of two and no case needs a tolerance, and at least half (a quarter under the causal mask) of the queries of every case that sees two keys hold a tie and its
+    reference dK is nonzero (both asserted: a case without ties would be family C again).
+    tolerance.  V in [-4, 4], dO = +-1 in two columns per row: O, delta, dP * fac - delta, dS and the four products are dyadic
+    with at most 8 significant bits where bf16 holds them (guarded, with sums_are_exact) and O, delta, dV, dQ, dK are asserted
+    bit for bit against the float64 reference formed from the exact P -- dK nonzero exactly on selected keys, 0 on the others
+    and on masked keys.  p = 0.5 runs under the launch's own keep mask."""
+    dev, dt = be.device, DT[c.dtype]
+    gen = generator(7000 + seed, dev)
+    nb, j, kind, free, masked, reps = subset_params(c, seed)                  # free: the bit positions a query leaves out
+    kk = torch.arange(c.Lk, device=dev)
+    Bkv = c.B // c.kv_group
+    km = None
+    if masked:                                                                 # whole subsets in or out: the mask is a function of k & ~free
+        cls = kk & ~free
+        on = torch.rand(Bkv, 1 << nb, generator=gen, device=dev) < 0.67
+        on[:, 0] = True                                                        # key 0 stays (query 0 under the causal mask)
+        km = on[:, cls].float()
+    bit = torch.arange(nb, device=dev)
+    code = torch.zeros(c.Lk, c.d, device=dev)
+    code[:, :nb * reps] = (((kk[:, None] >> bit[None, :]) & 1) * 32.0 - 16.0).repeat_interleave(reps, 1)
+    code[:, nb * reps:2 * nb * reps] = 16.0
+    sign = torch.randint(0, 2, (Bkv, 1, c.nh, c.d), generator=gen, device=dev).float() * 2 - 1
+    K = code[None, :, None, :] * sign
+    al = allowed_keys(c, km, dev).expand(c.B, c.nh, c.Lq, c.Lk)
+    # per (query, key): how many allowed keys share the key's class; sel is drawn among the keys whose subset is whole for that
+    # query (2, 4 or 8 allowed members), ten times less often among the others -- every key can still be pointed at
+    same = ((kk[:, None] & ~free) == (kk[None, :] & ~free)).float()            # [Lk, Lk]
+    size = (al.float() @ same).long()                                          # [B, nh, Lq, Lk]
+    good = al & (size > 1) & ((size & (size - 1)) == 0)
+    sel = torch.multinomial((good.float() + 0.1 * (al & ~good).float()).reshape(-1, c.Lk), 1, generator=gen).view(c.B, c.nh, c.Lq)
+    tied = al & ((kk[None, None, None, :] & ~free) == (sel[..., None] & ~free))
+    cnt = tied.sum(-1)
+    whole = (cnt & (cnt - 1)) == 0                                             # [B, nh, Lq]: the subset's count is a power of two
+    member = torch.where(whole[..., None], tied, kk[None, None, None, :] == sel[..., None])
+    cnt = member.sum(-1)
+    colbit = torch.arange(nb * reps, device=dev) // reps                       # the bit a code column carries
+    keepcol = torch.where(whole[..., None], ((torch.full_like(colbit, free) >> colbit) & 1) == 0, torch.ones_like(colbit, dtype=torch.bool))      # [B, nh, Lq, nb * reps]
+    bidx = torch.arange(c.B, device=dev)[:, None, None]
+    hidx = torch.arange(c.nh, device=dev)[None, :, None]
+    Kx = K.repeat_interleave(c.kv_group, 0)
+    Qh = Kx[bidx, sel, hidx].clone()                                           # [B, nh, Lq, d]
+    Qh[..., :nb * reps] *= keepcol
+    nkept = keepcol.sum(-1, keepdim=True)                                      # (nb - j) * reps, or nb * reps
+    Qh[..., nb * reps:2 * nb * reps] *= -(torch.arange(nb * reps, device=dev) < nkept).float()
+    Q = Qh.permute(0, 2, 1, 3).contiguous()
+    V = integers((Bkv, c.Lk, c.nh, c.d), 4, gen, torch.float32, dev)
+    col = torch.randint(0, c.d, (c.B, c.Lq, c.nh, 2), generator=gen, device=dev)
+    dO = torch.zeros(c.B, c.Lq, c.nh, c.d, device=dev).scatter_(-1, col, torch.randint(0, 2, col.shape, generator=gen, device=dev).float() * 2 - 1)
+    inp = dict(Q=Q, K=K, V=V, dO=dO, key_mask=km)
+    # the premise, in float64 (every score is an exact integer multiple of 128): members at 0, everything else at least 104 lower
+    s = torch.einsum("bqhd,bkhd->bhqk", Q.double(), Kx.double()) * I_SCALE
+    assert bool((s[member] == 0).all()) and float(s[al & ~member].max() if bool((al & ~member).any()) else -1e9) <= -104, c.id + ": subset scores"
+    assert float(s.max()) == 0.0 and float(s.min()) > max(c.neg, -10000.0) + 104      # a masked key stays below every allowed one
+    share = float((cnt > 1).float().mean())
+    assert share >= I_MIN_TIED[c.causal] or keys_in_sight(c) == 1, "%s: subset: only %.0f %% of the queries hold a tie" % (c.id, 100 * share)
+    got, keep = launch(be, c, inp, seed, c.id + ": subset", scale=I_SCALE)
+    ref = reference(c, inp, keep, scale=I_SCALE, P=member.double() / cnt[..., None].double())
+    assert 1.0 / (1.0 - c.p) in (1.0, 2.0)
+    assert_bit_equal(got["O"], ref["O"], c.id + ": subset O")
+    assert_close(got["LSE"], torch.log(cnt.double()), 2 * TOL[F32], c.id + ": subset LSE")
+    if out:
+        out("%s: subset attention, %d %s bit(s) free, %.0f %% of the queries tied, counts %s" % (c.id, j, kind, 100 * share, sorted(set(cnt.reshape(-1).tolist()))))
+    if not c.has_bwd:
+        return "forward"
+    assert sums_are_exact(c, ref, inp), c.id + ": subset: a partial sum may pass 2^24 units"
+    assert dt == F32 or (fits(ref["Pd"], BF16) and fits(ref["O"], BF16) and fits(ref["dS"], BF16)), c.id + ": subset: a ninth bit in a bf16 operand"
+    # (a handful of rows can cancel by chance: two tied keys with equal V in the dO columns, or both dropped)
+    assert int((ref["dK"] != 0).sum()) > 0 or keys_in_sight(c) == 1 or c.B * c.nh * c.Lq < 16, c.id + ": the construction gave dK = 0"
+    for nme in ("delta", "dV", "dQ", "dK"):
+        assert_bit_equal(got[nme], ref[nme], "%s: subset %s" % (c.id, nme))
+    picked = member.any(2)                                                    # [B, nh, Lk]: some query selected the key
+    assert_all_zero(got["dK"].permute(0, 2, 1, 3)[~picked], c.id + ": subset dK of keys no query selected")
+    assert_all_zero(got["dV"].permute(0, 2, 1, 3)[~picked], c.id + ": subset dV of keys no query selected")
+    return "exact"
+
+
+# ---------------------------------------------------------------------------------------------- J. graded ("tent") rows
+J_SCALE, J_DELTA = 2.0 ** -3, 0.5
+J_MASS = 1.0 / 16
+J_NEAR, J_NOISE = 3, 16
+# The largest err / B (B: the first-order rounding bound of check_tent) the ROUNDED stand-in of tests/test_exact_attn_harness_cpu.py
+# reaches over J_CASES-like shapes on the CPU -- fp32 arithmetic, online softmax per update group, bf16 rounding of P * fac and
+# dS -- per type and for {O, LSE} / {dQ, dK, dV}; J_K is the smallest power of two >= 2 x that (the factor 2: second-order terms
+# and the hardware's __expf).  test_tent_factors_are_twice_what_the_rounded_standin_reaches re-measures them.
+# Measured over the 83 cases tent_case() selects: O 1.82 / 0.13, LSE 0.03 / 0.03, dQ 1.73 / 0.08, dK 1.85 / 0.07, dV 1.77 / 0.13 (bf16 / fp32).
+J_MEASURED = {("bf16", "fwd"): 1.82, ("bf16", "bwd"): 1.85, ("f32", "fwd"): 0.13, ("f32", "bwd"): 0.13}
+J_K = {("bf16", "fwd"): 4.0, ("bf16", "bwd"): 4.0, ("f32", "fwd"): 0.5, ("f32", "bwd"): 0.5}
+
+
+def update_group(c):
+    """Keys per softmax update of attn_fwd_body: 64 for d <= 64, 32 for d = 128."""
+    return 64 if c.d <= 64 else 32
+
+
+def tent_case(c):
+    """The cases of `RUNNABLE` family J runs on: the smallest shapes at which the rescale can go wrong (key counts around one,
+    two, four update groups, every query count up to 256 the table pairs with them), the causal 100 x 200 and the production
+    shapes."""
+    if c.nh > 2 or (c.Lq, c.Lk) == (100, 200):
+        return True
+    return c.kv_group == 1 and c.Lk in ((65, 129, 256, 293) if c.d <= 64 else (37, 65, 256)) and c.Lq in (1, 17, 63, 64, 65, 100, 256)
+
+
+def tent_borders(c):
+    """The key indices at which a new softmax update group begins."""
+    return list(range(update_group(c), c.Lk, update_group(c)))
+
+
+def tent_must_straddle(c):
+    """From the table alone: the case has an update border with J_NEAR keys on each side in sight of some query (tent_mask keeps
+    those keys unmasked), so assert_tent_condition MUST find a border to check.  The others -- 65 keys at d <= 64 and the border
+    at key 128 of 129 (ONE key beyond: 4.5 % of the mass at best), fewer keys than one update group, and the causal cases whose
+    last query sees fewer than J_NEAR keys past the first border -- still run, with no border that counts."""
+    return any(c.Lk - x >= J_NEAR and (not c.causal or c.Lq - x >= J_NEAR) for x in tent_borders(c))
+
+
+def tent_mask(c, gen, dev):
+    """make_mask with the J_NEAR keys on either side of every update border left unmasked: which borders can be straddled is
+    then a property of the case, not of the draw."""
+    km = make_mask(c, gen, dev)
+    for x in tent_borders(c):
+        km[:, x - J_NEAR:x + J_NEAR] = 1
+    return km
+
+
+def tent_reach(c, al):
+    """[B, Lq, borders] bool: the row may see at least J_NEAR keys on each side of the border."""
+    nal = torch.cumsum(al.expand(c.B, 1, c.Lq, c.Lk)[:, 0].long(), -1)
+    nl = torch.stack([nal[..., x - 1] for x in tent_borders(c)], -1)
+    return (nl >= J_NEAR) & (nal[..., -1:] - nl >= J_NEAR), nl, nal[..., -1:] - nl
+
+
+def tent_inputs(c, gen, dev, km):
+    """K[k] has a 1 in column tile(k) = k // 16; Q[q, t] = -(delta / scale) |t - peak(q)| for t < ntiles: the scaled score of key k
+    is -delta * |tile(k) - peak(q)| plus the noise of the next J_NOISE columns ({-1, 0, 1} in Q and K; the rest 0, so that the
+    noise has the same size at every head dimension), all exact integers times 2^-3.  peak(q) is dealt inside every 16-query
+    tile: the rows that can straddle an update border (tent_reach) take, in turn, a tile next to each such border -- the left
+    one, or the one on the side with fewer than 16 keys -- and the other rows go round-robin (rotated by the head) over the
+    remaining tiles with a key the row may see.  So one wave holds rows whose maximum moves at a given update and rows whose
+    maximum does not, and a short last tile still meets the borders."""
+    nt = -(-c.Lk // 16)
+    al = allowed_keys(c, km, dev)                                              # [B, 1, Lq, Lk]
+    pad = torch.zeros(c.B, c.Lq, nt * 16 - c.Lk, dtype=torch.bool, device=dev)
+    seen = torch.cat([al[:, 0], pad], -1).view(c.B, c.Lq, nt, 16).any(-1).cpu()      # [B, Lq, nt]: the tile has a key the row may see
+    borders = tent_borders(c)
+    if borders:
+        reach, nl, nr = (x.cpu() for x in tent_reach(c, al))
+    peak = torch.zeros(c.B, c.nh, c.Lq, dtype=torch.long)
+    for b in range(c.B):
+        rank = 0
+        for q in range(c.Lq):
+            rank = 0 if q % 16 == 0 else rank
+            first = []
+            for n, x in enumerate(borders):
+                if reach[b, q, n]:
+                    side = 1 if nr[b, q, n] < 16 and nr[b, q, n] <= nl[b, q, n] else 0
+                    first.append(x // 16 - 1 + side)
+            rest = [t for t in range(nt) if seen[b, q, t] and t not in first]
+            for h in range(c.nh):
+                peak[b, h, q] = first[rank] if rank < len(first) else rest[(q % 16 + h) % len(rest)] if rest else first[rank % len(first)]
+            rank += 1 if first else 0
+    peak = peak.to(dev)
+    Bkv = c.B // c.kv_group
+    Q = integers((c.B, c.Lq, c.nh, c.d), 1, gen, torch.float32, dev)
+    K = integers((Bkv, c.Lk, c.nh, c.d), 1, gen, torch.float32, dev)
+    Q[..., nt + J_NOISE:] = 0
+    K[..., nt + J_NOISE:] = 0
+    t = torch.arange(nt, device=dev)
+    Q[..., :nt] = (-(J_DELTA / J_SCALE) * (t[None, None, None, :] - peak[..., None]).abs().float()).permute(0, 2, 1, 3)
+    K[..., :nt] = (torch.arange(c.Lk, device=dev)[:, None] // 16 == t[None, :]).float()[None, :, None, :]
+    V = integers((Bkv, c.Lk, c.nh, c.d), 4, gen, torch.float32, dev)
+    dO = integers((c.B, c.Lq, c.nh, c.d), 3, gen, torch.float32, dev)
+    return dict(Q=Q, K=K, V=V, dO=dO, key_mask=km)
+
+
+def assert_tent_condition(c, P, al, name):
+    """The condition of family J, in float64: every (batch row, head, 16-query tile) holds, for every border between two update
+    groups, a row with at least 1 / 16 of its probability on each side.  Two things bound it.  A border COUNTS for a tile when
+    every row of the tile that can straddle a border at all can straddle this one (tent_reach: J_NEAR = 3 keys in sight on each
+    side; with ONE key beyond the border, as at 65 and 129 keys, that key holds 1 / (1 + 16 (e^-0.5 + e^-1 + ...)) = 4.5 % at
+    best).  And a tile with fewer such rows than counting borders (one query against 293 keys) must straddle as many borders as
+    it has rows.  For a full tile without the causal mask that is the condition as stated.  Returns the number of (batch row,
+    tile, border) it required."""
+    borders = tent_borders(c)
+    if not borders:
+        return 0
+    cum = torch.cumsum(P, -1)                                                  # [B, nh, Lq, Lk]
+    left = torch.stack([cum[..., x - 1] for x in borders], -1)                 # [B, nh, Lq, borders]: mass on the left
+    hit = (left >= J_MASS) & (1 - left >= J_MASS)
+    reach = tent_reach(c, al)[0]                                               # [B, Lq, borders]
+    checked = 0
+    for q0 in range(0, c.Lq, 16):
+        rows = slice(q0, min(q0 + 16, c.Lq))
+        r = reach[:, rows]
+        can = r.any(-1)                                                        # [B, rows]
+        counts = (r | ~can[..., None]).all(1) & can.any(1)[:, None]            # [B, borders]
+        need = torch.minimum(can.sum(1), counts.sum(1))                        # [B]
+        have = (hit[:, :, rows].any(2) & counts[:, None]).sum(-1)              # [B, nh]
+        assert bool((have >= need[:, None]).all()), "%s: queries %d..%d: rows straddle %s of the counting borders, %s are required" % (
+            name, rows.start, rows.stop - 1, have.tolist(), need.tolist())
+        checked += int(need.sum())
+    return checked
+
+
+def tent_bounds(c, ref, inp, dtype, delta_term=True):
+    """The first-order rounding bounds of check_tent, element by element, in float64."""
+    if dtype == BF16:
+        u = uo = 2.0 ** -9                                                     # one rounding of the MFMA operand formed on the device, one of the stored value
+    else:
+        u, uo = (max(c.Lq, c.Lk) + 8) * 2.0 ** -24, 2.0 ** -24                 # exact_attn_maps.check_integer_scores' form
+    x = lambda n: (inp[n].double().repeat_interleave(c.kv_group, 0) if n in ("K", "V") else inp[n].double()).abs()
+    Pd, dS = ref["Pd"].abs(), ref["dS"].abs()
+    b = dict(O=u * torch.einsum("bhqk,bkhd->bqhd", Pd, x("V")) + uo * ref["O"].abs(),
+             LSE=(c.Lk + 8) * 2.0 ** -23 * torch.clamp(ref["LSE"].abs(), min=1.0))
+    if "dS" in ref:
+        # delta = rowsum(dO * O) is an fp32 sum of d terms in both modes, and dP * fac - delta cancels: that error is relative to
+        # sum |dO| |O|, not to |dS|, so it gets a term of its own (dP itself is exact: integer V and dO)
+        ed = ((c.d + 8) * 2.0 ** -24 * torch.einsum("bqhd,bqhd->bhq", x("dO"), ref["O"].abs()))[..., None] * ref["P"] * ref["scale"] * float(delta_term)
+        b.update(dV=u * torch.einsum("bhqk,bqhd->bkhd", Pd, x("dO")) + uo * ref["dV"].abs(),
+                 dQ=torch.einsum("bhqk,bkhd->bqhd", u * dS + ed, x("K")) + uo * ref["dQ"].abs(),
+                 dK=torch.einsum("bhqk,bqhd->bkhd", u * dS + ed, x("Q")) + uo * ref["dK"].abs())
+    return b
+
+
+def check_tent(be, c, seed=0, out=None, factors=None, delta_term=True):
+    """Scores with a designed profile (tent_inputs): every row's running maximum moves by 0.5 per 16-key tile towards its peak
+    and the rows of one 16-query tile peak at different tiles, so the online-softmax rescale of attn_fwd_body runs with factors
+    strictly between 0 and 1 in some lanes of a wave and with 1 in others, on rows that keep a sixteenth of their mass on both
+    sides of an update border (assert_tent_condition).  Every output is judged element by element against the float64 reference
+    under the launch's own keep mask (delta from the O the launch stored): |got - ref| <= J_K x the first-order rounding bound
+    of tent_bounds().  `factors`: other factors than J_K (the CPU harness measures with infinity); `delta_term`: tent_bounds
+    without its term for delta (the CPU harness shows that a correct fp32 implementation fails then).  Returns the largest
+    err / bound per output."""
+    dev, dt = be.device, DT[c.dtype]
+    gen = generator(8000 + seed, dev)
+    km = tent_mask(c, gen, dev) if seed % 3 != 2 else None
+    inp = tent_inputs(c, gen, dev, km)
+    got, keep = launch(be, c, inp, seed, c.id + ": tent", scale=J_SCALE)
+    ref = reference(c, inp, keep, scale=J_SCALE, O_stored=got["O"])
+    checked = assert_tent_condition(c, ref["P"], allowed_keys(c, km, dev), c.id + ": tent")
+    assert (checked > 0) == tent_must_straddle(c), "%s: tent: %d border(s) checked, the table says %r" % (c.id, checked, tent_must_straddle(c))
+    bound = tent_bounds(c, ref, inp, dt, delta_term)
+    k = J_K if factors is None else factors
+    ratios, fail = {}, []
+    for nme in ("O", "LSE") + (("dQ", "dK", "dV") if c.has_bwd else ()):
+        g = got[nme].double()
+        assert torch.isfinite(g).all(), "%s: tent %s: non-finite output" % (c.id, nme)
+        r = ref[nme].reshape(g.shape)
+        err, b = (g - r).abs(), bound[nme].reshape(g.shape)
+        ratios[nme] = float(torch.where(b > 0, err / b, torch.where(err > 0, float("inf"), 0.0).to(err)).max())
+        kk = k[(c.dtype, "fwd" if nme in ("O", "LSE") else "bwd")]
+        if ratios[nme] > kk:
+            i = tuple(int(x) for x in torch.nonzero((err > kk * b))[0])
+            fail.append("%s: tent %s: error %.2f x the first-order bound (allowed %g x); first at %s: got %r want %r"
+                        % (c.id, nme, ratios[nme], kk, i, g[i].item(), r[i].item()))
+    if out:
+        out("%s: tent (%d borders straddled) err / bound: %s" % (c.id, checked, ", ".join("%s %.3f" % kv for kv in ratios.items())))
+    assert not fail, "\n".join(fail)
+    return ratios
 
 
 # ---------------------------------------------------------------------------------------------- which cases run which layer

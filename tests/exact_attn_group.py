@@ -57,8 +57,8 @@ class GroupProblem(A.Problem):
     of ONE poisoned [B / G * Lk, 4 * nh * d (+ pad)] buffer -- the cross-attention K/V projection of two decoder layers, the
     second layer's slices are used -- and dK, dV the two halves of one canary [B / G * Lk, 2 * nh * d (+ pad)] buffer."""
 
-    def __init__(self, c, device, seed=0, key_mask=True, wide=False):
-        A.Problem.__init__(self, c, device, seed, key_mask)
+    def __init__(self, c, device, seed=0, key_mask=True, wide=False, scale=None):
+        A.Problem.__init__(self, c, device, seed, key_mask, scale)
         self.wide = wide
         if not wide:
             return
@@ -73,12 +73,12 @@ class GroupProblem(A.Problem):
         self._dK, self._dV = g.view3[..., :H], g.view3[..., H:]
 
 
-def launch(be, c, inp, seed=0, name=None, wide=False, plain=False):
+def launch(be, c, inp, seed=0, name=None, wide=False, plain=False, scale=None):
     """One forward + backward of case c on backend be: windows built (dK, dV NaN before the launch: a row that is not written
     shows), backend run, windows checked.  -> (outputs, keep mask or None)."""
     name = name or c.id
     km = inp.get("key_mask")
-    p = GroupProblem(c, be.device, seed, key_mask=km is not None, wide=wide)
+    p = GroupProblem(c, be.device, seed, key_mask=km is not None, wide=wide, scale=scale)
     p.set(**{k: v for k, v in inp.items() if v is not None})
     p.t("dK").fill_(float("nan"))
     p.t("dV").fill_(float("nan"))
@@ -224,6 +224,54 @@ def check_uniform(be, c, seed=0):
     assert bool(((n & (n - 1)) == 0).all()) and int(n.min()) >= 1
     A.assert_bit_equal(got["dV"], group_sum(ref["dV"], G), c.id + ": uniform dV")
     A.assert_all_zero(got["dK"], c.id + ": uniform dK")
+
+
+def disjoint_must_be_exact(c):
+    """exact_attn.disjoint_must_be_exact for the grouped cases (no causal mask here): fp32 always, bf16 without dropout below
+    256 keys; None: the data decide."""
+    return "exact" if c.dtype == "f32" or (c.p == 0 and c.Lk < 256) else None
+
+
+def check_uniform_dk(be, c, seed=0, out=None):
+    """exact_attn family H across a group: Q on the upper half of the columns, K on the lower, explicit scale 2^-3 -- every score
+    is exactly 0 and P = 1 / n as in check_uniform, but dK = dS^T Q is nonzero: the sum over ALL queries of ALL members of the
+    group.  Where the float64 guards of exact_attn.check_uniform_dk hold (bf16 operands exact, every partial sum below 2^24 units,
+    taken over the WHOLE group) dK and dV are bit-equal to the float64 reference summed over the group, whatever the order of
+    the additions, and dQ and delta to the reference per query row; elsewhere 4 x TOL.  Returns the mode."""
+    dev, dt, G = be.device, A.DT[c.dtype], c.kv_group
+    assert 1.0 / (1.0 - c.p) in (1.0, 2.0)
+    gen = generator(6000 + seed, dev)
+    km = A.pow2_mask(c, gen, dev, seed)
+    inp = dict(A.disjoint_inputs(c, gen, dev), key_mask=km)
+    got, keep = launch(be, c, inp, seed, c.id + ": uniform, disjoint columns", wide=seed % 2 == 1, scale=A.H_SCALE)
+    ref = A.reference(c, inp, keep, scale=A.H_SCALE)
+    n = A.allowed_keys(c, km, dev).sum(-1)
+    assert bool(((n & (n - 1)) == 0).all()) and int(n.min()) >= 1
+    A.assert_bit_equal(got["O"], ref["O"], c.id + ": disjoint O")
+    Kx, Vx = (inp[t].double().repeat_interleave(G, 0) for t in ("K", "V"))
+    # the group's sum runs over (member, query): fold the members into the query axis for the guard
+    fold = lambda x: x.reshape(c.B // G, G, *x.shape[1:])
+    dSg = fold(ref["dS"]).permute(0, 2, 1, 3, 4).reshape(c.B // G, c.nh, G * c.Lq, c.Lk)
+    Pdg = fold(ref["Pd"]).permute(0, 2, 1, 3, 4).reshape(c.B // G, c.nh, G * c.Lq, c.Lk)
+    Qg, dOg = (fold(inp[t].double()).reshape(c.B // G, G * c.Lq, c.nh, c.d) for t in ("Q", "dO"))
+    exact = (A.sum_is_exact("bhqk,bqhd->bkhd", dSg, Qg) and A.sum_is_exact("bhqk,bqhd->bkhd", Pdg, dOg)
+             and A.sum_is_exact("bhqk,bkhd->bqhd", ref["dS"], Kx) and A.sum_is_exact("bhqk,bkhd->bqhd", ref["Pd"], Vx)
+             and (dt == F32 or (A.fits(ref["Pd"], BF16) and A.fits(ref["O"], BF16) and A.fits(ref["dS"], BF16))))
+    want = dict(dK=group_sum(ref["dK"], G), dV=group_sum(ref["dV"], G), dQ=ref["dQ"], delta=ref["delta"])
+    if exact:
+        for nme in ("delta", "dV", "dQ", "dK"):
+            A.assert_bit_equal(got[nme], want[nme], "%s: disjoint %s" % (c.id, nme))
+        assert int((got["dK"] != 0).sum()) > 0 or int(n.max()) < 4, c.id + ": the construction gave dK = 0"
+    else:
+        A.assert_bit_equal(got["dV"], want["dV"], c.id + ": disjoint dV")              # (as check_uniform: P * fac is exact whatever dS holds)
+        for nme in ("dQ", "dK"):
+            A.assert_close(got[nme], want[nme], 4 * A.TOL[dt], "%s: disjoint %s" % (c.id, nme))
+    mode = "exact" if exact else "tol"
+    must = disjoint_must_be_exact(c)
+    assert must is None or mode == must, "%s: disjoint-column backward was checked as %r, the construction promises %r" % (c.id, mode, must)
+    if out:
+        out("%s: disjoint-column backward checked as %s" % (c.id, mode))
+    return mode
 
 
 def check_all_masked_row(be, c, seed=0, out=None):

@@ -1,9 +1,11 @@
 """Exact layer of the attention tests on a real MI355X (tests/exact_attn.py): every route of
 gstvd_attn_fwd / gstvd_attn_bwd through ops.attn_fwd / ops.attn_bwd only.  Every launch names the kernels it expects (the library
 is asked: ops.attn_kernel_symbol) and runs on canary / NaN-poisoned windows with padded leading dimensions.  One-hot attention
-(C), the power-of-two part of uniform attention (D), the invariances (E) and the recovered dropout masks (F) are compared bit for
-bit; the only tolerances are test_ops_gpu.py's tol (restated as exact_attn.TOL), one ulp of the output type, and the derived
-bound of the fully masked row (G).  The harness itself is proved on the CPU by tests/test_exact_attn_harness_cpu.py.
+(C), the power-of-two part of uniform attention (D), the invariances (E), the recovered dropout masks (F), uniform attention on
+disjoint Q / K columns (H: a nonzero dK) and subset attention (I: ties, P = 2^-j) are compared bit for bit; the only tolerances
+are test_ops_gpu.py's tol (restated as exact_attn.TOL), one ulp of the output type, the derived bound of the fully masked row
+(G) and, for the graded rows that walk the online-softmax rescale (J), exact_attn.J_K x the first-order rounding bound of
+exact_attn.tent_bounds, element by element.  The harness itself is proved on the CPU by tests/test_exact_attn_harness_cpu.py.
 
 Premises of C and D that only the hardware can confirm -- __expf(0) == 1, __expf(x) == 0 for x <= -104, __logf(1) == 0, forward
 and backward score expressions rounding alike, __expf(-__logf(2^k)) == 2^-k -- are what these tests assert on every case; see
@@ -34,7 +36,7 @@ class Gpu(object):
     def run(self, p):
         o, c = ops(), p.c
         a = o.attn_desc(p._Q, p._K, p._V, p._O, p.t("LSE"), p.km, c.B, c.nh, c.Lq, c.Lk, c.d, causal=c.causal, mask_neg=c.neg,
-                        drop_p=c.p, site=SITE, rng=self.rng, ldq=p.ld_in, ldk=p.ld_kv, ldv=p.ld_kv, ldo=p.ld_o, kv_group=c.kv_group,
+                        scale=p.scale_arg, drop_p=c.p, site=SITE, rng=self.rng, ldq=p.ld_in, ldk=p.ld_kv, ldv=p.ld_kv, ldo=p.ld_o, kv_group=c.kv_group,
                         kv_bstride=c.kv_bstride, drop_bits=p.bits)
         sym = o.attn_kernel_symbol(a, False)
         assert c.fwd_kernel in sym, "%s: forward would launch %s, the case expects %s" % (c.id, sym, c.fwd_kernel)
@@ -106,6 +108,39 @@ def test_uniform_attention_has_bit_exact_backward_cases_in_both_types():
     for dt in ("f32", "bf16"):
         c = next(c for c in RUNNABLE if c.dtype == dt and c.d == 64 and c.has_bwd and not c.causal and c.p == 0 and c.Lk == 17)
         assert A.check_uniform(be, c, 0) == "exact", c.id
+
+
+# ------------------------------------------------------------------------------------------ H, I, J
+H_CASES = [c for c in RUNNABLE if c.has_bwd]
+ONEPASS_BORDERS = [c for c in RUNNABLE if c.dtype == "bf16" and c.d == 64 and not c.causal and c.has_bwd and c.p > 0 and not c.fused and c.nh <= 2
+                   and ((c.Lk in (64, 65, 256, 257) and c.Lq in (64, 100)) or (c.Lq in (63, 64) and c.Lk == 200))]
+I_CASES = A.first_per_kernel(RUNNABLE, per=2)
+I_CASES += [c for c in ONEPASS_BORDERS + [c for c in RUNNABLE if c.nh > 2] if c not in I_CASES]
+J_CASES = [c for c in RUNNABLE if A.tent_case(c)]
+
+
+@pytest.mark.parametrize("c", H_CASES, ids=ids(H_CASES))
+def test_uniform_attention_on_disjoint_columns_has_an_exact_nonzero_dk(c):
+    A.check_uniform_dk(Gpu(), c, A.CASES.index(c), out=print)
+
+
+@pytest.mark.parametrize("c", I_CASES, ids=ids(I_CASES))
+def test_subset_attention_is_bit_exact_with_ties(c):
+    A.check_subset(Gpu(), c, A.CASES.index(c), out=print)
+
+
+@pytest.mark.parametrize("c", J_CASES, ids=ids(J_CASES))
+def test_graded_rows_through_the_softmax_rescale_stay_inside_the_rounding_bound(c):
+    A.check_tent(Gpu(), c, A.CASES.index(c), out=print)
+
+
+def test_disjoint_columns_and_subsets_reach_a_bit_exact_dk_in_both_types():
+    """The constructions of H and I are not vacuous: a nonzero dK is compared bit for bit in fp32 and in bf16 mode."""
+    be = Gpu()
+    for dt in ("f32", "bf16"):
+        c = next(c for c in RUNNABLE if c.dtype == dt and c.d == 64 and c.has_bwd and not c.causal and c.p == 0 and c.Lk == 17)
+        assert A.check_uniform_dk(be, c, 0) == "exact", c.id
+        assert A.check_subset(be, c, 0) == "exact", c.id
 
 
 # ------------------------------------------------------------------------------------------ E. invariances

@@ -2,7 +2,7 @@
 ops.attn_desc / ops.attn_fwd / ops.attn_group_bwd only, on canary / NaN-poisoned windows with padded leading dimensions, K / V
 and dK / dV also as column slices of a wide buffer.  dQ and delta are compared bit for bit with gstvd_attn_bwd's two-part kernel
 on replicated K / V, dK and dV with a float64 reference at 4 x exact_attn.TOL and bit for bit between runs, against exact integer
-sums (one-hot, uniform attention) and against the draws the grouped forward applied.  The checks themselves are proved on the CPU
+sums (one-hot, uniform attention; uniform attention on disjoint Q / K columns for a nonzero dK) and against the draws the grouped forward applied.  The checks themselves are proved on the CPU
 by tests/test_exact_attn_group_harness_cpu.py."""
 import pytest
 import torch
@@ -29,7 +29,7 @@ class Gpu(object):
 
     def _desc(self, p, **over):
         o, c = ops(), p.c
-        kw = dict(causal=c.causal, mask_neg=c.neg, drop_p=c.p, site=SITE, rng=self.rng, ldq=p.ld_in, ldk=p.ld_kv, ldv=p.ld_kv, ldo=p.ld_o,
+        kw = dict(causal=c.causal, mask_neg=c.neg, scale=p.scale_arg, drop_p=c.p, site=SITE, rng=self.rng, ldq=p.ld_in, ldk=p.ld_kv, ldv=p.ld_kv, ldo=p.ld_o,
                   kv_group=c.kv_group, kv_bstride=c.kv_bstride)
         B = c.B - over.pop("B_minus", 0)
         kw.update(over)
@@ -118,6 +118,18 @@ def test_onehot_attention_sums_the_group_exactly(c):
 @pytest.mark.parametrize("c", EXACT, ids=ids(EXACT))
 def test_uniform_attention_sums_the_group_exactly(c):
     X.check_uniform(Gpu(), c, EXACT.index(c))
+
+
+@pytest.mark.parametrize("c", EXACT, ids=ids(EXACT))
+def test_uniform_attention_on_disjoint_columns_sums_a_nonzero_dk_over_the_group_exactly(c):
+    X.check_uniform_dk(Gpu(), c, EXACT.index(c), out=print)
+
+
+def test_disjoint_columns_reach_a_bit_exact_grouped_dk_in_both_types():
+    be = Gpu()
+    for dt in ("f32", "bf16"):
+        c = next(c for c in EXACT if c.dtype == dt and c.kv_group > 1 and c.p == 0 and c.Lk < 256 and c.Lq > 1)
+        assert X.check_uniform_dk(be, c, EXACT.index(c)) == "exact", c.id
 
 
 @pytest.mark.parametrize("c", MASKED, ids=ids(MASKED))

@@ -10,7 +10,8 @@ import exact_attn_group as X
 
 A = X.A
 DEV = torch.device("cpu")
-MUTANTS = ("mask_of_query_row", "last_member_dropped", "draws_of_kv_row", "row_not_written", "writes_when_refusing")
+MUTANTS = ("mask_of_query_row", "last_member_dropped", "draws_of_kv_row", "row_not_written", "writes_when_refusing",
+           "dk_zero", "dk_first_member_only")
 
 
 class StandIn(object):
@@ -37,7 +38,7 @@ class StandIn(object):
         c = p.c
         G, Bkv = c.kv_group, c.B // c.kv_group
         Q, K, V = p.t("Q").double(), p.t("K").double().repeat_interleave(G, 0), p.t("V").double().repeat_interleave(G, 0)
-        sc = A.scale32(c.d)
+        sc = p.scale
         al = torch.ones(c.B, 1, c.Lq, c.Lk, dtype=torch.bool)
         if p.km is not None:
             row = torch.arange(c.B) % Bkv if mu == "mask_of_query_row" else torch.arange(c.B) // G
@@ -64,7 +65,11 @@ class StandIn(object):
         if mu == "last_member_dropped" and G > 1:
             live = (torch.arange(c.B) % G != G - 1)[:, None, None, None]
             dV, dK = dV * live, dK * live
+        if mu == "dk_first_member_only":                         # dK (not dV) keeps the first member's part only
+            dK = dK * (torch.arange(c.B) % G == 0)[:, None, None, None]
         dVs, dKs = X.group_sum(dV, G).float(), X.group_sum(dK, G).float()
+        if mu == "dk_zero":
+            dKs = dKs * 0
         if mu == "row_not_written":
             dVs[-1, -1] = p.t("dV")[-1, -1].float()
         p.t("dV").copy_(dVs)
@@ -117,8 +122,31 @@ def test_standin_passes_the_exact_families(c):
     be, i = StandIn(), EXACT.index(c)
     X.check_onehot(be, c, i)
     X.check_uniform(be, c, i)
+    X.check_uniform_dk(be, c, i)
     if c.B // c.kv_group >= 2:
         X.check_all_masked_row(be, c, i)
+
+
+def test_disjoint_columns_promise_a_bit_exact_grouped_dk_in_both_types():
+    """disjoint_must_be_exact is not vacuous: groups of two, three and four members with a bit-exact dK in fp32 and in bf16, and check_uniform_dk
+    (which asserts the promise itself) keeps it on the stand-in."""
+    for dt in ("f32", "bf16"):
+        mine = [c for c in EXACT if c.dtype == dt and X.disjoint_must_be_exact(c) == "exact"]
+        assert {2, 3, 4} <= set(c.kv_group for c in mine), dt
+        for c in mine:
+            assert X.check_uniform_dk(StandIn(), c, EXACT.index(c)) == "exact"
+
+
+def test_mutants_of_the_grouped_dk():
+    for c in (X.case("bf16", 32, X.SHAPES[0]), X.case("f32", 64, X.SHAPES[1], p=0.5), X.case("f32", 32, X.SHAPES[2])):
+        X.check_uniform_dk(StandIn(), c, 0)
+        X.check_uniform(StandIn("dk_zero"), c, 0)                                     # family D cannot see it: dK is 0 there
+        X.check_uniform(StandIn("dk_first_member_only"), c, 0)
+        for mu in ("dk_zero", "dk_first_member_only"):
+            with pytest.raises(AssertionError, match="disjoint dK"):
+                X.check_uniform_dk(StandIn(mu), c, 0)
+        with pytest.raises(AssertionError, match="disjoint dK|disjoint dV"):   # (dV is compared first, and is wrong too)
+            X.check_uniform_dk(StandIn("last_member_dropped"), c, 0)
 
 
 DRAWS = [X.case("bf16", 32, X.SHAPES[0], p=0.5), X.case("f32", 64, X.SHAPES[1], p=0.5)]
