@@ -17,6 +17,10 @@ EPI_BIAS, EPI_ADD, EPI_GELU, EPI_DGELU, EPI_DROPOUT = 1, 2, 4, 8, 16
 EPI_COLSUM, EPI_COLSUM_ACC = 32, 64
 EPI_ADAMW = 128
 LN_RESID, LN_EMBED, LN_IMAGE = 0, 1, 2
+RANK_MAX_OPTIONS = 128
+(RANK_N_SPARSE, RANK_N_GT_SKIPPED, RANK_N_NDCG, RANK_N_NDCG_EMPTY, RANK_N_REL_SKIPPED, RANK_N_CALLS, RANK_NDCG_SUM) = range(7)
+RANK_HIST = 8
+RANK_ACC_SLOTS = RANK_HIST + RANK_MAX_OPTIONS + 1
 
 _vp, _i64, _i32, _f32, _u32 = C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_uint32
 
@@ -153,6 +157,13 @@ class DiscRowsDesc(C.Structure):
                 ("tot_rounds", _i32), ("num_options", _i32), ("train", _i32)]
 
 
+class RankMetricsDesc(C.Structure):
+    """gstvd_rank_metrics_t: ranks, ground-truth ranks, NDCG ratios and accumulator additions of L score lists, one call."""
+    _fields_ = [("scores", _vp), ("ld_scores", _i64), ("gt_index", _vp), ("relevance", _vp), ("ld_rel", _i64), ("n_rel", _i64),
+                ("rel_index", _vp), ("discounts", _vp), ("n_discounts", _i64), ("ranks", _vp), ("ld_ranks", _i64),
+                ("gt_rank", _vp), ("ndcg", _vp), ("acc", _vp), ("L", _i64), ("O", _i32), ("reserved_", _i32)]
+
+
 class ColsumEntry(C.Structure):
     _fields_ = [("partial", _vp), ("out", _vp * 3), ("nblk", _i64), ("stride", _i64), ("H", _i64),
                 ("nvec", _i32), ("accumulate", _i32 * 3), ("blk0", _i32)]
@@ -235,6 +246,7 @@ SIGNATURES = {
     "gstvd_cos_topk": (_i32, [_vp, _i64, _i64, _i64, _vp, _i64, _i32, _f32, _i32, _vp, _i64, _vp, _vp, _vp]),
     "gstvd_subseq_replace": (_i32, [C.POINTER(SubseqReplaceDesc), _vp]),
     "gstvd_disc_rows": (_i32, [C.POINTER(DiscRowsDesc), _vp]),
+    "gstvd_rank_metrics": (_i32, [C.POINTER(RankMetricsDesc), _vp]),
     "gstvd_distill_bwd": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _f32, _f32, _i32, _vp, _i64, _vp]),
 }
 

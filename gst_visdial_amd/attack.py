@@ -34,6 +34,7 @@ import contextlib
 import torch
 
 from . import ops
+from . import metrics as _metrics
 from .metrics import SparseGTMetrics, NDCG, scores_to_ranks
 
 ROWS_PER_CALL = 100         # evaluate_gen_attack.py:241
@@ -240,12 +241,18 @@ def score_chunk(model, item, params, epsilon, textattack=None, coref=None):
 
 
 @torch.no_grad()
-def evaluate_attack(model, dataloader, params, epsilon=1.0, mode="vd_eval_val", textattack=None, coref=None, coref_dependency=None):
+def evaluate_attack(model, dataloader, params, epsilon=1.0, mode="vd_eval_val", textattack=None, coref=None, coref_dependency=None,
+                    metrics="host"):
     """The loop of evaluate_gen_attack.evaluate (evaluate_gen_attack.py:233-369) for attack='fgsm', with a masked-LM filler
     (`textattack=` or params["textattack"]) attack='random_token', and with a substituter (`coref=` or params["coref"])
     attack='coreference': chunks of 100 option rows, the metrics of metrics.py; -> (ranks_json, metrics) as evaluate.evaluate
     returns them.  `coref_dependency`: the reference's dependency file, indexed [dialog]['coreference'][chunk] with the dialogs
-    numbered in the loader's order (evaluate_gen_attack.py:318-319); a chunk's entry is a {round: word} dict, possibly empty."""
+    numbered in the loader's order (evaluate_gen_attack.py:318-319); a chunk's entry is a {round: word} dict, possibly empty.
+    `metrics`: "host" -- the classes of metrics.py on the host; "device" -- one metrics.DeviceRankMetrics.observe per batch on the
+    scores where they are, the loop's metric work synchronises only in retrieve (tied options ranked by the stable rule)."""
+    if metrics not in ("host", "device"):
+        raise ValueError("evaluate_attack: metrics must be 'host' or 'device' (got %r)" % (metrics,))
+    on_device = metrics == "device"
     attack = params.get("attack")
     ready = attack == "fgsm" or (attack == "random_token" and _filler(params, textattack) is not None) \
         or (attack == "coreference" and _substituter(params, coref) is not None)
@@ -253,7 +260,10 @@ def evaluate_attack(model, dataloader, params, epsilon=1.0, mode="vd_eval_val", 
         forward_attack(model, {}, params)           # raises, naming what is missing
     if attack == "coreference" and coref_dependency is None:
         raise ValueError("evaluate_attack: attack='coreference' needs coref_dependency= (per dialog, per chunk, a {round: word} dict)")
-    sparse, ndcg, ranks_json = SparseGTMetrics(), NDCG(), []
+    if on_device:
+        dev_metrics, kept, ranks_json = _metrics.DeviceRankMetrics(params["device"]), ([], [], []), []
+    else:
+        sparse, ndcg, ranks_json = SparseGTMetrics(), NDCG(), []
     model.eval()
     dialog_no = 0
     for batch in dataloader:
@@ -280,7 +290,15 @@ def evaluate_attack(model, dataloader, params, epsilon=1.0, mode="vd_eval_val", 
                 out.append(score_chunk(model, item, params, epsilon, textattack=textattack, coref=coref))
         dialog_no += Bd
         scores = torch.cat(out, 0).view(Bd, rounds, options)
-        if mode == "vd_eval_val":
+        if on_device:
+            if mode == "vd_eval_val":
+                with_rel = params.get("vd_version", "1.0") == "1.0"
+                dev_metrics.observe(scores, batch["gt_option_inds"], batch["gt_relevance"] if with_rel else None,
+                                    batch["round_id"] if with_rel else None)
+            else:
+                for keep, t in zip(kept, (_metrics.scores_to_ranks_device(scores), batch["image_id"], batch["round_id"])):
+                    keep.append(t)
+        elif mode == "vd_eval_val":
             sparse.observe(scores, batch["gt_option_inds"])
             if params.get("vd_version", "1.0") == "1.0":
                 rid = batch["round_id"].reshape(Bd)
@@ -290,6 +308,9 @@ def evaluate_attack(model, dataloader, params, epsilon=1.0, mode="vd_eval_val", 
             for i in range(Bd):
                 ranks_json.append({"image_id": batch["image_id"][i].item(), "round_id": int(batch["round_id"][i].item()),
                                    "ranks": [r.item() for r in ranks[i][:]]})
+    if on_device:
+        from .evaluate import ranks_json_of
+        return ranks_json_of(*kept), (dev_metrics.retrieve(reset=True) if mode == "vd_eval_val" else {})
     metrics = {}
     if mode == "vd_eval_val":
         metrics.update(sparse.retrieve(reset=True))

@@ -5,6 +5,7 @@ same metrics; the model work differs in one way that does not change results: ev
 ONCE and shared by its `options` answer candidates instead of being re-encoded per candidate."""
 import torch
 
+from . import metrics as _metrics
 from .metrics import SparseGTMetrics, NDCG, scores_to_ranks
 
 
@@ -58,14 +59,21 @@ def _score_batch_per_row(model, batch, device, rounds_per_call):
 
 
 @torch.no_grad()
-def evaluate(model, dataloader, params, mode="vd_eval_val", scorer=None, group=None):
+def evaluate(model, dataloader, params, mode="vd_eval_val", scorer=None, group=None, metrics="host"):
     """Returns (ranks_json, metrics) like evaluate_gen.evaluate + its logged metric dict.
 
     Multi-GPU: with an initialised process group the dialogs are sharded by batch index (batch i goes to
     rank i % world), there is no exchange on the data path, and the metric state -- the ground-truth ranks, the NDCG
     sums, the ranks json -- is all-gathered once at the end, so every rank returns the metrics of the whole set.
-    `scorer(model, batch, device) -> [B, rounds, options]` defaults to `score_batch`."""
+    `scorer(model, batch, device) -> [B, rounds, options]` defaults to `score_batch`.
+    `metrics`: "host" -- the classes of metrics.py on the host, as the reference has them; "device" -- the scores stay on the
+    device, one metrics.DeviceRankMetrics.observe per batch, and the loop synchronises only in its retrieve (tied options are
+    then ranked by the stable rule; in the test-split modes the ranks cross to the host once, after the loop)."""
     import torch.distributed as dist
+    if metrics == "device":
+        return _evaluate_device(model, dataloader, params, mode, scorer or score_batch, group)
+    if metrics != "host":
+        raise ValueError("evaluate: metrics must be 'host' or 'device' (got %r)" % (metrics,))
     scorer = scorer or score_batch
     sparse, ndcg, ranks_json = SparseGTMetrics(), NDCG(), []
     if hasattr(model, "eval"):
@@ -98,3 +106,45 @@ def evaluate(model, dataloader, params, mode="vd_eval_val", scorer=None, group=N
         metrics.update(sparse.retrieve(reset=True))
         metrics.update(ndcg.retrieve(reset=True))
     return ranks_json, metrics
+
+
+def ranks_json_of(ranks, image_ids, round_ids):
+    """The ranks_json entries of a test-split run from what its loop kept: per batch the int64 ranks [B, 1, options] on the device
+    and the batch's image_id / round_id tensors.  One device-to-host copy for all batches."""
+    if not ranks:
+        return []
+    host = torch.cat([r.squeeze(1) for r in ranks], 0).cpu().tolist()
+    img = torch.cat([t.reshape(-1) for t in image_ids]).tolist()
+    rid = torch.cat([t.reshape(-1) for t in round_ids]).tolist()
+    return [{"image_id": i, "round_id": int(r), "ranks": row} for i, r, row in zip(img, rid, host)]
+
+
+def _evaluate_device(model, dataloader, params, mode, scorer, group):
+    """evaluate(..., metrics="device"): the same loop with the metric state on the device."""
+    import torch.distributed as dist
+    device = params["device"]
+    dev = _metrics.DeviceRankMetrics(device)
+    kept = ([], [], [])
+    if hasattr(model, "eval"):
+        model.eval()
+    sharded = dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1
+    rank, world = (dist.get_rank(group), dist.get_world_size(group)) if sharded else (0, 1)
+    for i, batch in enumerate(dataloader):
+        if i % world != rank:
+            continue
+        scores = scorer(model, batch, device)
+        if mode == "vd_eval_val":
+            with_rel = params.get("vd_version", "1.0") == "1.0" and "gt_relevance" in batch
+            dev.observe(scores, batch["gt_option_inds"], batch["gt_relevance"] if with_rel else None,
+                        batch["round_id"] if with_rel else None)
+        else:
+            for keep, t in zip(kept, (_metrics.scores_to_ranks_device(scores), batch["image_id"], batch["round_id"])):
+                keep.append(t)
+    ranks_json = ranks_json_of(*kept)
+    state = dev.state() if mode == "vd_eval_val" else None
+    if sharded:
+        parts = [None] * world
+        dist.all_gather_object(parts, (state, ranks_json), group=group)
+        state = _metrics.DeviceRankMetrics.merge([p[0] for p in parts]) if mode == "vd_eval_val" else None
+        ranks_json = [e for p in parts for e in p[1]]
+    return ranks_json, (_metrics.DeviceRankMetrics.metrics(state) if mode == "vd_eval_val" else {})

@@ -14,6 +14,7 @@ tests/test_disc_cpu.py."""
 import torch
 
 from . import disc_rows
+from . import metrics as _metrics
 from .metrics import SparseGTMetrics, NDCGBatchSum, scores_to_ranks
 
 
@@ -155,11 +156,18 @@ def score_batch(encoder, batch, params, rows_per_call=200):
 
 
 @torch.no_grad()
-def evaluate_disc(encoder, dataloader, params, eval_batch_size=None, rows_per_call=200):
+def evaluate_disc(encoder, dataloader, params, eval_batch_size=None, rows_per_call=200, metrics="host"):
     """evaluate_disc.py:27-118.  mode 'vd_eval_val': the metrics dict (r@1/5/10, mean, mrr, ndcg); any other eval mode
     ('vd_eval_test'): the ranks_json list.  `eval_batch_size` is kept for the reference's signature: dialogs per batch are read
-    off each batch (the reference's expand needs every batch full)."""
+    off each batch (the reference's expand needs every batch full).
+    `metrics`: "host" -- the scores move to the host and the classes of metrics.py run there, as in the reference; "device" -- the
+    scores stay on the device, the targets are uploaded once per batch, one metrics.DeviceRankMetrics.observe per batch, and the
+    loop synchronises only in its retrieve (tied options are then ranked by the stable rule)."""
     mode = params["mode"]
+    if metrics == "device":
+        return _evaluate_disc_device(encoder, dataloader, params, rows_per_call)
+    if metrics != "host":
+        raise ValueError("evaluate_disc: metrics must be 'host' or 'device' (got %r)" % (metrics,))
     sparse, ndcg, ranks_json = SparseGTMetrics(), NDCGBatchSum(), []
     _module(encoder).eval()
     for batch in dataloader:
@@ -183,3 +191,26 @@ def evaluate_disc(encoder, dataloader, params, eval_batch_size=None, rows_per_ca
         metrics.update(ndcg.retrieve(reset=True))
         return metrics
     return ranks_json
+
+
+def _evaluate_disc_device(encoder, dataloader, params, rows_per_call):
+    """evaluate_disc(..., metrics="device"): the same loop with the metric state on the device."""
+    from .evaluate import ranks_json_of
+    mode = params["mode"]
+    dev = _metrics.DeviceRankMetrics(params["device"])
+    kept = ([], [], [])
+    _module(encoder).eval()
+    for batch in dataloader:
+        output = score_batch(encoder, batch, params, rows_per_call)
+        if mode == "vd_eval_val":
+            if disc_rows.is_pooled(batch):
+                gt_option_inds, gt_relevance = disc_rows.eval_targets(batch, params)
+            else:
+                gt_option_inds, gt_relevance = batch["gt_option_inds"], batch["gt_relevance"]
+            dev.observe(output, gt_option_inds, gt_relevance, batch["round_id"])
+        else:
+            for keep, t in zip(kept, (_metrics.scores_to_ranks_device(output), batch["image_id"], batch["round_id"])):
+                keep.append(t)
+    if mode == "vd_eval_val":
+        return dev.retrieve(reset=True)
+    return ranks_json_of(*kept)

@@ -1283,6 +1283,72 @@ def disc_rows(cap, ques, ans, opts, gt_index, row_dialog, row_round, row_slot, T
     return o
 
 
+RANK_MAX_OPTIONS = L.RANK_MAX_OPTIONS      # options of a list gstvd_rank_metrics covers (a lane owns options i and i + 64)
+RANK_ACC_SLOTS = L.RANK_ACC_SLOTS          # int64 slots of its accumulator: the counts, the bits of the float64 ndcg sum, hist[0..128]
+RANK_N_SPARSE, RANK_N_GT_SKIPPED, RANK_N_NDCG, RANK_N_NDCG_EMPTY = L.RANK_N_SPARSE, L.RANK_N_GT_SKIPPED, L.RANK_N_NDCG, L.RANK_N_NDCG_EMPTY
+RANK_N_REL_SKIPPED, RANK_N_CALLS, RANK_NDCG_SUM, RANK_HIST = L.RANK_N_REL_SKIPPED, L.RANK_N_CALLS, L.RANK_NDCG_SUM, L.RANK_HIST
+
+
+def rank_metrics(scores, gt_index=None, relevance=None, rel_index=None, discounts=None, ranks=None, gt_rank=None, ndcg=None, acc=None):
+    """Ranks, ground-truth ranks, NDCG ratios and accumulator additions of L score lists of O <= 128 options in one call without a
+    host synchronisation (gstvd_rank_metrics; the rule -- the stable descending sort, the sequential float64 NDCG sums, the
+    add-only accumulator -- is stated in include/gstvd_hip.h).
+    scores fp32 [L, O] (dense rows, row stride free); gt_index int64 [L]; relevance fp32 [n_rel, O] (dense rows); rel_index int32 [L]
+    (-1: no relevance row; None: row l, n_rel == L); discounts fp32 [>= O] = log2(arange(O) + 2) computed on the host, required with
+    relevance.  Outputs are caller-owned and each optional: ranks int64 [L, O] (dense rows), gt_rank int32 [L] (needs gt_index),
+    ndcg fp32 [L] (required with relevance), acc int64 [RANK_ACC_SLOTS] (added to).  Returns a dict of the outputs written."""
+    who = "rank_metrics"
+    _rows_i64(who, "scores", scores, None, torch.float32)
+    n, O = scores.shape
+    if n < 1 or not 1 <= O <= RANK_MAX_OPTIONS:
+        raise L.GstvdError("%s: scores must be [L >= 1, 1 <= O <= %d] (got %d x %d)" % (who, RANK_MAX_OPTIONS, n, O))
+    if gt_index is not None:
+        _flag_vec(who, "gt_index", gt_index, n, torch.int64)
+    if gt_rank is not None:
+        if gt_index is None:
+            raise L.GstvdError("%s: gt_rank needs gt_index" % who)
+        _flag_vec(who, "gt_rank", gt_rank, n, torch.int32)
+    n_rel = 0
+    if relevance is not None:
+        n_rel = _rows_i64(who, "relevance", relevance, O, torch.float32).shape[0]
+        if discounts is None:
+            raise L.GstvdError("%s: relevance needs discounts, fp32 log2(arange(O) + 2) computed on the host" % who)
+        if not isinstance(discounts, torch.Tensor) or discounts.dtype != torch.float32 or discounts.dim() != 1 \
+                or discounts.numel() < O or not discounts.is_contiguous():
+            raise L.GstvdError("%s: discounts must be a contiguous float32 vector of at least O = %d elements" % (who, O))
+        if ndcg is None:
+            raise L.GstvdError("%s: relevance needs ndcg, the fp32 [L] output of the ratios" % who)
+        if rel_index is not None:
+            _flag_vec(who, "rel_index", rel_index, n, torch.int32)
+        elif n_rel != n:
+            raise L.GstvdError("%s: without rel_index, relevance must have one row per list (L = %d, got %d rows)" % (who, n, n_rel))
+        if n_rel < 1:
+            raise L.GstvdError("%s: relevance must have at least one row" % who)
+    elif ndcg is not None or rel_index is not None:
+        raise L.GstvdError("%s: ndcg and rel_index need relevance" % who)
+    if ndcg is not None:
+        _flag_vec(who, "ndcg", ndcg, n, torch.float32)
+    if ranks is not None and tuple(_rows_i64(who, "ranks", ranks, O, torch.int64).shape) != (n, O):
+        raise L.GstvdError("%s: ranks must be int64 [L = %d, O = %d]" % (who, n, O))
+    if acc is not None:
+        _flag_vec(who, "acc", acc, RANK_ACC_SLOTS, torch.int64)
+    for name, t in (("gt_index", gt_index), ("relevance", relevance), ("rel_index", rel_index), ("discounts", discounts), ("ranks", ranks),
+                    ("gt_rank", gt_rank), ("ndcg", ndcg), ("acc", acc)):
+        if t is not None and t.device != scores.device:
+            raise L.GstvdError("%s: %s lives on %s, scores on %s" % (who, name, t.device, scores.device))
+    d = L.RankMetricsDesc()
+    d.scores, d.ld_scores, d.gt_index = _p(scores), max(scores.stride(0), O), _p(gt_index)
+    d.relevance, d.ld_rel, d.n_rel = _p(relevance), (max(relevance.stride(0), O) if relevance is not None else 0), n_rel
+    d.rel_index, d.discounts, d.n_discounts = _p(rel_index), _p(discounts), (discounts.numel() if discounts is not None else 0)
+    d.ranks, d.ld_ranks = _p(ranks), (max(ranks.stride(0), O) if ranks is not None else 0)
+    d.gt_rank, d.ndcg, d.acc, d.L, d.O = _p(gt_rank), _p(ndcg), _p(acc), n, O
+    lib = L.load()
+    e0 = _prof_begin()
+    L.check("gstvd_rank_metrics", lib.gstvd_rank_metrics(C.byref(d), _stream()))
+    _prof_end(e0, "rank_metrics", 0.0, n * O * (4.0 + (8.0 if ranks is not None else 0.0)), (n, O))
+    return {k: v for k, v in (("ranks", ranks), ("gt_rank", gt_rank), ("ndcg", ndcg), ("acc", acc)) if v is not None}
+
+
 FUSION = {"mul": 0, "sum": 1}
 
 

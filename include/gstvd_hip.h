@@ -794,6 +794,56 @@ typedef struct {
 } gstvd_disc_rows_t;
 int gstvd_disc_rows(const gstvd_disc_rows_t* a, gstvd_stream_t s);
 
+/* ---- ranking metrics (entry point added, no signature changed: ABI stays 9) ------------------------------------------------------
+ * gstvd_rank_metrics: L score lists of O options -> the rank of every option, the rank of the ground truth, the NDCG ratio of the
+ * list and additions to a device-resident accumulator: what utils/visdial_metrics.py computes on the host per batch
+ * (scores_to_ranks :21-39, SparseGTMetrics :41-117, NDCG :119-195).  No workspace, allocation or host synchronisation; safe to
+ * capture, and a captured call may be replayed on other contents.  Every output element is written exactly once; the accumulator is
+ * only ever added to, in stream order.
+ * Operands: scores fp32 [L, O] (dense rows, row stride ld_scores); gt_index int64 [L] or NULL; relevance fp32 [n_rel, O] (dense
+ * rows, row stride ld_rel) or NULL; rel_index int32 [L] or NULL: the relevance row of list l, -1 = none; NULL = row l (then
+ * n_rel == L); discounts fp32 [n_discounts >= O], required with relevance: discounts[p] = log2(p + 2), computed by the caller on the
+ * host (torch.log2(torch.arange(O).float() + 2)) so that no device log2 enters a result.
+ * Outputs, each may be NULL: ranks int64 [L, O] (row stride ld_ranks); gt_rank int32 [L] (needs gt_index); ndcg fp32 [L] (needs
+ * relevance, and relevance needs it); acc int64 [GSTVD_RANK_ACC_SLOTS].
+ *   Rank rule: the stable descending sort.  Keys compare as fp32 values, except that NaN is the largest key with all NaNs equal,
+ *     and -0.0 == +0.0.   rank[i] = 1 + #{j : key_j > key_i} + #{j < i : key_j == key_i}
+ *     (= torch.sort(dim=1, descending=True, stable=True); the reference's scores.sort(1, descending=True) is not stable, so the rank
+ *     of tied options is implementation-defined there).
+ *   Sparse rule: 0 <= gt_index[l] < O: gt_rank[l] = rank[gt_index[l]], acc[N_SPARSE] += 1, acc[HIST + gt_rank[l]] += 1.
+ *     Otherwise gt_rank[l] = 0, acc[N_GT_SKIPPED] += 1 and the histogram is unchanged.  Without gt_index none of this happens.
+ *   NDCG rule, list l with relevance row r = rel_index[l] (or l), 0 <= r < n_rel:  k = #{i : rel[r, i] != 0};
+ *       dcg   = sum over p = 0 .. k-1 of rel[r, option of rank p + 1] / discounts[p]
+ *       ideal = the same sum with the options ordered by the rank rule applied to rel[r, :]
+ *     every term ONE fp32 division; the terms added in ascending p, sequentially, in double; each sum then rounded to fp32;
+ *     ndcg[l] = the fp32 quotient dcg / ideal.  k == 0: ndcg[l] = NaN (the reference's 0 / 0).  A finite ndcg[l] adds 1 to
+ *     acc[N_NDCG]; a non-finite one (k == 0, or an ideal sum of 0 or a non-finite relevance) adds 1 to acc[N_NDCG_EMPTY] and stays
+ *     out of the sum -- a stated departure: the reference adds the NaN and poisons its running sum.
+ *     r outside [0, n_rel): ndcg[l] = NaN, no relevance is read, acc[N_REL_SKIPPED] += 1 unless r == -1.
+ *   Accumulator: the counts and the histogram are integer slots (integer atomics: order-independent).  acc[NDCG_SUM] holds the bit
+ *     pattern of a double: a call adds to it the sum of its finite ndcg[l] taken in ascending l, sequentially, in double -- one
+ *     lane of a one-wave launch behind the lists, no float atomics: the same bits on every run.  acc[N_CALLS] += 1 per call.
+ * Limits: 1 <= O <= GSTVD_RANK_MAX_OPTIONS, 1 <= L <= 2^31 - 1.  Refused before the launch, nothing written: scores NULL, relevance
+ * without discounts or ndcg, gt_rank without gt_index, ndcg without relevance (GSTVD_E_NULL); a shape outside the limits, a row
+ * stride below O, n_discounts < O, n_rel < 1, rel_index NULL with n_rel != L (GSTVD_E_SHAPE). */
+enum { GSTVD_RANK_MAX_OPTIONS = 128 };
+enum { GSTVD_RANK_N_SPARSE = 0, GSTVD_RANK_N_GT_SKIPPED = 1, GSTVD_RANK_N_NDCG = 2, GSTVD_RANK_N_NDCG_EMPTY = 3,
+       GSTVD_RANK_N_REL_SKIPPED = 4, GSTVD_RANK_N_CALLS = 5, GSTVD_RANK_NDCG_SUM = 6, /* slot 7 is not used */
+       GSTVD_RANK_HIST = 8,           /* hist[0 .. GSTVD_RANK_MAX_OPTIONS]: hist[r] = lists whose ground truth has rank r */
+       GSTVD_RANK_ACC_SLOTS = 8 + GSTVD_RANK_MAX_OPTIONS + 1 };
+typedef struct {
+  const float* scores; int64_t ld_scores;
+  const int64_t* gt_index;
+  const float* relevance; int64_t ld_rel; int64_t n_rel;
+  const int32_t* rel_index;
+  const float* discounts; int64_t n_discounts;
+  int64_t* ranks; int64_t ld_ranks;
+  int32_t* gt_rank; float* ndcg; int64_t* acc;
+  int64_t L;
+  int32_t O; int32_t reserved_;
+} gstvd_rank_metrics_t;
+int gstvd_rank_metrics(const gstvd_rank_metrics_t* a, gstvd_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
