@@ -31,7 +31,7 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_kernel(GemmP p) {
   const char* gA = p.A + z * p.sA * (int64_t)sizeof(T);
   const char* gB = p.B + z * p.sB * (int64_t)sizeof(T);
 
-  f32x4 acc[MI][NI];
+  f32x4 acc[MI][NI];      // (zero_acc written out: behind the helper the scalar prologue comes out in another order)
 #pragma unroll
   for (int i = 0; i < MI; ++i)
 #pragma unroll
@@ -105,10 +105,7 @@ static int launch_layout(const GemmP& p, int64_t batch, hipStream_t s) {
 }
 
 static int launch_f32(const GemmP& p, int64_t batch, int akm, int bkm, hipStream_t s) {
-  if (!akm && !bkm) return launch_layout<false, false>(p, batch, s);
-  if (!akm && bkm) return launch_layout<false, true>(p, batch, s);
-  if (akm && bkm) return launch_layout<true, true>(p, batch, s);
-  return launch_layout<true, false>(p, batch, s);
+  return by_layout<ALL_LAYOUTS>(akm, bkm, [&](auto a, auto b) { return launch_layout<a.value, b.value>(p, batch, s); });
 }
 
 thread_local const void** gstvd_plan_capture = nullptr;
@@ -136,12 +133,7 @@ static int gemm_params(const gstvd_gemm_t* g, GemmP& p) {
   if ((g->epilogue & GSTVD_EPI_BIAS) && !g->bias) return GSTVD_E_NULL;
   if ((g->epilogue & GSTVD_EPI_ADD) && !g->addend) return GSTVD_E_NULL;
   if ((g->epilogue & (GSTVD_EPI_GELU | GSTVD_EPI_DGELU)) && !g->aux) return GSTVD_E_NULL;
-  p.A = (const char*)g->A; p.B = (const char*)g->B; p.C = (char*)g->C;
-  p.bias = g->bias; p.addend = (const char*)g->addend; p.aux = (char*)g->aux;
-  p.M = g->M; p.N = g->N; p.K = g->K;
-  p.lda = g->lda; p.ldb = g->ldb; p.ldc = g->ldc; p.ldadd = g->ldadd; p.ldaux = g->ldaux;
-  p.sA = g->sA; p.sB = g->sB; p.sC = g->sC; p.sAdd = g->sAdd; p.sAux = g->sAux;
-  p.epi = g->epilogue; p.alpha = g->alpha; p.p = g->dropout_p; p.site = g->site; p.rng = g->rng;
+  p = gemm_p_from(*g);
   return 0;
 }
 

@@ -1,6 +1,8 @@
 // Shared pieces of the GEMM kernels (gemm.hip: register-staged, fp32; gemm_dma.hip, gemm_dma256.hip, gemm_rows.hip, gemv.hip: bf16).
+// The LDS-DMA ring pieces of the three gemm_dma* / gemm_rows files are in gemm_ring.h.
 #pragma once
 #include "common.h"
+#include <type_traits>
 
 struct GemmP {
   const char* A; const char* B; char* C;
@@ -8,15 +10,30 @@ struct GemmP {
   int64_t M, N, K, lda, ldb, ldc, ldadd, ldaux, sA, sB, sC, sAdd, sAux;
   int epi; float alpha, p; uint32_t site; const uint64_t* rng;
 };
+// the C ABI's problem as the kernels take it (no checks: gemm_params / rows_check / the grouped launch's host side do those)
+__host__ __device__ inline GemmP gemm_p_from(const gstvd_gemm_t& g) {
+  GemmP p;
+  p.A = (const char*)g.A; p.B = (const char*)g.B; p.C = (char*)g.C;
+  p.bias = g.bias; p.addend = (const char*)g.addend; p.aux = (char*)g.aux;
+  p.M = g.M; p.N = g.N; p.K = g.K;
+  p.lda = g.lda; p.ldb = g.ldb; p.ldc = g.ldc; p.ldadd = g.ldadd; p.ldaux = g.ldaux;
+  p.sA = g.sA; p.sB = g.sB; p.sC = g.sC; p.sAdd = g.sAdd; p.sAux = g.sAux;
+  p.epi = g.epilogue; p.alpha = g.alpha; p.p = g.dropout_p; p.site = g.site; p.rng = g.rng;
+  return p;
+}
 
 template <typename T> struct TileCfg;
 template <> struct TileCfg<bf16> { static constexpr int VE = 8, BK = 64; };
 template <> struct TileCfg<float> { static constexpr int VE = 4, BK = 32; };
 
 // ---- LDS images -------------------------------------------------------------------------------
-// row-major image: BX rows of 128 bytes (BK elements); 16-byte slot s of row r lives at slot s ^ (r & 7)
-DEVFN int rm_off(int row, int slot) { return row * 128 + (((slot ^ row) & 7) << 4); }
-// k-major bf16 image: BK rows of BX*2 bytes; 32-byte block b of k-row r lives at block b ^ f(r)
+// row-major image of a stage KD elements of 2 bytes deep (fp32: 32 of 4 bytes, the KD = 64 image): BX rows of 2 KD bytes;
+//   KD = 64: 16-byte slot s of row r lives at slot s ^ (r & 7)
+//   KD = 32: 16-byte slot s of row r lives at slot s ^ (2*((r>>3)&1))   (conflict-free ds_read_b128 for the 16x16x32 fragment
+//            pattern; found by exhaustive search over the b128 lane groups)
+template <int KD> DEVFN int rm_slot(int row, int slot) { return KD == 64 ? ((slot ^ row) & 7) : (slot ^ (((row >> 3) & 1) << 1)); }
+template <int KD = 64> DEVFN int rm_off(int row, int slot) { return row * (KD * 2) + (rm_slot<KD>(row, slot) << 4); }
+// k-major bf16 image (either depth): KD k-rows of BX*2 bytes; 32-byte block b of k-row r lives at block b ^ ((r&3) | ((r>>3)&1)<<2)
 template <int BX> DEVFN int km_off_bf16(int krow, int col) {
   constexpr int NB = BX / 16;
   int f = (krow & 3) | (((krow >> 3) & 1) << 2);
@@ -68,11 +85,11 @@ DEVFN void store_tile(const u32x4 (&reg)[NV], char* img, int tid) {
 }
 
 // ---- LDS image -> MFMA fragment ----------------------------------------------------------------
-// bf16: 8 elements k = kk*32 + 8g + j for x = xb + (lane & 15)
-template <int BX, bool KM> DEVFN bf16x8 frag_bf16(const char* img, int xb, int kk, int lane) {
+// bf16: 8 elements k = kk*32 + 8g + j for x = xb + (lane & 15); KD = depth of the image's stage (32: kk = 0)
+template <int BX, bool KM, int KD = 64> DEVFN bf16x8 frag_bf16(const char* img, int xb, int kk, int lane) {
   int g = lane >> 4, li = lane & 15;
   if (!KM) {
-    return *(const bf16x8*)(img + rm_off(xb + li, kk * 4 + g));
+    return *(const bf16x8*)(img + rm_off<KD>(xb + li, kk * 4 + g));
   } else {
     int kr = kk * 32 + 8 * g + (li >> 2), col = xb + 4 * (lane & 3);
     s16x4 lo = lds_tr16(img + km_off_bf16<BX>(kr, col));
@@ -89,6 +106,12 @@ template <int BX, bool KM> DEVFN float frag_f32(const char* img, int xb, int ks,
   return *(const float*)(img + (ks * 4 + g) * km_row_bytes_f32<BX>() + (xb + li) * 4);
 }
 
+template <int MI, int NI> DEVFN void zero_acc(f32x4 (&acc)[MI][NI]) {
+#pragma unroll
+  for (int i = 0; i < MI; ++i)
+#pragma unroll
+    for (int j = 0; j < NI; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+}
 
 // ---- epilogue shared by both main loops: lane owns C[m0 + li][n0 + 4g .. +3] of a 16x16 accumulator tile ----
 template <typename T, typename OT>
@@ -270,14 +293,20 @@ int gemv16_ln_dispatch(const GemmP& p, int64_t batch, int akm, int bkm, int out_
 // gemm_dma256.hip: 256x256x32 tile for problems whose grid still fills the chip
 int gemm_dma256_dispatch(const GemmP& p, int64_t batch, int akm, int bkm, int out_f32, hipStream_t s);
 
-// LDS-DMA issue in inline asm.  The compiler's waitcnt pass treats a *builtin* global_load_lds as a pending LDS write and
-// puts `s_waitcnt vmcnt(0)` in front of every ds_read_b64_tr_b16 that follows (it cannot see that the ring slot being
-// read is not the one being filled) -- which serialises the ring for k-major operands.  Issued from asm the DMA is
-// invisible to that pass; ordering is ours: a counted `s_waitcnt vmcnt(N)` + s_barrier before a slot is read, and
-// `s_waitcnt vmcnt(0)` before the epilogue.  m0 (the LDS destination base) is saved/restored around the instruction.
-DEVFN void glds16_asm(const char* gsrc, unsigned lds_dst_uniform) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(gsrc), "s"(lds_dst_uniform) : "memory");
+// ---- host side: (akm, bkm) and the output type as template arguments ---------------------------------------------------------------
+// f(a, b) is called with two std::bool_constant: a.value = A is k-major, b.value = B is k-major.  TT = false: the launcher has no
+// kernel for k-major A with row-major B ("tt"; nothing is instantiated for it) and the problem is GSTVD_E_UNSUPPORTED.
+constexpr bool ALL_LAYOUTS = true, NO_TT = false;
+template <bool TT, typename F> static int by_layout(int akm, int bkm, F f) {
+  if (!akm && !bkm) return f(std::false_type{}, std::false_type{});
+  if (!akm && bkm) return f(std::false_type{}, std::true_type{});
+  if (akm && bkm) return f(std::true_type{}, std::true_type{});
+  if constexpr (TT) return f(std::true_type{}, std::false_type{});
+  else return GSTVD_E_UNSUPPORTED;
 }
-DEVFN unsigned lds_addr(const char* p) { return (unsigned)(uintptr_t)(__attribute__((address_space(3))) const char*)p; }
+// the same with the output type in front: f(t, a, b), decltype(t)::type = float or bf16
+template <typename T> struct type_tag { using type = T; };
+template <bool TT, typename F> static int by_out_layout(int out_f32, int akm, int bkm, F f) {
+  if (out_f32) return by_layout<TT>(akm, bkm, [&](auto a, auto b) { return f(type_tag<float>{}, a, b); });
+  return by_layout<TT>(akm, bkm, [&](auto a, auto b) { return f(type_tag<bf16>{}, a, b); });
+}

@@ -11,56 +11,8 @@
 //  * tails (M, N, K not tile multiples) never mask lanes: an out-of-range 16-byte unit reads a device-side
 //    zero page instead, so contraction tails are zero filled and the DMA count per stage stays constant;
 //  * blockIdx is remapped so that each XCD (private L2) walks a contiguous range of output tiles.
-#include "gemm_common.h"
+#include "gemm_ring.h"
 #include <stdlib.h>
-
-__device__ __attribute__((aligned(256))) char g_zero_page[256];
-
-
-DEVFN void glds16(const char* src, char* lds_wave_base) {
-  glds16_asm(src, __builtin_amdgcn_readfirstlane(lds_addr(lds_wave_base)));
-}
-
-// Per-thread description of the 16-byte units this thread feeds into one operand image, fixed over the K loop.
-template <int BX, bool KM, int NP, int NT>
-struct DmaUnits {
-  const char* ptr[NP];   // address of the unit in K-tile 0 (meaningless when !okx)
-  int kofs[NP];          // k index of the unit inside a K-tile
-  bool okx[NP];
-  int64_t kstep;         // byte advance per K-tile
-
-  DEVFN void init(const char* g, int64_t ld, int64_t x0, int64_t X, int tid) {
-#pragma unroll
-    for (int i = 0; i < NP; ++i) {
-      const int u = i * NT + tid;
-      int64_t x;
-      if (!KM) {
-        const int r = u >> 3, ls = ((u & 7) ^ r) & 7;
-        x = x0 + r;
-        kofs[i] = ls * 8;
-        ptr[i] = g + (x * ld + ls * 8) * 2;
-      } else {
-        constexpr int VPR = BX / 8, NB = BX / 16;
-        const int kr = u / VPR, cu = u % VPR;
-        const int f = (kr & 3) | (((kr >> 3) & 1) << 2);
-        const int lb = ((cu >> 1) ^ f) & (NB - 1);
-        x = x0 + lb * 16 + (cu & 1) * 8;
-        kofs[i] = kr;
-        ptr[i] = g + ((int64_t)kr * ld + x) * 2;
-      }
-      okx[i] = x < X;
-    }
-    kstep = KM ? 64 * ld * 2 : 128;
-  }
-  DEVFN void issue(int64_t kt, int64_t K, char* img, int wave) const {
-#pragma unroll
-    for (int i = 0; i < NP; ++i) {
-      const bool ok = okx[i] && (kt * 64 + kofs[i] < K);
-      const char* src = ok ? ptr[i] + kt * kstep : (const char*)g_zero_page;
-      glds16(src, img + (i * NT + wave * 64) * 16);
-    }
-  }
-};
 
 // One output tile: the whole K loop + epilogue.  `wg` is the tile's index in the problem's L2-friendly order.
 // Split-K (S > 1): the tile's K range is cut into S contiguous runs of K-tiles, one workgroup each.  Every workgroup
@@ -80,17 +32,17 @@ DEVFN void dma_tile(const GemmP& p, int64_t z, int wg, int ntn, int nwg, char* s
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / WN, wn = wave % WN;
-  // tiles are numbered in column strips 4 n-tiles wide, so ~32 consecutive ids form an (8 m) x (4 n) block
-  const int ntm = nwg / ntn;
-  const int strip = wg / (4 * ntm), sw = (ntn - strip * 4) < 4 ? (ntn - strip * 4) : 4;
-  const int within = wg - strip * 4 * ntm;
-  const int64_t m0 = (int64_t)(within / sw) * BM, n0 = (int64_t)(strip * 4 + within % sw) * BNU;
+  int64_t m0, n0;
+  tile_origin<BM, BNU, 4>(wg, ntn, nwg, m0, n0);       // column strips 4 n-tiles wide
 
   DmaUnits<BM, AKM, NPA, NT> ua;
   DmaUnits<BN, BKM, NPB, NT> ub;
   ua.init(p.A + z * p.sA * 2, p.lda, m0, p.M, tid);
   ub.init(p.B + z * p.sB * 2, p.ldb, n0, (n0 + BNU < p.N) ? n0 + BNU : p.N, tid);    // columns past the tile read the zero page
 
+  // (zero_acc written out: behind the helper the scalar prologue comes out in another order and one or two v_mov_b32 shorter, and
+  // 592x1024x3072 nn ran 20.3-20.7 us against 19.9-20.2; written out every kernel of this file is the earlier code instruction for
+  // instruction, profiles/gemm_refactor_resources.txt.  The split-K re-zero below goes through the helper with no such effect.)
   f32x4 acc[MI][NI];
 #pragma unroll
   for (int i = 0; i < MI; ++i)
@@ -153,10 +105,7 @@ DEVFN void dma_tile(const GemmP& p, int64_t z, int wg, int ntn, int nwg, char* s
     __syncthreads();
     if (*flag != S - 1) return;
     if (tid == 0) __hip_atomic_store(cnt + wg, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // re-armed for the next launch
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-      for (int j = 0; j < NI; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    zero_acc(acc);
     for (int q = 0; q < S; ++q) {
       const float* part = ws + (int64_t)(wg * S + q) * NT * APT + tid;
 #pragma unroll
@@ -169,6 +118,8 @@ DEVFN void dma_tile(const GemmP& p, int64_t z, int wg, int ntn, int nwg, char* s
     }
   }
 
+  // (the tail of gemm_epilogue_wave with a barrier in front of the parking stores, written out: behind the helper three shapes ran 2 % slower
+  // with the K loop's instructions unchanged, profiles/gemm_refactor_resources.txt, tried and not kept)
   const int g = lane >> 4, li = lane & 15;
   const DropKey dk = make_drop((p.epi & GSTVD_EPI_DROPOUT) ? p.p : 0.f, p.site, p.rng);
   constexpr int EPI_LPR = NI <= 1 ? 2 : (NI <= 2 ? 4 : 8);           // lanes per row of the row-wise epilogue
@@ -186,12 +137,6 @@ DEVFN void dma_tile(const GemmP& p, int64_t z, int wg, int ntn, int nwg, char* s
 #pragma unroll
     for (int j = 0; j < NI; ++j)
       gemm_epilogue_tile<bf16, OT>(p, dk, acc[i][j], z, m0 + wm * WTM + i * 16 + li, n0 + wn * WTN + j * 16 + 4 * g);
-}
-
-// XCD-aware block order: blocks b and b+8 share an XCD (private 4 MiB L2); give each XCD a contiguous run of ids
-DEVFN int xcd_remap(int bid, int nwg) {
-  const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
 }
 
 template <typename OT, int BM, int BN, int WM, int WN, bool AKM, bool BKM, int NS, int NIU = 0>
@@ -248,14 +193,6 @@ static int dma_layout(const GemmP& p, int64_t batch, hipStream_t s) {
   return dma_launch<OT, 64, 64, 2, 2, AKM, BKM, 3>(p, batch, s);
 }
 
-template <typename OT>
-static int dma_out(const GemmP& p, int64_t batch, int akm, int bkm, hipStream_t s) {
-  if (!akm && !bkm) return dma_layout<OT, false, false>(p, batch, s);
-  if (!akm && bkm) return dma_layout<OT, false, true>(p, batch, s);
-  if (akm && bkm) return dma_layout<OT, true, true>(p, batch, s);
-  return dma_layout<OT, true, false>(p, batch, s);
-}
-
 constexpr int SPLITK_MAX_TILES = 1024;      // counters occupy the first 4 KiB of the scratch, partials follow
 
 template <typename OT, bool AKM, bool BKM, int NS>
@@ -289,17 +226,13 @@ extern "C" int64_t gstvd_gemm_splitk_ws_bytes(int64_t M, int64_t N, int32_t spli
 }
 
 int gemm_dma_splitk_dispatch(const GemmP& p, int akm, int bkm, int out_f32, int S, void* ws, int64_t ws_bytes, hipStream_t s) {
-  if (akm && !bkm) return GSTVD_E_UNSUPPORTED;
-  if (out_f32) {
-    if (!akm && !bkm) return splitk_launch<float, false, false>(p, S, ws, ws_bytes, s);
-    if (!akm && bkm) return splitk_launch<float, false, true>(p, S, ws, ws_bytes, s);
-    return splitk_launch<float, true, true>(p, S, ws, ws_bytes, s);
-  }
-  if (!akm && !bkm) return splitk_launch<bf16, false, false>(p, S, ws, ws_bytes, s);
-  if (!akm && bkm) return splitk_launch<bf16, false, true>(p, S, ws, ws_bytes, s);
-  return splitk_launch<bf16, true, true>(p, S, ws, ws_bytes, s);
+  return by_out_layout<NO_TT>(out_f32, akm, bkm, [&](auto t, auto a, auto b) {      // no split-K kernels for k-major A with row-major B
+    return splitk_launch<typename decltype(t)::type, a.value, b.value>(p, S, ws, ws_bytes, s);
+  });
 }
 
 int gemm_dma_dispatch(const GemmP& p, int64_t batch, int akm, int bkm, int out_f32, hipStream_t s) {
-  return out_f32 ? dma_out<float>(p, batch, akm, bkm, s) : dma_out<bf16>(p, batch, akm, bkm, s);
+  return by_out_layout<ALL_LAYOUTS>(out_f32, akm, bkm, [&](auto t, auto a, auto b) {
+    return dma_layout<typename decltype(t)::type, a.value, b.value>(p, batch, s);
+  });
 }

@@ -6,13 +6,11 @@
 // This tile stages the same 32 KB per K-step but does 4x the MFMA work per step over half the K depth:
 // 1 B / 128 FLOP.  Same ring / counted-vmcnt / one-barrier structure and the same zero-page tails as gemm_dma.hip.
 //
-// LDS images for a 32-deep K step:
-//   row-major operand  : 256 rows x 64 B; 16-byte slot s of row r lives at slot s ^ (2*((r>>3)&1))   (conflict-free
-//                        ds_read_b128 for the 16x16x32 fragment pattern; found by exhaustive search over the b128 lane groups)
+// LDS images for a 32-deep K step (gemm_common.h: rm_off<32>, km_off_bf16; unit table: DmaUnits<.., 32> of gemm_ring.h):
+//   row-major operand  : 256 rows x 64 B; 16-byte slot s of row r lives at slot s ^ (2*((r>>3)&1))
 //   k-major operand    : 32 k-rows x 512 B; 32-byte block b of k-row r lives at block b ^ ((r&3) | ((r>>3)&1)<<2)
-#include "gemm_common.h"
+#include "gemm_ring.h"
 
-static __device__ __attribute__((aligned(256))) char g_zero_page256[256];
 static constexpr int g_strip_w = 8;      // column-strip width of the tile order (measured 2 / 4 / 8: 31.3 / 30.7 / 30.5 us at 4096x3072x768)
 // Ring depth.  Rounds 1-2 used 5 stages (the whole 160 KB LDS of a CU).  Round 3 measured the K-step slope at 5 / 4 / 3 stages
 // (tools/nt_study.py on three builds): 0.669 / 0.686 / 0.684 us (producer / consumer form), 0.775 / 0.736 / 0.778 us (8-wave form)
@@ -20,67 +18,6 @@ static constexpr int g_strip_w = 8;      // column-strip width of the tile order
 // ~0.8 us off the fill in front of the first MFMA: 29.0 -> 27.8 us at 4096x3072x768, step +0.8 % (1190 vs 1181 rounds/s, three
 // A/B pairs).  The LDS allocation is the larger of the ring and the epilogue's parking space.
 constexpr int NS256 = 3;
-
-DEVFN int opaque_lane(int lane) { asm volatile("" : "+v"(lane)); return lane; }
-DEVFN int rm32_off(int row, int slot) { return row * 64 + ((slot ^ (((row >> 3) & 1) << 1)) << 4); }
-template <int BX> DEVFN int km32_off(int krow, int col) {
-  constexpr int NB = BX / 16;
-  const int f = (krow & 3) | (((krow >> 3) & 1) << 2);
-  return krow * (BX * 2) + ((((col >> 4) ^ f) & (NB - 1)) << 5) + ((col & 15) << 1);
-}
-
-template <int BX, bool KM> DEVFN bf16x8 frag32(const char* img, int xb, int lane) {
-  const int g = lane >> 4, li = lane & 15;
-  if (!KM) {
-    return *(const bf16x8*)(img + rm32_off(xb + li, g));
-  } else {
-    const int kr = 8 * g + (li >> 2), col = xb + 4 * (lane & 3);
-    s16x4 lo = lds_tr16(img + km32_off<BX>(kr, col));
-    s16x4 hi = lds_tr16(img + km32_off<BX>(kr + 4, col));
-    typedef __attribute__((ext_vector_type(8))) short s16x8;
-    s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(bf16x8, v);
-  }
-}
-
-template <int BX, bool KM, int NP, int NT>
-struct Dma32 {
-  const char* ptr[NP];
-  int kofs[NP];
-  bool okx[NP];
-  int64_t kstep;
-  DEVFN void init(const char* g, int64_t ld, int64_t x0, int64_t X, int tid) {
-#pragma unroll
-    for (int i = 0; i < NP; ++i) {
-      const int u = i * NT + tid;
-      int64_t x;
-      if (!KM) {
-        const int r = u >> 2, ls = (u & 3) ^ (((r >> 3) & 1) << 1);
-        x = x0 + r;
-        kofs[i] = ls * 8;
-        ptr[i] = g + (x * ld + ls * 8) * 2;
-      } else {
-        constexpr int VPR = BX / 8, NB = BX / 16;
-        const int kr = u / VPR, cu = u % VPR;
-        const int f = (kr & 3) | (((kr >> 3) & 1) << 2);
-        const int lb = ((cu >> 1) ^ f) & (NB - 1);
-        x = x0 + lb * 16 + (cu & 1) * 8;
-        kofs[i] = kr;
-        ptr[i] = g + ((int64_t)kr * ld + x) * 2;
-      }
-      okx[i] = x < X;
-    }
-    kstep = KM ? 32 * ld * 2 : 64;
-  }
-  DEVFN void issue(int64_t kt, int64_t K, char* img, int wave) const {
-#pragma unroll
-    for (int i = 0; i < NP; ++i) {
-      const bool ok = okx[i] && (kt * 32 + kofs[i] < K);
-      const char* src = ok ? ptr[i] + kt * kstep : (const char*)g_zero_page256;
-      glds16_asm(src, __builtin_amdgcn_readfirstlane(lds_addr(img + (i * NT + wave * 64) * 16)));
-    }
-  }
-};
 
 // NIU = 16-column accumulator tiles per wave actually used (4: the full 256-wide tile; 3: a 192-wide tile inside the same
 // 256-wide LDS image -- N = 3072 then gives 16 x 16 = 256 tiles, one per CU, instead of 192 tiles on 256 CUs).
@@ -97,24 +34,16 @@ DEVFN void dma_tile256(const GemmP& p, int64_t z, int wg, int ntn, int nwg, char
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / WN, wn = wave % WN;
-  // tiles are numbered in column strips g_strip_w n-tiles wide, row-major inside a strip: the ~32 tiles an XCD runs
-  // concurrently form a compact block that shares A rows and B columns in its L2
-  const int ntm = nwg / ntn;
-  const int SWD = g_strip_w;
-  const int strip = wg / (SWD * ntm), sw = (ntn - strip * SWD) < SWD ? (ntn - strip * SWD) : SWD;
-  const int within = wg - strip * SWD * ntm;
-  const int64_t m0 = (int64_t)(within / sw) * BM, n0 = (int64_t)(strip * SWD + within % sw) * BNU;
+  int64_t m0, n0;
+  tile_origin<BM, BNU, g_strip_w>(wg, ntn, nwg, m0, n0);
 
-  Dma32<BM, AKM, NPA, NT> ua;
-  Dma32<BN, BKM, NPB, NT> ub;
+  DmaUnits<BM, AKM, NPA, NT, 32> ua;
+  DmaUnits<BN, BKM, NPB, NT, 32> ub;
   ua.init(p.A + z * p.sA * 2, p.lda, m0, p.M, tid);
   ub.init(p.B + z * p.sB * 2, p.ldb, n0, (n0 + BNU < p.N) ? n0 + BNU : p.N, tid);     // columns past the tile read the zero page
 
   f32x4 acc[MI][NI];
-#pragma unroll
-  for (int i = 0; i < MI; ++i)
-#pragma unroll
-    for (int j = 0; j < NI; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  zero_acc(acc);
 
   const int64_t nkt = (p.K + 31) / 32;
 #pragma unroll
@@ -131,20 +60,15 @@ DEVFN void dma_tile256(const GemmP& p, int64_t z, int wg, int ntn, int nwg, char
     ub.issue(t + NS - 1, p.K, smem + fill * STAGE + A_BYTES, wave);
     const char* cA = smem + slot * STAGE;
     const char* cB = cA + A_BYTES;
-    bf16x8 fb[NI];
-#pragma unroll
-    for (int j = 0; j < NI; ++j) fb[j] = frag32<BN, BKM>(cB, wn * WTN + j * 16, lane);
-#pragma unroll
-    for (int i = 0; i < MI; ++i) {
-      const bf16x8 fa = frag32<BM, AKM>(cA, wm * WTM + i * 16, lane);
-#pragma unroll
-      for (int j = 0; j < NI; ++j) acc[i][j] = mfma_bf16_k32(fb[j], fa, acc[i][j]);
-    }
+    mma_step<MI, NI, false>(acc, [&](int i) { return frag_bf16<BM, AKM, 32>(cA, wm * WTM + i * 16, 0, lane); },
+                            [&](int j) { return frag_bf16<BN, BKM, 32>(cB, wn * WTN + j * 16, 0, lane); });
     slot = (slot + 1 == NS) ? 0 : slot + 1;
     fill = (fill + 1 == NS) ? 0 : fill + 1;
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 
+  // (the tail of gemm_epilogue_wave with a barrier in front of the parking stores, written out: behind the helper the 8-wave tile ran
+  // 2 % slower at 4688 x 18432 x 768, profiles/gemm_refactor_resources.txt, tried and not kept)
   const int g = lane >> 4, li = lane & 15;
   const DropKey dk = make_drop((p.epi & GSTVD_EPI_DROPOUT) ? p.p : 0.f, p.site, p.rng);
   if constexpr (sizeof(OT) == 2) {
@@ -172,9 +96,7 @@ DEVFN void dma_tile256(const GemmP& p, int64_t z, int wg, int ntn, int nwg, char
 // between (the compiler may not move a load across a store it cannot tell apart from it): 3 D 16-byte loads in flight per lane.
 // Rows / columns outside the matrix: loads are clamped onto a valid element (no branch around a load), stores are masked.
 // Addresses: wave-uniform 64-bit bases + one 32-bit lane offset per row group.
-#ifndef ADAMW_PARK_DEPTH
-#define ADAMW_PARK_DEPTH 5
-#endif
+constexpr int ADAMW_PARK_DEPTH = 5;
 template <int NI, int ROWS, int D>
 DEVFN void adamw_rows_pass(const gstvd_adamw_fuse_t& af, float alpha, float lr, float wd, float bc, const float* park, int64_t flat0,
                            int rows_left, int cols_left, unsigned ldc, int lane) {
@@ -236,17 +158,14 @@ DEVFN void pc_tile256(const GemmP& p, int64_t z, int wg, int ntn, int nwg, char*
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const bool producer = wave >= 8;
-  const int ntm = nwg / ntn;
-  const int SWD = g_strip_w;
-  const int strip = wg / (SWD * ntm), sw = (ntn - strip * SWD) < SWD ? (ntn - strip * SWD) : SWD;
-  const int within = wg - strip * SWD * ntm;
-  const int64_t m0 = (int64_t)(within / sw) * BM, n0 = (int64_t)(strip * SWD + within % sw) * BNU;
+  int64_t m0, n0;
+  tile_origin<BM, BNU, g_strip_w>(wg, ntn, nwg, m0, n0);
   const int64_t nkt = (p.K + 31) / 32;
 
   if (producer) {
     const int ptid = tid - 512, pw = wave - 8;
-    Dma32<BM, AKM, NPA, NTP> ua;
-    Dma32<BN, BKM, NPB, NTP> ub;
+    DmaUnits<BM, AKM, NPA, NTP, 32> ua;
+    DmaUnits<BN, BKM, NPB, NTP, 32> ub;
     ua.init(p.A + z * p.sA * 2, p.lda, m0, p.M, ptid);
     ub.init(p.B + z * p.sB * 2, p.ldb, n0, (n0 + BNU < p.N) ? n0 + BNU : p.N, ptid);
 #pragma unroll
@@ -273,7 +192,7 @@ DEVFN void pc_tile256(const GemmP& p, int64_t z, int wg, int ntn, int nwg, char*
         const char* cA = smem + slot * STAGE;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const bf16x8 v = *(const bf16x8*)(cA + km32_off<BM>(rg * 4 + r, cg * 8));
+          const bf16x8 v = *(const bf16x8*)(cA + km_off_bf16<BM>(rg * 4 + r, cg * 8));
 #pragma unroll
           for (int e = 0; e < 8; ++e) cs[e] += (float)v[e];
         }
@@ -337,47 +256,24 @@ DEVFN void pc_tile256(const GemmP& p, int64_t z, int wg, int ntn, int nwg, char*
 
   const int wm = wave / WN, wn = wave % WN;
   f32x4 acc[MI][NI];
-#pragma unroll
-  for (int i = 0; i < MI; ++i)
-#pragma unroll
-    for (int j = 0; j < NI; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  zero_acc(acc);
   int slot = 0;
   for (int64_t t = 0; t < nkt; ++t) {
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     const char* cA = smem + slot * STAGE;
     const char* cB = cA + A_BYTES;
-    bf16x8 fb[NI];
-#pragma unroll
-    for (int j = 0; j < NI; ++j) fb[j] = frag32<BN, BKM>(cB, wn * WTN + j * 16, lane);
-    if constexpr (NIU <= 3) {          // 96 accumulator registers: room for all eight A fragments up front (no spill at 168 VGPRs)
-      bf16x8 fa[MI];
-#pragma unroll
-      for (int i = 0; i < MI; ++i) fa[i] = frag32<BM, AKM>(cA, wm * WTM + i * 16, lane);
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < NI; ++j) acc[i][j] = mfma_bf16_k32(fb[j], fa[i], acc[i][j]);
-    } else {                           // 128 accumulator registers: A fragments two at a time, like dma_tile256
-#pragma unroll
-      for (int i = 0; i < MI; ++i) {
-        const bf16x8 fa = frag32<BM, AKM>(cA, wm * WTM + i * 16, lane);
-#pragma unroll
-        for (int j = 0; j < NI; ++j) acc[i][j] = mfma_bf16_k32(fb[j], fa, acc[i][j]);
-      }
-    }
+    // NIU <= 3: 96 accumulator registers, room for all eight A fragments up front (no spill at 168 VGPRs); 4: as dma_tile256
+    mma_step<MI, NI, (NIU <= 3)>(acc, [&](int i) { return frag_bf16<BM, AKM, 32>(cA, wm * WTM + i * 16, 0, lane); },
+                                 [&](int j) { return frag_bf16<BN, BKM, 32>(cB, wn * WTN + j * 16, 0, lane); });
     slot = (slot + 1 == NS) ? 0 : slot + 1;
   }
   __builtin_amdgcn_s_barrier();       // every producer has drained its DMAs, every consumer is done with the ring: LDS is free
-  // The epilogue's per-lane addresses are derived from an OPAQUE copy of the lane id: derived from `lane` the compiler computes
-  // them in front of the K loop and, at the 168-VGPR cap of three waves per SIMD, spills them across it (8-28 B of scratch per
-  // lane, which also makes the dispatch set up scratch memory) -- VERDICT r5 item 1b.
-  const int lane_e = (sizeof(OT) == 4 || ADAM) ? opaque_lane(lane) : lane;     // (the row-wise bf16 epilogue is better off without it)
-  const int g = lane_e >> 4, li = lane_e & 15;
   if constexpr (ADAM) {
     if (p.epi & GSTVD_EPI_ADAMW) {
       // park 64 rows, let the producer waves update them (adamw_rows_pass), twice
+      const int lane_e = opaque_lane(lane);          // (why: see gemm_epilogue_wave)
+      const int g = lane_e >> 4, li = lane_e & 15;
       constexpr int S = epi_row_floats<NI>(), HB = MI / 2;
       float* park = (float*)(smem + wave * epi_wave_bytes<NI, HB>());
 #pragma unroll
@@ -399,22 +295,7 @@ DEVFN void pc_tile256(const GemmP& p, int64_t z, int wg, int ntn, int nwg, char*
       return;
     }
   }
-  const DropKey dk = make_drop((p.epi & GSTVD_EPI_DROPOUT) ? p.p : 0.f, p.site, p.rng);
-  if constexpr (sizeof(OT) == 2) {
-    if (epilogue_rows_ok(p)) {
-      gemm_epilogue_rows<MI, NI, 4, (NIU >= 4)>(p, dk, acc, z, m0 + wm * WTM, n0 + wn * WTN, smem + wave * epi_wave_bytes<NI, 4>(), lane_e);
-      return;
-    }
-  }
-  // (tile-wise fallback for unaligned operands: fresh opaque lane values per row block keep its 64-bit row / column indices from
-  // being computed up front and spilled at the 168-VGPR cap)
-#pragma unroll
-  for (int i = 0; i < MI; ++i) {
-    const int li_i = opaque_lane(li), g_i = opaque_lane(g);
-#pragma unroll
-    for (int j = 0; j < NI; ++j)
-      gemm_epilogue_tile<bf16, OT>(p, dk, acc[i][j], z, m0 + wm * WTM + i * 16 + li_i, n0 + wn * WTN + j * 16 + 4 * g_i);
-  }
+  gemm_epilogue_wave<OT, MI, NI, (NIU >= 4)>(p, acc, z, m0 + wm * WTM, n0 + wn * WTN, smem + wave * epi_wave_bytes<NI, EPI_HB>(), lane);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -454,8 +335,7 @@ struct Dma64 {
   DEVFN void issue(int64_t j, int64_t J, char* img, int pw) const {
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
-      const char* src = (okx[i] && j < J) ? ptr[i] + j * 128 : (const char*)g_zero_page256;
-      glds16_asm(src, __builtin_amdgcn_readfirstlane(lds_addr(img + (i * 256 + pw * 64) * 16)));
+      glds16((okx[i] && j < J) ? ptr[i] + j * 128 : (const char*)g_zero_page, img + (i * 256 + pw * 64) * 16);
     }
   }
 };
@@ -469,11 +349,8 @@ DEVFN void pc_tile256_nt64(const GemmP& p, int64_t z, int wg, int ntn, int nwg, 
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int ntm = nwg / ntn;
-  const int SWD = g_strip_w;
-  const int strip = wg / (SWD * ntm), sw = (ntn - strip * SWD) < SWD ? (ntn - strip * SWD) : SWD;
-  const int within = wg - strip * SWD * ntm;
-  const int64_t m0 = (int64_t)(within / sw) * BM, n0 = (int64_t)(strip * SWD + within % sw) * BNU;
+  int64_t m0, n0;
+  tile_origin<BM, BNU, g_strip_w>(wg, ntn, nwg, m0, n0);
   const int64_t nkt = p.K / 32, J = p.K / 64;
 
   if (wave >= 8) {                     // ---- producers
@@ -508,85 +385,42 @@ DEVFN void pc_tile256_nt64(const GemmP& p, int64_t z, int wg, int ntn, int nwg, 
 
   const int wm = wave / WN, wn = wave % WN;                        // ---- consumers
   f32x4 acc[MI][NI];
-#pragma unroll
-  for (int i = 0; i < MI; ++i)
-#pragma unroll
-    for (int j = 0; j < NI; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  zero_acc(acc);
   int sa = 0, sb = 0;
-  {
   const int g = lane >> 4, li = lane & 15;
   for (int64_t t = 0; t < nkt; t += 2) {
     const char* cA = smem + sa * A_SLOT;
     const char* cB = smem + B_BASE + sb * B_SLOT;
 #pragma unroll
-    for (int h = 0; h < 2; ++h) {
+    for (int h = 0; h < 2; ++h) {          // the two 32-deep halves of the 64-deep images
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
-      bf16x8 fb[NI];
-#pragma unroll
-      for (int j = 0; j < NI; ++j) fb[j] = *(const bf16x8*)(cB + rm64_off(wn * WTN + j * 16 + li, h * 4 + g));
-      if constexpr (NIU <= 3) {
-        bf16x8 fa[MI];
-#pragma unroll
-        for (int i = 0; i < MI; ++i) fa[i] = *(const bf16x8*)(cA + rm64_off(wm * WTM + i * 16 + li, h * 4 + g));
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int i = 0; i < MI; ++i)
-#pragma unroll
-          for (int j = 0; j < NI; ++j) acc[i][j] = mfma_bf16_k32(fb[j], fa[i], acc[i][j]);
-      } else {
-#pragma unroll
-        for (int i = 0; i < MI; ++i) {
-          const bf16x8 fa = *(const bf16x8*)(cA + rm64_off(wm * WTM + i * 16 + li, h * 4 + g));
-#pragma unroll
-          for (int j = 0; j < NI; ++j) acc[i][j] = mfma_bf16_k32(fb[j], fa, acc[i][j]);
-        }
-      }
+      mma_step<MI, NI, (NIU <= 3)>(acc, [&](int i) { return *(const bf16x8*)(cA + rm64_off(wm * WTM + i * 16 + li, h * 4 + g)); },
+                                   [&](int j) { return *(const bf16x8*)(cB + rm64_off(wn * WTN + j * 16 + li, h * 4 + g)); });
     }
     sa = (sa + 1 == 3) ? 0 : sa + 1;
     sb ^= 1;
   }
-  }
   __builtin_amdgcn_s_barrier();        // every producer has drained its DMAs, every consumer is done with the ring: LDS is free
-  const int lane_e = sizeof(OT) == 4 ? opaque_lane(lane) : lane;        // (see pc_tile256)
-  const int g = lane_e >> 4, li = lane_e & 15;
-  const DropKey dk = make_drop((p.epi & GSTVD_EPI_DROPOUT) ? p.p : 0.f, p.site, p.rng);
-  if constexpr (sizeof(OT) == 2) {
-    if (epilogue_rows_ok(p)) {
-      gemm_epilogue_rows<MI, NI, 4, (NIU >= 4)>(p, dk, acc, z, m0 + wm * WTM, n0 + wn * WTN, smem + wave * epi_wave_bytes<NI, 4>(), lane_e);
-      return;
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < MI; ++i) {
-    const int li_i = opaque_lane(li), g_i = opaque_lane(g);
-#pragma unroll
-    for (int j = 0; j < NI; ++j)
-      gemm_epilogue_tile<bf16, OT>(p, dk, acc[i][j], z, m0 + wm * WTM + i * 16 + li_i, n0 + wn * WTN + j * 16 + 4 * g_i);
-  }
-}
-
-DEVFN int xcd_remap256(int bid, int nwg) {
-  const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+  gemm_epilogue_wave<OT, MI, NI, (NIU >= 4)>(p, acc, z, m0 + wm * WTM, n0 + wn * WTN, smem + wave * epi_wave_bytes<NI, EPI_HB>(), lane);
 }
 
 template <typename OT, bool AKM, bool BKM, int NIU = 4>
 __global__ __launch_bounds__(512) void gemm_dma256_kernel(GemmP p, int ntn, int nwg) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  dma_tile256<OT, AKM, BKM, NIU>(p, blockIdx.y, xcd_remap256(blockIdx.x, nwg), ntn, nwg, smem);
+  dma_tile256<OT, AKM, BKM, NIU>(p, blockIdx.y, xcd_remap(blockIdx.x, nwg), ntn, nwg, smem);
 }
 
 template <typename OT, bool AKM, bool BKM, int NIU = 4>
 __global__ __launch_bounds__(768) void gemm_pc256_kernel(GemmP p, int ntn, int nwg) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  pc_tile256<OT, AKM, BKM, NIU>(p, blockIdx.y, xcd_remap256(blockIdx.x, nwg), ntn, nwg, smem);
+  pc_tile256<OT, AKM, BKM, NIU>(p, blockIdx.y, xcd_remap(blockIdx.x, nwg), ntn, nwg, smem);
 }
 
 template <typename OT, int NIU>
 __global__ __launch_bounds__(768) void gemm_pc256_nt64_kernel(GemmP p, int ntn, int nwg) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  pc_tile256_nt64<OT, NIU>(p, blockIdx.y, xcd_remap256(blockIdx.x, nwg), ntn, nwg, smem);
+  pc_tile256_nt64<OT, NIU>(p, blockIdx.y, xcd_remap(blockIdx.x, nwg), ntn, nwg, smem);
 }
 
 // Which tile of the table a workgroup of a grouped launch runs.
@@ -609,43 +443,38 @@ DEVFN int grouped_tile_id(const int* bmap, int total, int chs) {
   return bid < full ? (((bid >> 3) >> chs) * 8 + (bid & 7)) * (1 << chs) + ((bid >> 3) & ((1 << chs) - 1)) : bid;
 }
 
-// The grouped kernels' prologue, once the workgroup's tile id `gid` is known to name a tile of the table: the problem's GemmP, the
+// The grouped kernels' prologue.  False: this workgroup's entry names no tile of the table.  Otherwise the problem's GemmP, the
 // tile's index inside the problem and the problem's tile grid (ntn columns, nwg tiles).
-DEVFN GemmP grouped_problem(const gstvd_gemm_t* tab, const int* tile_off, int nprob, int gid, int& tile, int& ntn, int& nwg) {
+DEVFN bool grouped_tile(const gstvd_gemm_t* tab, const int* tile_off, int nprob, int total, int chs, const int* bmap, GemmP& p, int& tile,
+                        int& ntn, int& nwg) {
+  const int entry = grouped_tile_id(bmap, total, chs), gid = entry & GROUP_TILE_MASK;
+  if (entry < 0 || gid >= total) return false;
   int lo = 0, hi = nprob - 1;
   while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (tile_off[mid] <= gid) lo = mid; else hi = mid - 1; }
-  const gstvd_gemm_t& g = tab[lo];
-  GemmP p;
-  p.A = (const char*)g.A; p.B = (const char*)g.B; p.C = (char*)g.C;
-  p.bias = g.bias; p.addend = (const char*)g.addend; p.aux = (char*)g.aux;
-  p.M = g.M; p.N = g.N; p.K = g.K;
-  p.lda = g.lda; p.ldb = g.ldb; p.ldc = g.ldc; p.ldadd = g.ldadd; p.ldaux = g.ldaux;
+  p = gemm_p_from(tab[lo]);
   p.sA = p.sB = p.sC = p.sAdd = p.sAux = 0;
-  p.epi = g.epilogue; p.alpha = g.alpha; p.p = g.dropout_p; p.site = g.site; p.rng = g.rng;
-  ntn = (int)((g.N + 255) / 256);
-  nwg = (int)((g.M + 255) / 256) * ntn;
+  ntn = (int)((p.N + 255) / 256);
+  nwg = (int)((p.M + 255) / 256) * ntn;
   tile = gid - tile_off[lo];
-  return p;
+  return true;
 }
 
 template <typename OT, bool AKM, bool BKM>
 __global__ __launch_bounds__(768) void gemm_pc256_grouped_kernel(const gstvd_gemm_t* tab, const int* tile_off, int nprob, int total, int chs,
                                                                  const int* bmap) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int entry = grouped_tile_id(bmap, total, chs);
-  if (entry < 0 || (entry & GROUP_TILE_MASK) >= total) return;
+  GemmP p;
   int tile, ntn, nwg;
-  const GemmP p = grouped_problem(tab, tile_off, nprob, entry & GROUP_TILE_MASK, tile, ntn, nwg);
+  if (!grouped_tile(tab, tile_off, nprob, total, chs, bmap, p, tile, ntn, nwg)) return;
   pc_tile256<OT, AKM, BKM, 4, true>(p, 0, tile, ntn, nwg, smem);
 }
 
 __global__ __launch_bounds__(768) void gemm_pc256_grouped_adamw_kernel(const gstvd_gemm_t* tab, const int* tile_off, int nprob, int total, int chs,
                                                                        const int* bmap, gstvd_adamw_fuse_t af) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int entry = grouped_tile_id(bmap, total, chs);
-  if (entry < 0 || (entry & GROUP_TILE_MASK) >= total) return;
+  GemmP p;
   int tile, ntn, nwg;
-  const GemmP p = grouped_problem(tab, tile_off, nprob, entry & GROUP_TILE_MASK, tile, ntn, nwg);
+  if (!grouped_tile(tab, tile_off, nprob, total, chs, bmap, p, tile, ntn, nwg)) return;
   pc_tile256<float, true, true, 4, true, true>(p, 0, tile, ntn, nwg, smem, af);
 }
 
@@ -661,51 +490,35 @@ constexpr int64_t GEMM256_MIN_TILES = 120;
 // Tiles per XCD chunk of a grouped launch without a block map = 2^GROUP_CHUNK_LOG2 (8: measured best of 1..128 inside the step).
 constexpr int GROUP_CHUNK_LOG2 = 3;
 
+// The (NIU = 4, NIU = 3) instantiations of one kernel: both get their LDS size once, `narrow` (192-wide tiles) picks K3.
+using Kern256 = void (*)(GemmP, int, int);
+template <Kern256 K4, Kern256 K3, int THREADS, int LDS4, int LDS3 = LDS4>
+static int launch_pair256(bool narrow, const dim3& grid, const GemmP& p, int ntn, hipStream_t s) {
+  static int attr_rc = ensure_lds(K4, LDS4) | ensure_lds(K3, LDS3);
+  if (attr_rc) return attr_rc;
+  GSTVD_LAUNCH(narrow ? K3 : K4, grid, dim3(THREADS), narrow ? LDS3 : LDS4, s, p, ntn, (int)grid.x);
+  GSTVD_LAUNCH_CHECK();
+  return 0;
+}
+
 template <typename OT, bool AKM, bool BKM>
 static int launch256(const GemmP& p, int64_t batch, int niu, hipStream_t s) {
   const int bnu = niu == 3 ? 192 : 256;
   const int ntm = (int)((p.M + 255) / 256), ntn = (int)((p.N + bnu - 1) / bnu);
   const dim3 grid((unsigned)(ntm * ntn), (unsigned)batch);
-  if ((int64_t)ntm * ntn * batch > PC256_MAX_TILES) {
-    auto k4 = gemm_dma256_kernel<OT, AKM, BKM, 4>;
-    auto k3 = gemm_dma256_kernel<OT, AKM, BKM, 3>;
-    static int attr_rc = ensure_lds(k4, LDS256) | ensure_lds(k3, LDS256);
-    if (attr_rc) return attr_rc;
-    GSTVD_LAUNCH(bnu == 192 ? k3 : k4, grid, dim3(512), LDS256, s, p, ntn, ntm * ntn);
-    GSTVD_LAUNCH_CHECK();
-    return 0;
-  }
+  if ((int64_t)ntm * ntn * batch > PC256_MAX_TILES)
+    return launch_pair256<gemm_dma256_kernel<OT, AKM, BKM, 4>, gemm_dma256_kernel<OT, AKM, BKM, 3>, 512, LDS256>(niu == 3, grid, p, ntn, s);
   if constexpr (!AKM && !BKM) {
     // full-line (64-deep, alternating) staging of two row-major operands
     if (p.K % 64 == 0 && p.K >= 128) {
-      auto n4 = gemm_pc256_nt64_kernel<OT, 4>;
-      auto n3 = gemm_pc256_nt64_kernel<OT, 3>;
       constexpr int L4 = 3 * 256 * 128 + 2 * 256 * 128, L3 = 3 * 256 * 128 + 2 * 192 * 128;
       constexpr int P4 = 8 * epi_wave_bytes<4, 4>(), P3 = 8 * epi_wave_bytes<3, 4>();
       constexpr int lds4 = L4 > P4 ? L4 : P4, lds3 = L3 > P3 ? L3 : P3;
       static_assert(lds4 <= 160 * 1024 && lds3 <= 160 * 1024, "LDS budget");
-      static int nt_rc = ensure_lds(n4, lds4) | ensure_lds(n3, lds3);
-      if (nt_rc) return nt_rc;
-      GSTVD_LAUNCH(bnu == 192 ? n3 : n4, grid, dim3(768), bnu == 192 ? lds3 : lds4, s, p, ntn, ntm * ntn);
-      GSTVD_LAUNCH_CHECK();
-      return 0;
+      return launch_pair256<gemm_pc256_nt64_kernel<OT, 4>, gemm_pc256_nt64_kernel<OT, 3>, 768, lds4, lds3>(niu == 3, grid, p, ntn, s);
     }
   }
-  auto c4 = gemm_pc256_kernel<OT, AKM, BKM, 4>;
-  auto c3 = gemm_pc256_kernel<OT, AKM, BKM, 3>;
-  static int pc_rc = ensure_lds(c4, LDS256) | ensure_lds(c3, LDS256);
-  if (pc_rc) return pc_rc;
-  GSTVD_LAUNCH(bnu == 192 ? c3 : c4, grid, dim3(768), LDS256, s, p, ntn, ntm * ntn);
-  GSTVD_LAUNCH_CHECK();
-  return 0;
-}
-
-template <typename OT>
-static int launch256_layout(const GemmP& p, int64_t batch, int akm, int bkm, int niu, hipStream_t s) {
-  if (!akm && !bkm) return launch256<OT, false, false>(p, batch, niu, s);
-  if (!akm && bkm) return launch256<OT, false, true>(p, batch, niu, s);
-  if (akm && bkm) return launch256<OT, true, true>(p, batch, niu, s);
-  return GSTVD_E_UNSUPPORTED;
+  return launch_pair256<gemm_pc256_kernel<OT, AKM, BKM, 4>, gemm_pc256_kernel<OT, AKM, BKM, 3>, 768, LDS256>(niu == 3, grid, p, ntn, s);
 }
 
 // Tile width: 256 columns, or 192 when that needs fewer rounds of 256 CUs for the work it does.  Cost model from the
@@ -721,7 +534,9 @@ int gemm_dma256_dispatch(const GemmP& p, int64_t batch, int akm, int bkm, int ou
   const int64_t tiles = ((p.M + 255) / 256) * ((p.N + 255) / 256) * batch;
   if (p.M < 256 || p.N < 256 || tiles < GEMM256_MIN_TILES) return GSTVD_E_UNSUPPORTED;
   const int niu = pick_niu(p, batch);
-  return out_f32 ? launch256_layout<float>(p, batch, akm, bkm, niu, s) : launch256_layout<bf16>(p, batch, akm, bkm, niu, s);
+  return by_out_layout<NO_TT>(out_f32, akm, bkm, [&](auto t, auto a, auto b) {      // k-major A with row-major B: gemm_dma.hip
+    return launch256<typename decltype(t)::type, a.value, b.value>(p, batch, niu, s);
+  });
 }
 
 // Weight gradients are long-K problems (K = rows of the batch): the producer / consumer tile gains ~0.08 us on every one of
@@ -759,12 +574,19 @@ extern "C" int gstvd_gemm_grouped_adamw_kernel_name(char* buf, int32_t buf_len) 
   return copy_kernel_name((const void*)gemm_pc256_grouped_adamw_kernel, buf, buf_len);
 }
 
-extern "C" int gstvd_gemm_grouped_adamw(const gstvd_gemm_t* table_dev, const int32_t* tile_off_dev, int64_t nprob, int64_t total_tiles,
-                                        const gstvd_adamw_fuse_t* f, const int32_t* block_map_dev, int64_t nblocks, gstvd_stream_t stream) {
-  if (!table_dev || !tile_off_dev || !f) return GSTVD_E_NULL;
-  if (!f->grad_base || !f->param || !f->m || !f->v || !f->step) return GSTVD_E_NULL;
+// argument checks shared by the two grouped entry points
+static int grouped_check(const gstvd_gemm_t* table_dev, const int32_t* tile_off_dev, int64_t nprob, int64_t total_tiles,
+                         const int32_t* block_map_dev, int64_t nblocks) {
+  if (!table_dev || !tile_off_dev) return GSTVD_E_NULL;
   if (nprob <= 0 || total_tiles <= 0) return GSTVD_E_SHAPE;
   if (block_map_dev && (nblocks < total_tiles || total_tiles > GROUP_TILE_MASK)) return GSTVD_E_SHAPE;     // a map that cannot name every tile
+  return 0;
+}
+
+extern "C" int gstvd_gemm_grouped_adamw(const gstvd_gemm_t* table_dev, const int32_t* tile_off_dev, int64_t nprob, int64_t total_tiles,
+                                        const gstvd_adamw_fuse_t* f, const int32_t* block_map_dev, int64_t nblocks, gstvd_stream_t stream) {
+  if (!f || !f->grad_base || !f->param || !f->m || !f->v || !f->step) return GSTVD_E_NULL;
+  if (const int crc = grouped_check(table_dev, tile_off_dev, nprob, total_tiles, block_map_dev, nblocks)) return crc;
   if (((uintptr_t)f->grad_base | (uintptr_t)f->param | (uintptr_t)f->m | (uintptr_t)f->v | (uintptr_t)f->shadow_bf16) & 15) return GSTVD_E_ALIGN;
   auto kp = gemm_pc256_grouped_adamw_kernel;
   static int rc = ensure_lds(kp, LDS256);
@@ -778,21 +600,10 @@ extern "C" int gstvd_gemm_grouped_adamw(const gstvd_gemm_t* table_dev, const int
 extern "C" int gstvd_gemm_grouped(const gstvd_gemm_t* table_dev, const int32_t* tile_off_dev, int64_t nprob, int64_t total_tiles,
                                   int32_t dtype_in, int32_t dtype_out, int32_t a_kmajor, int32_t b_kmajor,
                                   const int32_t* block_map_dev, int64_t nblocks, gstvd_stream_t stream) {
-  if (!table_dev || !tile_off_dev) return GSTVD_E_NULL;
-  if (nprob <= 0 || total_tiles <= 0) return GSTVD_E_SHAPE;
-  if (block_map_dev && (nblocks < total_tiles || total_tiles > GROUP_TILE_MASK)) return GSTVD_E_SHAPE;     // a map that cannot name every tile
-  if (dtype_in != GSTVD_BF16) return GSTVD_E_UNSUPPORTED;
-  hipStream_t s = (hipStream_t)stream;
-  const int n = (int)nprob, t = (int)total_tiles, nb = (int)nblocks;
-  const int* bm = block_map_dev;
-  if (dtype_out == GSTVD_F32) {
-    if (a_kmajor && b_kmajor) return grouped256<float, true, true>(table_dev, tile_off_dev, n, t, bm, nb, s);
-    if (!a_kmajor && b_kmajor) return grouped256<float, false, true>(table_dev, tile_off_dev, n, t, bm, nb, s);
-    if (!a_kmajor && !b_kmajor) return grouped256<float, false, false>(table_dev, tile_off_dev, n, t, bm, nb, s);
-  } else if (dtype_out == GSTVD_BF16) {
-    if (a_kmajor && b_kmajor) return grouped256<bf16, true, true>(table_dev, tile_off_dev, n, t, bm, nb, s);
-    if (!a_kmajor && b_kmajor) return grouped256<bf16, false, true>(table_dev, tile_off_dev, n, t, bm, nb, s);
-    if (!a_kmajor && !b_kmajor) return grouped256<bf16, false, false>(table_dev, tile_off_dev, n, t, bm, nb, s);
-  }
-  return GSTVD_E_UNSUPPORTED;
+  if (const int crc = grouped_check(table_dev, tile_off_dev, nprob, total_tiles, block_map_dev, nblocks)) return crc;
+  if (dtype_in != GSTVD_BF16 || (dtype_out != GSTVD_F32 && dtype_out != GSTVD_BF16)) return GSTVD_E_UNSUPPORTED;
+  return by_out_layout<NO_TT>(dtype_out == GSTVD_F32, a_kmajor, b_kmajor, [&](auto t, auto a, auto b) {      // the 256 tile's layouts
+    return grouped256<typename decltype(t)::type, a.value, b.value>(table_dev, tile_off_dev, (int)nprob, (int)total_tiles, block_map_dev,
+                                                                   (int)nblocks, (hipStream_t)stream);
+  });
 }

@@ -18,9 +18,7 @@
 // rounding where ln_fwd / ln_bwd round), so y, mean, rstd, dx, dres are bit-identical to the unfused kernels; the column
 // partials are summed over these 16-row blocks (two rows per wave) instead of 4 / 16-row blocks of one row per wave (fp32
 // reassociation only).
-#include "gemm_common.h"
-
-static __device__ __attribute__((aligned(256))) char g_zero_page_rows[256];
+#include "gemm_ring.h"
 
 struct RowPro {
   gstvd_ln_t f;
@@ -42,43 +40,8 @@ constexpr int rows_kt_max(int NV) { return NV * 4; }
 constexpr int rows_lds(int NV) { return rows_kt_max(NV) * ROWS_A_TILE + ROWS_NS * ROWS_B_TILE; }
 static_assert(4 * 1024 * 4 <= ROWS_B_TILE, "partial scratch must fit the free ring slot");
 
-// B operand: ROWS_NPB 16-byte units per thread and stage (128 columns x 64 k = 16 KB), lane-linear LDS image with the read
-// swizzle applied to the source address (same images as gemm_dma.hip: rm_off / km_off_bf16)
-template <bool KM>
-struct DmaB {
-  const char* ptr[ROWS_NPB]; int kofs[ROWS_NPB]; bool okx[ROWS_NPB]; int64_t kstep;
-  DEVFN void init(const char* g, int64_t ld, int64_t x0, int64_t X, int tid) {
-#pragma unroll
-    for (int i = 0; i < ROWS_NPB; ++i) {
-      const int u = i * ROWS_NT + tid;
-      int64_t x;
-      if (!KM) {
-        const int r = u >> 3, ls = ((u & 7) ^ r) & 7;
-        x = x0 + r;
-        kofs[i] = ls * 8;
-        ptr[i] = g + (x * ld + ls * 8) * 2;
-      } else {
-        constexpr int VPR = ROWS_BN / 8, NB = ROWS_BN / 16;
-        const int kr = u / VPR, cu = u % VPR;
-        const int f = (kr & 3) | (((kr >> 3) & 1) << 2);
-        const int lb = ((cu >> 1) ^ f) & (NB - 1);
-        x = x0 + lb * 16 + (cu & 1) * 8;
-        kofs[i] = kr;
-        ptr[i] = g + ((int64_t)kr * ld + x) * 2;
-      }
-      okx[i] = x < X;
-    }
-    kstep = KM ? 64 * ld * 2 : 128;
-  }
-  DEVFN void issue(int64_t kt, int64_t K, char* img, int wave) const {
-#pragma unroll
-    for (int i = 0; i < ROWS_NPB; ++i) {
-      const bool ok = okx[i] && (kt * 64 + kofs[i] < K);
-      const char* src = ok ? ptr[i] + kt * kstep : (const char*)g_zero_page_rows;
-      glds16_asm(src, __builtin_amdgcn_readfirstlane(lds_addr(img + (i * ROWS_NT + wave * 64) * 16)));
-    }
-  }
-};
+// B operand: ROWS_NPB 16-byte units per thread and stage (128 columns x 64 k = 16 KB), the unit table and images of gemm_dma.hip
+template <bool KM> using DmaB = DmaUnits<ROWS_BN, KM, ROWS_NPB, ROWS_NT>;
 
 DEVFN f32x4 unpack4(const bf16x4& v) { return (f32x4){(float)v[0], (float)v[1], (float)v[2], (float)v[3]}; }
 DEVFN bf16x4 pack4(const f32x4& v) { return (bf16x4){(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3]}; }
@@ -313,12 +276,9 @@ static int rows_check(const gstvd_gemm_t* g, const gstvd_ln_t& f, GemmP& p) {
   if ((g->epilogue & GSTVD_EPI_ADD) && !g->addend) return GSTVD_E_NULL;
   if ((g->epilogue & (GSTVD_EPI_GELU | GSTVD_EPI_DGELU)) && !g->aux) return GSTVD_E_NULL;
   if (g->epilogue & (GSTVD_EPI_COLSUM | GSTVD_EPI_COLSUM_ACC)) return GSTVD_E_UNSUPPORTED;
-  p.A = nullptr; p.B = (const char*)g->B; p.C = (char*)g->C;
-  p.bias = g->bias; p.addend = (const char*)g->addend; p.aux = (char*)g->aux;
-  p.M = g->M; p.N = g->N; p.K = g->K;
-  p.lda = 0; p.ldb = g->ldb; p.ldc = g->ldc; p.ldadd = g->ldadd; p.ldaux = g->ldaux;
+  p = gemm_p_from(*g);
+  p.A = nullptr; p.lda = 0;                 // A is the LayerNorm's output, formed in the kernel
   p.sA = p.sB = p.sC = p.sAdd = p.sAux = 0;
-  p.epi = g->epilogue; p.alpha = g->alpha; p.p = g->dropout_p; p.site = g->site; p.rng = g->rng;
   return 0;
 }
 
