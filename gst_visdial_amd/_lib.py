@@ -12,6 +12,8 @@ LIB_PATH = os.path.join(_HERE, "lib", "libgstvd_hip.so")
 ABI_VERSION = 9
 
 F32, BF16 = 0, 1
+F16 = 2                                # the in-domain filter's entries only
+GAUSS_MAX_D, GAUSS_FIT_SLAB = 1024, 4096
 COS_TOPK_AUTO, COS_TOPK_MANY, COS_TOPK_FEW = 0, 1, 2
 EPI_BIAS, EPI_ADD, EPI_GELU, EPI_DGELU, EPI_DROPOUT = 1, 2, 4, 8, 16
 EPI_COLSUM, EPI_COLSUM_ACC = 32, 64
@@ -164,6 +166,19 @@ class RankMetricsDesc(C.Structure):
                 ("gt_rank", _vp), ("ndcg", _vp), ("acc", _vp), ("L", _i64), ("O", _i32), ("reserved_", _i32)]
 
 
+class GaussFitDesc(C.Structure):
+    """gstvd_gauss_fit_t: mean and covariance of N feature rows in float64, two launches."""
+    _fields_ = [("x", _vp), ("ldx", _i64), ("N", _i64), ("mean", _vp), ("cov", _vp), ("workspace", _vp), ("workspace_bytes", _i64),
+                ("D", _i32), ("dtype", _i32)]
+
+
+class GaussLogprobDesc(C.Structure):
+    """gstvd_gauss_logprob_t: the Gaussian log density of M feature rows and the optional cut at a threshold, one launch."""
+    _fields_ = [("x", _vp), ("ldx", _i64), ("M", _i64), ("mean", _vp), ("w_packed", _vp),
+                ("klog2pi", C.c_double), ("half_log_det", C.c_double), ("threshold", C.c_double),
+                ("out", _vp), ("keep", _vp), ("n_kept", _vp), ("D", _i32), ("dtype", _i32)]
+
+
 class ColsumEntry(C.Structure):
     _fields_ = [("partial", _vp), ("out", _vp * 3), ("nblk", _i64), ("stride", _i64), ("H", _i64),
                 ("nvec", _i32), ("accumulate", _i32 * 3), ("blk0", _i32)]
@@ -247,6 +262,10 @@ SIGNATURES = {
     "gstvd_subseq_replace": (_i32, [C.POINTER(SubseqReplaceDesc), _vp]),
     "gstvd_disc_rows": (_i32, [C.POINTER(DiscRowsDesc), _vp]),
     "gstvd_rank_metrics": (_i32, [C.POINTER(RankMetricsDesc), _vp]),
+    "gstvd_gauss_fit_ws_bytes": (_i64, [_i64, _i32]),
+    "gstvd_gauss_fit": (_i32, [C.POINTER(GaussFitDesc), _vp]),
+    "gstvd_gauss_w_packed_elems": (_i64, [_i32]),
+    "gstvd_gauss_logprob": (_i32, [C.POINTER(GaussLogprobDesc), _vp]),
     "gstvd_distill_bwd": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _f32, _f32, _i32, _vp, _i64, _vp]),
 }
 

@@ -1349,6 +1349,120 @@ def rank_metrics(scores, gt_index=None, relevance=None, rel_index=None, discount
     return {k: v for k, v in (("ranks", ranks), ("gt_rank", gt_rank), ("ndcg", ndcg), ("acc", acc)) if v is not None}
 
 
+GAUSS_MAX_D, GAUSS_FIT_SLAB = L.GAUSS_MAX_D, L.GAUSS_FIT_SLAB
+_GAUSS_DTYPE = {torch.float16: L.F16, torch.float32: L.F32}
+
+
+def _gauss_feats(who, feats, min_rows):
+    """The feature matrix of the in-domain filter: fp16 or fp32 [rows, D], dense rows (row stride free), D % 16 == 0, 16 <= D <= 1024."""
+    if not isinstance(feats, torch.Tensor) or feats.dim() != 2:
+        raise L.GstvdError("%s: feats must be a 2-D tensor [rows, D]" % who)
+    if feats.dtype not in _GAUSS_DTYPE:
+        raise L.GstvdError("%s: feats must be float16 or float32 (got %s)" % (who, str(feats.dtype).replace("torch.", "")))
+    n, D = feats.shape
+    if D % 16 or not 16 <= D <= GAUSS_MAX_D:
+        raise L.GstvdError("%s: D must be a multiple of 16 in [16, %d] (got %d)" % (who, GAUSS_MAX_D, D))
+    if n < min_rows:
+        raise L.GstvdError("%s: feats must have at least %d row%s (got %d)" % (who, min_rows, "s" if min_rows > 1 else "", n))
+    if feats.stride(1) != 1 or (n > 1 and feats.stride(0) < D):
+        raise L.GstvdError("%s: feats must have dense rows (element stride 1, row stride >= D)" % who)
+    if not feats.is_cuda:
+        raise L.GstvdError("%s: feats lives on %s; gst_visdial_amd ops need GPU tensors, there is no CPU path" % (who, feats.device))
+    return n, D
+
+
+def _gauss_f64(who, name, t, shape, device):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise L.GstvdError("%s: %s must be a contiguous float64 tensor of shape %s" % (who, name, list(shape)))
+    if t.device != device:
+        raise L.GstvdError("%s: %s lives on %s, feats on %s" % (who, name, t.device, device))
+    return t
+
+
+def gauss_fit_ws_bytes(N, D):
+    """Bytes of workspace gauss_fit needs for N rows of D features."""
+    need = L.load().gstvd_gauss_fit_ws_bytes(N, D)
+    if need < 0:
+        raise L.GstvdError("gauss_fit_ws_bytes: N = %d, D = %d is outside the rule (N in [2, 2^28], D %% 16 == 0, 16 <= D <= %d)"
+                           % (N, D, GAUSS_MAX_D))
+    return need
+
+
+def gauss_fit(feats, mean=None, cov=None, workspace=None):
+    """Mean float64 [D] and covariance float64 [D, D] of the rows of feats (fp16 or fp32 [N >= 2, D]) in two launches, no host
+    synchronisation (gstvd_gauss_fit; the rule -- two passes, float64 sums in a fixed order, fact = 1/(N-1) applied once, the lower
+    tiles mirrored -- is stated in include/gstvd_hip.h).  mean, cov and workspace (uint8, >= gauss_fit_ws_bytes(N, D)) are
+    caller-owned when given, allocated here otherwise.  Returns (mean, cov)."""
+    who = "gauss_fit"
+    n, D = _gauss_feats(who, feats, 2)
+    if n > (1 << 28):
+        raise L.GstvdError("%s: at most 2^28 rows (got %d)" % (who, n))
+    dev = feats.device
+    mean = torch.empty(D, dtype=torch.float64, device=dev) if mean is None else _gauss_f64(who, "mean", mean, (D,), dev)
+    cov = torch.empty(D, D, dtype=torch.float64, device=dev) if cov is None else _gauss_f64(who, "cov", cov, (D, D), dev)
+    need = gauss_fit_ws_bytes(n, D)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.dim() != 1 \
+            or not workspace.is_contiguous() or workspace.numel() < need:
+        raise L.GstvdError("%s: workspace must be a contiguous uint8 vector of at least %d bytes" % (who, need))
+    elif workspace.device != dev:
+        raise L.GstvdError("%s: workspace lives on %s, feats on %s" % (who, workspace.device, dev))
+    d = L.GaussFitDesc()
+    d.x, d.ldx, d.N, d.mean, d.cov = _p(feats), max(feats.stride(0), D), n, _p(mean), _p(cov)
+    d.workspace, d.workspace_bytes, d.D, d.dtype = _p(workspace), workspace.numel(), D, _GAUSS_DTYPE[feats.dtype]
+    lib = L.load()
+    e0 = _prof_begin()
+    L.check("gstvd_gauss_fit", lib.gstvd_gauss_fit(C.byref(d), _stream()))
+    _prof_end(e0, "gauss_fit", float(n) * D * (D + 64), 2.0 * n * D * feats.element_size(), (n, D))
+    return mean, cov
+
+
+def gauss_pack_w(w):
+    """The lower triangle of W = L^-1 (float64 [D, D], any device; done once per fit, on the host) in the operand order
+    gstvd_gauss_logprob reads: block row t of 16 rows, then K-step s < 4 t + 4, then column c of the step, then row r --
+    packed[128 t (t + 1) + 64 s + 16 c + r] = W[16 t + r, 4 s + c].  Returns a CPU float64 vector."""
+    if not isinstance(w, torch.Tensor) or w.dtype != torch.float64 or w.dim() != 2 or w.shape[0] != w.shape[1] \
+            or w.shape[0] % 16 or not 16 <= w.shape[0] <= GAUSS_MAX_D:
+        raise L.GstvdError("gauss_pack_w: w must be float64 [D, D], D a multiple of 16 in [16, %d]" % GAUSS_MAX_D)
+    w = w.detach().cpu()
+    return torch.cat([w[16 * t:16 * t + 16, :16 * t + 16].t().contiguous().reshape(-1) for t in range(w.shape[0] // 16)])
+
+
+def gauss_logprob(feats, mean, w, klog2pi, half_log_det, out=None, threshold=None, keep=None, n_kept=None):
+    """out[m] = (-0.5 * (klog2pi + |W (feats[m] - mean)|^2)) - half_log_det in float64, one launch (gstvd_gauss_logprob; rule in
+    include/gstvd_hip.h).  feats fp16 or fp32 [M >= 1, D]; mean float64 [D]; w the packed lower triangle of W (gauss_pack_w) on the
+    device; the two constants are Python floats.  With a threshold: keep uint8 [M] receives out[m] >= threshold (a NaN score is
+    never kept) and the int64 [1] counter n_kept is added to; both optional.  A NaN or Inf feature gives a NaN or Inf score and does
+    not raise.  Returns out."""
+    who = "gauss_logprob"
+    M, D = _gauss_feats(who, feats, 1)
+    if M > 0x7fffffff:
+        raise L.GstvdError("%s: at most 2^31 - 1 rows (got %d)" % (who, M))
+    dev = feats.device
+    _gauss_f64(who, "mean", mean, (D,), dev)
+    _gauss_f64(who, "w", w, (128 * (D // 16) * (D // 16 + 1),), dev)
+    out = torch.empty(M, dtype=torch.float64, device=dev) if out is None else _gauss_f64(who, "out", out, (M,), dev)
+    if threshold is None and (keep is not None or n_kept is not None):
+        raise L.GstvdError("%s: keep and n_kept need a threshold" % who)
+    if keep is not None:
+        _flag_vec(who, "keep", keep, M, torch.uint8)
+    if n_kept is not None:
+        _flag_vec(who, "n_kept", n_kept, 1, torch.int64)
+    for name, t in (("keep", keep), ("n_kept", n_kept)):
+        if t is not None and t.device != dev:
+            raise L.GstvdError("%s: %s lives on %s, feats on %s" % (who, name, t.device, dev))
+    d = L.GaussLogprobDesc()
+    d.x, d.ldx, d.M, d.mean, d.w_packed = _p(feats), max(feats.stride(0), D), M, _p(mean), _p(w)
+    d.klog2pi, d.half_log_det, d.threshold = float(klog2pi), float(half_log_det), float(threshold) if threshold is not None else 0.0
+    d.out, d.keep, d.n_kept, d.D, d.dtype = _p(out), _p(keep), _p(n_kept), D, _GAUSS_DTYPE[feats.dtype]
+    lib = L.load()
+    e0 = _prof_begin()
+    L.check("gstvd_gauss_logprob", lib.gstvd_gauss_logprob(C.byref(d), _stream()))
+    _prof_end(e0, "gauss_logprob", float(M) * D * (D + 16), float(M) * D * feats.element_size(), (M, D))
+    return out
+
+
 FUSION = {"mul": 0, "sum": 1}
 
 

@@ -844,6 +844,60 @@ typedef struct {
 } gstvd_rank_metrics_t;
 int gstvd_rank_metrics(const gstvd_rank_metrics_t* a, gstvd_stream_t s);
 
+/* ---- in-domain image filter (entry points added, no signature changed: ABI stays 9) ----------------------------------------------
+ * The first stage of GST (preprocessing/clip_in_domain_filtering.py, from the feature matrix on): fit a multivariate normal to the
+ * image features of the dialog data (cov_mean :54-90), score other images by its log density (MultivariateNormal.log_prob
+ * :183,192) and cut at a threshold.  Feature rows x[n, :] are GSTVD_F16 (IEEE half: what CLIP emits; these two entries alone take
+ * it) or GSTVD_F32, dense rows with a free row stride ldx >= D, D % 16 == 0, 16 <= D <= GSTVD_GAUSS_MAX_D.  Every product and sum
+ * below is in float64.
+ *
+ * gstvd_gauss_fit on x [N, D], N >= 2.  Two passes over the rows, two launches on the caller's stream:
+ *     mean[i] = (sum_n x[n, i]) / N
+ *     S[i, j] = sum_n (x[n, i] - mean[i]) * (x[n, j] - mean[j])
+ *     cov     = fact * S,  fact = 1.0 / (N - 1), applied once, behind the sum
+ *   mean double [D]; cov double [D, D], dense, written in full: the elements with i >= j are computed, cov[j, i] is a copy of
+ *   cov[i, j], so the matrix is symmetric to the bit.  The rows are cut into slabs of GSTVD_GAUSS_FIT_SLAB; the first launch leaves
+ *   one column sum per slab in the workspace, the second adds them in ascending slab order (every workgroup the same way), centres
+ *   the rows on their way into the fp64 MFMA and leaves one 64 x 64 partial tile of S per (lower tile, slab) in the workspace; the
+ *   workgroup that finishes a tile's last slab adds that tile's partials in ascending slab order.  No floating-point atomics: the
+ *   same input gives the same bits on every run.  workspace: gstvd_gauss_fit_ws_bytes(N, D) bytes, 8-byte aligned, caller-owned,
+ *   contents free on entry (the first launch initialises what the second counts in).
+ *
+ * gstvd_gauss_logprob on x [M, D], M >= 1, one launch:
+ *     z = W (x[m, :] - mean),   q = sum_i z_i^2,   out[m] = (-0.5 * (klog2pi + q)) - half_log_det
+ *   W = L^-1 for cov = L L^T (lower triangular; the caller factors on the host, in float64), klog2pi = D * log(2 pi),
+ *   half_log_det = sum_i log L[i, i].  z is never stored.  Only the lower triangle of W is read (the products with the zeros above
+ *   the diagonal are skipped, in 16 x 4 blocks): w_packed holds it in the order the kernel's operand registers take it,
+ *     w_packed[128 * t * (t + 1) + 64 * s + 16 * c + r] = W[16 t + r, 4 s + c]   t < D/16, s < 4 t + 4, c < 4, r < 16
+ *   gstvd_gauss_w_packed_elems(D) = 128 * (D/16) * (D/16 + 1) doubles.  A row's result depends on that row alone: not on M, nor on
+ *   where the row stands in the batch.  A NaN or Inf feature gives a NaN or Inf result and nothing is raised (torch's
+ *   MultivariateNormal validates its argument and raises: a stated departure).  out double [M].
+ *   Cut, optional, same launch: keep uint8 [M]: keep[m] = (out[m] >= threshold), so a NaN score is never kept; n_kept: one int64
+ *   that the kept rows of the call are ADDED to (integer atomic; zero it in front of a loop, read it once behind it).  Either may
+ *   be NULL.
+ * Both: no allocation, no synchronisation, safe under stream capture.  Refused before a launch, nothing written: a NULL operand
+ * (GSTVD_E_NULL), a dtype other than the two (GSTVD_E_DTYPE), D outside the rule, N < 2 or N > 2^28, M < 1 or M > 2^31 - 1,
+ * ldx < D, a workspace smaller than gstvd_gauss_fit_ws_bytes (GSTVD_E_SHAPE), a misaligned workspace (GSTVD_E_ALIGN). */
+enum { GSTVD_F16 = 2 };
+enum { GSTVD_GAUSS_MAX_D = 1024, GSTVD_GAUSS_FIT_SLAB = 4096 };
+typedef struct {
+  const void* x; int64_t ldx; int64_t N;
+  double* mean; double* cov;
+  void* workspace; int64_t workspace_bytes;
+  int32_t D; int32_t dtype;
+} gstvd_gauss_fit_t;
+int64_t gstvd_gauss_fit_ws_bytes(int64_t N, int32_t D);     /* < 0: N or D outside the rule */
+int gstvd_gauss_fit(const gstvd_gauss_fit_t* a, gstvd_stream_t s);
+typedef struct {
+  const void* x; int64_t ldx; int64_t M;
+  const double* mean; const double* w_packed;
+  double klog2pi; double half_log_det; double threshold;
+  double* out; uint8_t* keep; int64_t* n_kept;
+  int32_t D; int32_t dtype;
+} gstvd_gauss_logprob_t;
+int64_t gstvd_gauss_w_packed_elems(int32_t D);              /* < 0: D outside the rule */
+int gstvd_gauss_logprob(const gstvd_gauss_logprob_t* a, gstvd_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
