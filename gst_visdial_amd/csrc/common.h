@@ -241,6 +241,12 @@ DEVFN s16x4 pack_bf16x4(float a, float b, float c, float d) {
 }
 
 #define GSTVD_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return (int)e_; } while (0)
+// opt-in for more than 48 KB of dynamic LDS (call once per kernel: `static int rc = ensure_lds(k, max_bytes)`); 0 or the HIP error
+template <typename K> static int ensure_lds(K kernel, int bytes) {
+  if (bytes <= 48 * 1024) return 0;
+  hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  return e == hipSuccess ? 0 : (int)e;
+}
 
 // Runs the statement(s) `...` with `T` naming the element type of `dtype` (GSTVD_BF16 -> bf16, GSTVD_F32 -> float); any other
 // dtype returns GSTVD_E_DTYPE from the calling function.  A launch spells its argument list once, with T in it.

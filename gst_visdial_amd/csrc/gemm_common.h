@@ -277,12 +277,6 @@ int copy_kernel_name(const void* fn, char* buf, int32_t buf_len);
     else hipLaunchKernelGGL(k_, grid, block, lds, stream, __VA_ARGS__);                                \
   } while (0)
 
-template <typename K> static int ensure_lds(K kernel, int bytes) {
-  if (bytes <= 48 * 1024) return 0;
-  hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  return e == hipSuccess ? 0 : (int)e;
-}
-
 // gemm_dma.hip: bf16 inputs through the LDS-DMA pipelined main loop; returns GSTVD_E_UNSUPPORTED when not applicable
 int gemm_dma_dispatch(const GemmP& p, int64_t batch, int akm, int bkm, int out_f32, hipStream_t s);
 int gemm_dma_splitk_dispatch(const GemmP& p, int akm, int bkm, int out_f32, int S, void* ws, int64_t ws_bytes, hipStream_t s);

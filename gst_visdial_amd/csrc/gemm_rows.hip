@@ -14,16 +14,12 @@
 // (y, mean / rstd; dres, dx, the [3][H] column partials for dgamma / dbeta / dbias), spread over different column tiles so
 // that no workgroup does all of it.  3 of 11 launches per layer and direction disappear.
 //
-// Arithmetic is that of layernorm.hip (same order of operations per row: two-pass variance, wave_sum reductions, bf16
-// rounding where ln_fwd / ln_bwd round), so y, mean, rstd, dx, dres are bit-identical to the unfused kernels; the column
+// The row arithmetic is ln_row.h's, the very functions ln_fwd_kernel / ln_bwd_kernel call (two-pass variance, wave_sum reductions;
+// bf16 rounding where ln_fwd / ln_bwd round), so y, mean, rstd, dx, dres are bit-identical to the unfused kernels; the column
 // partials are summed over these 16-row blocks (two rows per wave) instead of 4 / 16-row blocks of one row per wave (fp32
 // reassociation only).
 #include "gemm_ring.h"
-
-struct RowPro {
-  gstvd_ln_t f;
-  const void* dy; int64_t lddy; void* dres; int64_t lddres; void* dx; int64_t lddx; float* partial;
-};
+#include "ln_row.h"
 
 // Geometry.  The prologue is VALU work (~80 instructions per 4 elements incl. the dropout hash) that EVERY column tile of a row
 // block repeats, so its latency per workgroup decides: 64-row blocks measured 27 / 54 us per launch (forward / backward; 8 us /
@@ -46,10 +42,10 @@ template <bool KM> using DmaB = DmaUnits<ROWS_BN, KM, ROWS_NPB, ROWS_NT>;
 DEVFN f32x4 unpack4(const bf16x4& v) { return (f32x4){(float)v[0], (float)v[1], (float)v[2], (float)v[3]}; }
 DEVFN bf16x4 pack4(const f32x4& v) { return (bf16x4){(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3]}; }
 
-// PRO = 1: LayerNorm forward prologue; PRO = 2: LayerNorm backward prologue.  H = K <= 256 NV, narrower rows handled by the
-// `c < H` guards exactly like layernorm.hip (NV = 3 for H <= 768, NV = 4 for H <= 1024: ln_fwd_nv's / ln_bwd's choice).
+// PRO = 1: LayerNorm forward prologue (r's backward fields are zero); PRO = 2: LayerNorm backward prologue.  H = K <= 256 NV,
+// narrower rows handled by ln_col exactly like layernorm.hip (NV = 3 for H <= 768, NV = 4 for H <= 1024: ln_nv's choice).
 template <typename OT, bool BKM, int PRO, int NV>
-__global__ __launch_bounds__(ROWS_NT, 4) void gemm_rows_kernel(GemmP p, RowPro r, int ntn) {
+__global__ __launch_bounds__(ROWS_NT, 4) void gemm_rows_kernel(GemmP p, gstvd_ln_bwd_t r, int ntn) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int RPW = ROWS_BM / 8;                      // rows per wave in the prologue (2)
   constexpr int HS = NV * 256;                          // stride of a per-wave column-partial slab
@@ -82,10 +78,10 @@ __global__ __launch_bounds__(ROWS_NT, 4) void gemm_rows_kernel(GemmP p, RowPro r
     if (PRO == 2 && rv) { mean_[j] = f.mean[row]; rstd_[j] = f.rstd[row]; }
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
-      const int c = lane * 4 + i * 256;
+      const auto [c, in] = ln_col(lane, i, H);
       const bf16x4 z = {(bf16)0.f, (bf16)0.f, (bf16)0.f, (bf16)0.f};
       px[j][i] = pr[j][i] = pd[j][i] = z;
-      if (rv && c < H) {
+      if (rv && in) {
         px[j][i] = *(const bf16x4*)((const bf16*)f.x + row * f.ldx + c);
         if (has_res) pr[j][i] = *(const bf16x4*)((const bf16*)f.res + row * f.ldres + c);
         if (PRO == 2) pd[j][i] = *(const bf16x4*)((const bf16*)r.dy + row * r.lddy + c);
@@ -95,10 +91,10 @@ __global__ __launch_bounds__(ROWS_NT, 4) void gemm_rows_kernel(GemmP p, RowPro r
   f32x4 gam[NV], bet[NV];
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
-    const int c = lane * 4 + i * 256;
+    const auto [c, in] = ln_col(lane, i, H);
     gam[i] = bet[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    if (c < H && (PRO == 1 || NV <= 3)) gam[i] = *(const f32x4*)(f.gamma + c);
-    if (c < H && PRO == 1) bet[i] = *(const f32x4*)(f.beta + c);
+    if (in && (PRO == 1 || NV <= 3)) gam[i] = *(const f32x4*)(f.gamma + c);
+    if (in && PRO == 1) bet[i] = *(const f32x4*)(f.beta + c);
   }
   // column partials: a column tile emits ONE of the three vectors (tile 0: sum dy * xhat, 1: sum dy, 2: sum dx), so one accumulator
   // (same sums in the same order as three would give; 8 NV registers less -- what lets NV = 4 stay inside 128)
@@ -114,63 +110,53 @@ __global__ __launch_bounds__(ROWS_NT, 4) void gemm_rows_kernel(GemmP p, RowPro r
     f32x4 h[NV];
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
-      const int c = lane * 4 + i * 256;
+      const auto [c, in] = ln_col(lane, i, H);
       h[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-      if (rv && c < H) {
+      if (rv && in) {
         h[i] = unpack4(px[j][i]);
-        h[i] *= drop_factor4(dpre, (uint64_t)(row * f.H + c));
-        if (has_res) h[i] += unpack4(pr[j][i]);
+        ln_resid(h[i], ln_drop(dpre, row, f.H, c), has_res, [&] { return unpack4(pr[j][i]); });
       }
     }
     bf16x4 aout[NV];
     if (PRO == 1) {
-      float s = 0.f;
+      float s = 0.f, v = 0.f;
 #pragma unroll
-      for (int i = 0; i < NV; ++i) s += h[i][0] + h[i][1] + h[i][2] + h[i][3];
-      const float mean = wave_sum(s) / (float)H;
-      float v = 0.f;
+      for (int i = 0; i < NV; ++i) s += ln_sum4(h[i]);            // (zeros beyond H)
+      const float mean = ln_row_mean(s, H);
 #pragma unroll
-      for (int i = 0; i < NV; ++i) {
-        const int c = lane * 4 + i * 256;
-        if (c < H) {
-          const f32x4 d = h[i] - mean;
-          v += d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + d[3] * d[3];
-        }
-      }
-      const float var = wave_sum(v) / (float)H;
-      const float rstd = 1.0f / sqrtf(var + f.eps);
+      for (int i = 0; i < NV; ++i)
+        if (ln_col(lane, i, H).in) v += ln_var_term(h[i], mean, false);
+      const float rstd = ln_rstd(v, H, f.eps);
       if (nt == 1 % ntn && rv && lane == 0) { f.mean[row] = mean; f.rstd[row] = rstd; }
 #pragma unroll
       for (int i = 0; i < NV; ++i) {
-        const int c = lane * 4 + i * 256;
-        const f32x4 y = gam[i] * ((h[i] - mean) * rstd) + bet[i];
+        const auto [c, in] = ln_col(lane, i, H);
+        const f32x4 y = ln_y(h[i], mean, rstd, gam[i], bet[i]);
         aout[i] = pack4(rv ? y : (f32x4){0.f, 0.f, 0.f, 0.f});
-        if (nt == 0 && rv && c < H) *(bf16x4*)((bf16*)f.y + row * f.ldy + c) = aout[i];
+        if (nt == 0 && rv && in) *(bf16x4*)((bf16*)f.y + row * f.ldy + c) = aout[i];
       }
     } else {
       f32x4 xh[NV], gy[NV], dyv[NV];
       float s1 = 0.f, s2 = 0.f;
 #pragma unroll
       for (int i = 0; i < NV; ++i) {
-        const int c = lane * 4 + i * 256;
+        const auto [c, in] = ln_col(lane, i, H);
         xh[i] = gy[i] = dyv[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        if (rv && c < H) {
-          xh[i] = (h[i] - mean_[j]) * rstd_[j];
+        if (rv && in) {
+          xh[i] = ln_xhat(h[i], mean_[j], rstd_[j]);
           dyv[i] = unpack4(pd[j][i]);
-          gy[i] = dyv[i] * (NV > 3 ? *(const f32x4*)(f.gamma + c) : gam[i]);     // (NV = 4: 16 registers the prologue does not have)
-          s1 += gy[i][0] + gy[i][1] + gy[i][2] + gy[i][3];
-          const f32x4 t = gy[i] * xh[i];
-          s2 += t[0] + t[1] + t[2] + t[3];
+          // (NV = 4 reads gamma again: gam[] would be 16 registers the prologue does not have)
+          ln_bwd_sums(dyv[i], NV > 3 ? *(const f32x4*)(f.gamma + c) : gam[i], xh[i], gy[i], s1, s2);
         }
       }
-      const float c1 = wave_sum(s1) / (float)H, c2 = wave_sum(s2) / (float)H;
+      const float c1 = ln_row_mean(s1, H), c2 = ln_row_mean(s2, H);
 #pragma unroll
       for (int i = 0; i < NV; ++i) {
-        const int c = lane * 4 + i * 256;
+        const auto [c, in] = ln_col(lane, i, H);
         f32x4 dx = {0.f, 0.f, 0.f, 0.f};
-        if (rv && c < H) {
-          const f32x4 dh = (gy[i] - c1 - xh[i] * c2) * rstd_[j];
-          dx = dh * drop_factor4(dpre, (uint64_t)(row * f.H + c));
+        if (rv && in) {
+          const f32x4 dh = ln_bwd_dh(gy[i], xh[i], c1, c2, rstd_[j]);
+          dx = dh * ln_drop(dpre, row, f.H, c);
           mv[i] += nt == 0 ? dyv[i] * xh[i] : (nt == 1 ? dyv[i] : dx);
           if (nt == 3 % ntn && r.dres) *(bf16x4*)((bf16*)r.dres + row * r.lddres + c) = pack4(dh);
           if (nt == 4 % ntn && r.dx && (r.dx != r.dres || dpre.on)) *(bf16x4*)((bf16*)r.dx + row * r.lddx + c) = pack4(dx);
@@ -181,8 +167,8 @@ __global__ __launch_bounds__(ROWS_NT, 4) void gemm_rows_kernel(GemmP p, RowPro r
     // row rl of the resident A image: columns c .. c+3 sit in K-tile c / 64, 16-byte slot (c % 64) / 8 (swizzled like rm_off)
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
-      const int c = lane * 4 + i * 256;
-      if (c < H) {
+      const auto [c, in] = ln_col(lane, i, H);
+      if (in) {
         const int kt = c >> 6, slot = (c & 63) >> 3;
         *(bf16x4*)(A_img + kt * ROWS_A_TILE + rm_off(rl, slot) + (c & 7) * 2) = aout[i];
       }
@@ -195,17 +181,17 @@ __global__ __launch_bounds__(ROWS_NT, 4) void gemm_rows_kernel(GemmP p, RowPro r
     float* mine = scratch + (wave & 3) * HS;
     if (wave >= 4) {
 #pragma unroll
-      for (int i = 0; i < NV; ++i) { const int c = lane * 4 + i * 256; if (c < H) *(f32x4*)(mine + c) = mv[i]; }
+      for (int i = 0; i < NV; ++i) { const auto [c, in] = ln_col(lane, i, H); if (in) *(f32x4*)(mine + c) = mv[i]; }
     }
     __syncthreads();
     if (wave < 4) {
 #pragma unroll
-      for (int i = 0; i < NV; ++i) { const int c = lane * 4 + i * 256; if (c < H) mv[i] += *(const f32x4*)(mine + c); }
+      for (int i = 0; i < NV; ++i) { const auto [c, in] = ln_col(lane, i, H); if (in) mv[i] += *(const f32x4*)(mine + c); }
     }
     __syncthreads();
     if (wave < 4) {
 #pragma unroll
-      for (int i = 0; i < NV; ++i) { const int c = lane * 4 + i * 256; if (c < H) *(f32x4*)(mine + c) = mv[i]; }
+      for (int i = 0; i < NV; ++i) { const auto [c, in] = ln_col(lane, i, H); if (in) *(f32x4*)(mine + c) = mv[i]; }
     }
     __syncthreads();
     float* out = r.partial + ((int64_t)mt * 3 + nt) * H;
@@ -248,7 +234,7 @@ __global__ __launch_bounds__(ROWS_NT, 4) void gemm_rows_kernel(GemmP p, RowPro r
 }
 
 template <typename OT, bool BKM, int PRO, int NV>
-static int rows_launch_nv(const GemmP& p, const RowPro& r, hipStream_t s) {
+static int rows_launch_nv(const GemmP& p, const gstvd_ln_bwd_t& r, hipStream_t s) {
   auto k = gemm_rows_kernel<OT, BKM, PRO, NV>;
   static int attr_rc = ensure_lds(k, rows_lds(NV));
   if (attr_rc) return attr_rc;
@@ -258,7 +244,7 @@ static int rows_launch_nv(const GemmP& p, const RowPro& r, hipStream_t s) {
   return 0;
 }
 template <typename OT, bool BKM, int PRO>
-static int rows_launch(const GemmP& p, const RowPro& r, hipStream_t s) {
+static int rows_launch(const GemmP& p, const gstvd_ln_bwd_t& r, hipStream_t s) {
   return r.f.H <= 768 ? rows_launch_nv<OT, BKM, PRO, 3>(p, r, s) : rows_launch_nv<OT, BKM, PRO, 4>(p, r, s);
 }
 
@@ -289,7 +275,7 @@ extern "C" int gstvd_gemm_ln_fwd(const gstvd_gemm_t* g, const gstvd_ln_t* ln, gs
   if (rc) return rc;
   if (!ln->beta || !ln->y) return GSTVD_E_NULL;
   if ((ln->ldy % 4) || ((uintptr_t)ln->y & 7)) return GSTVD_E_ALIGN;
-  RowPro r{};
+  gstvd_ln_bwd_t r{};
   r.f = *ln;
   hipStream_t s = (hipStream_t)stream;
   const bool f32 = g->dtype_out == GSTVD_F32;
@@ -305,9 +291,7 @@ extern "C" int gstvd_gemm_ln_bwd(const gstvd_gemm_t* g, const gstvd_ln_bwd_t* lb
   if (!lb->dy || !lb->partial) return GSTVD_E_NULL;
   if ((lb->lddy % 4) || (lb->dres && (lb->lddres % 4)) || (lb->dx && (lb->lddx % 4))) return GSTVD_E_ALIGN;
   if (lb->nblk != (lb->f.M + ROWS_BM - 1) / ROWS_BM) return GSTVD_E_SHAPE;
-  RowPro r{};
-  r.f = lb->f;
-  r.dy = lb->dy; r.lddy = lb->lddy; r.dres = lb->dres; r.lddres = lb->lddres; r.dx = lb->dx; r.lddx = lb->lddx; r.partial = lb->partial;
+  const gstvd_ln_bwd_t& r = *lb;
   hipStream_t s = (hipStream_t)stream;
   const bool f32 = g->dtype_out == GSTVD_F32;
   if (!g->b_kmajor) return f32 ? rows_launch<float, false, 2>(p, r, s) : rows_launch<bf16, false, 2>(p, r, s);

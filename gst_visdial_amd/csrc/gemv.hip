@@ -6,6 +6,32 @@
 // once), MFMA 16x16x32 accumulates, and the waves' partial tiles are added through LDS.  One memory round trip per launch.
 #include "gemm_common.h"
 
+// The tail of both kernels: the waves' partial tiles are added through `red` (wave 0 goes on alone), then alpha / bias / addend /
+// GELU + aux and the store.  mfma(fb, fa): rows of the result index B's rows (n), columns index A's rows (m), so the lane holds
+// C[m = li][n = n0 + 4 g + r], li = lane & 15, g = lane >> 4.
+template <int NW, bool F32OUT>
+DEVFN void gemv16_tail(const GemmP& p, f32x4 acc, f32x4 (&red)[NW][64], int64_t n0, int wave, int lane, int g, int li) {
+  red[wave][lane] = acc;
+  __syncthreads();
+  if (wave != 0) return;
+#pragma unroll
+  for (int w = 1; w < NW; ++w) acc += red[w][lane];
+  const int64_t m = li, n = n0 + 4 * g;
+  if (m >= p.M || n >= p.N) return;
+  f32x4 v = acc * p.alpha;
+  if (p.epi & GSTVD_EPI_BIAS) v += *(const f32x4*)(p.bias + n);
+  if (p.epi & GSTVD_EPI_ADD)        // the addend has the OUTPUT's type, as in the tiled kernels' epilogue (gemm_epilogue_tile)
+    v += F32OUT ? ld4((const float*)p.addend + m * p.ldadd + n) : ld4((const bf16*)p.addend + m * p.ldadd + n);
+  if (p.epi & GSTVD_EPI_GELU) {
+    f32x4 d;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { float g_, d_; gelu_both<true>(v[e], g_, d_); v[e] = g_; d[e] = d_; }
+    if (p.aux) st4((bf16*)p.aux + m * p.ldaux + n, d);
+  }
+  if (F32OUT) st4((float*)p.C + m * p.ldc + n, v);
+  else st4((bf16*)p.C + m * p.ldc + n, v);
+}
+
 template <int NW, bool F32OUT>
 __global__ __launch_bounds__(NW * 64) void gemv16_kernel(GemmP p) {
   __shared__ f32x4 red[NW][64];
@@ -35,26 +61,7 @@ __global__ __launch_bounds__(NW * 64) void gemv16_kernel(GemmP p) {
 #pragma unroll
     for (int u = 0; u < UNR; ++u) acc = mfma_bf16_k32(fb[u], fa[u], acc);       // D[n = 4g + r][m = li] ... see below
   }
-  // mfma(fb, fa): rows of the result index B's rows (n), columns index A's rows (m): lane holds C[m = li][n = n0 + 4g + r]
-  red[wave][lane] = acc;
-  __syncthreads();
-  if (wave != 0) return;
-#pragma unroll
-  for (int w = 1; w < NW; ++w) acc += red[w][lane];
-  const int64_t m = li, n = n0 + 4 * g;
-  if (m >= p.M || n >= p.N) return;
-  f32x4 v = acc * p.alpha;
-  if (p.epi & GSTVD_EPI_BIAS) v += *(const f32x4*)(p.bias + n);
-  if (p.epi & GSTVD_EPI_ADD)        // the addend has the OUTPUT's type, as in the tiled kernels' epilogue (gemm_epilogue_tile)
-    v += F32OUT ? ld4((const float*)p.addend + m * p.ldadd + n) : ld4((const bf16*)p.addend + m * p.ldadd + n);
-  if (p.epi & GSTVD_EPI_GELU) {
-    f32x4 d;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { float g_, d_; gelu_both<true>(v[e], g_, d_); v[e] = g_; d[e] = d_; }
-    if (p.aux) st4((bf16*)p.aux + m * p.ldaux + n, d);
-  }
-  if (F32OUT) st4((float*)p.C + m * p.ldc + n, v);
-  else st4((bf16*)p.C + m * p.ldc + n, v);
+  gemv16_tail<NW, F32OUT>(p, acc, red, n0, wave, lane, g, li);
 }
 
 // The same product with a LayerNorm folded into the A operand: C = epi(LN(A; gamma, beta, eps) . B^T), K <= 1024 (a whole row of
@@ -129,25 +136,7 @@ __global__ __launch_bounds__(256) void gemv16_ln_kernel(GemmP p, LnIn ln) {
   }
 #pragma unroll
   for (int u = 0; u < UNR; ++u) acc = mfma_bf16_k32(fb[u], fa[u], acc);
-  red[wave][lane] = acc;
-  __syncthreads();
-  if (wave != 0) return;
-#pragma unroll
-  for (int w = 1; w < NW; ++w) acc += red[w][lane];
-  const int64_t m = li, n = n0 + 4 * g;
-  if (m >= p.M || n >= p.N) return;
-  f32x4 v = acc * p.alpha;
-  if (p.epi & GSTVD_EPI_BIAS) v += *(const f32x4*)(p.bias + n);
-  if (p.epi & GSTVD_EPI_ADD)        // the addend has the OUTPUT's type, as in the tiled kernels' epilogue (gemm_epilogue_tile)
-    v += F32OUT ? ld4((const float*)p.addend + m * p.ldadd + n) : ld4((const bf16*)p.addend + m * p.ldadd + n);
-  if (p.epi & GSTVD_EPI_GELU) {
-    f32x4 d;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { float g_, d_; gelu_both<true>(v[e], g_, d_); v[e] = g_; d[e] = d_; }
-    if (p.aux) st4((bf16*)p.aux + m * p.ldaux + n, d);
-  }
-  if (F32OUT) st4((float*)p.C + m * p.ldc + n, v);
-  else st4((bf16*)p.C + m * p.ldc + n, v);
+  gemv16_tail<NW, F32OUT>(p, acc, red, n0, wave, lane, g, li);
 }
 
 int gemv16_ln_dispatch(const GemmP& p, int64_t batch, int akm, int bkm, int out_f32, const float* gamma, const float* beta, float eps,

@@ -3,16 +3,11 @@
 // vector accesses, row statistics by wave shuffles, dropout masks regenerated from the counter hash.
 // Reference arithmetic: models/vilbert_dialog.py:283-296 (TF-style LN), :324-352 (BertEmbeddingsDialog),
 // :1420-1427 (BertImageEmbeddings), :416-420 / :458-462 / :735-742 (dense -> dropout -> LN(x + residual)).
+// The row arithmetic itself is in ln_row.h, shared with the fused prologues of gemm_rows.hip.
 #include <stdio.h>
+#include <type_traits>
 
-#include "common.h"
-
-struct LnP {
-  gstvd_ln_t f;
-  // backward extras
-  const void* dy; int64_t lddy; void* dres; int64_t lddres; void* dx; int64_t lddx; float* partial;
-  float *dword, *dpos, *dtt, *dtt_ext;
-};
+#include "ln_row.h"
 
 // rows per wave in backward: 2 (both rows' loads in flight before any reduction) for large M; 1 for small M, where the
 // grid cannot fill the chip anyway and the shorter per-wave chain is what counts (decoder / vision rows)
@@ -30,8 +25,7 @@ DEVFN f32x4 ln_prologue(const gstvd_ln_t& f, int64_t row, int c, const DropKey& 
   f32x4 h;
   if (MODE == GSTVD_LN_RESID) {
     h = ld4((const T*)f.x + row * f.ldx + c);
-    h *= drop_factor4(dpre, (uint64_t)(row * f.H + c));
-    if (f.res) h += ld4((const T*)f.res + row * f.ldres + c);
+    ln_resid(h, ln_drop(dpre, row, f.H, c), f.res != nullptr, [&] { return ld4((const T*)f.res + row * f.ldres + c); });
   } else if (MODE == GSTVD_LN_EMBED) {
     h = *(const f32x4*)(f.word + id * f.H + c) + *(const f32x4*)(f.pos + tpos * f.H + c);
     const float* trow = (seg < f.type_vocab) ? f.tt + seg * f.H : f.tt_ext + (seg - f.type_vocab) * f.H;
@@ -71,35 +65,39 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(gstvd_ln_t f) {
   float s = 0.f;
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
-    const int c = lane * 4 + i * 256;
+    const auto [c, in] = ln_col(lane, i, H);
     h[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    if (c < H) {
+    if (in) {
       h[i] = ln_prologue<T, MODE>(f, row, c, dpre, id, tpos, seg, locrow);
-      s += h[i][0] + h[i][1] + h[i][2] + h[i][3];
+      s += ln_sum4(h[i]);
     }
   }
-  const float mean = wave_sum(s) / (float)H;
+  const float mean = ln_row_mean(s, H);
   float v = 0.f;
 #pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    const int c = lane * 4 + i * 256;
-    if (c < H) {
-      f32x4 d = h[i] - mean;
-      v += d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + d[3] * d[3];
-    }
-  }
-  const float var = wave_sum(v) / (float)H;
-  const float rstd = 1.0f / sqrtf(var + f.eps);
+  for (int i = 0; i < NV; ++i)
+    if (ln_col(lane, i, H).in) v += ln_var_term(h[i], mean, NV == 1);
+  const float rstd = ln_rstd(v, H, f.eps);
   if (lane == 0) { f.mean[row] = mean; f.rstd[row] = rstd; }
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
-    const int c = lane * 4 + i * 256;
-    if (c < H) {
-      f32x4 y = *(const f32x4*)(f.gamma + c) * ((h[i] - mean) * rstd) + *(const f32x4*)(f.beta + c);
-      y *= drop_factor4(dpost, (uint64_t)(row * f.H + c));
+    const auto [c, in] = ln_col(lane, i, H);
+    if (in) {
+      f32x4 y = ln_y(h[i], mean, rstd, *(const f32x4*)(f.gamma + c), *(const f32x4*)(f.beta + c));
+      y *= ln_drop(dpost, row, f.H, c);
       st4((T*)f.y + row * f.ldy + c, y);
     }
   }
+}
+
+// LDS of the backward in vectors of H floats per wave, read by the kernel's carve-up and by the launcher's size alike.  NVP: the
+// column partials that go to HBM; embedding mode with H <= 1024 (EXT) adds the block's position row (NVL = 5) and, behind all
+// waves' slabs, one word strip per wave.
+constexpr bool ln_bwd_ext(int mode, int nv) { return mode == GSTVD_LN_EMBED && nv <= 4; }
+constexpr int ln_bwd_nvp(int mode) { return mode == GSTVD_LN_EMBED ? 4 : 3; }
+constexpr int ln_bwd_nvl(int mode, int nv) { return ln_bwd_ext(mode, nv) ? 5 : ln_bwd_nvp(mode); }
+constexpr int ln_bwd_lds(int mode, int nv, int nw, int64_t H) {
+  return (int)(nw * (ln_bwd_nvl(mode, nv) + (ln_bwd_ext(mode, nv) ? 1 : 0)) * H * sizeof(float));
 }
 
 // Backward: a block owns 4*RW consecutive rows, each wave RW of them (RW = 1 up to 8192 rows: measured 17.1 -> 13.0 us
@@ -107,18 +105,17 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(gstvd_ln_t f) {
 // before any reduction (memory-level parallelism), column partial sums stay in registers and are combined
 // across the 4 waves through LDS with plain stores (no LDS atomics), one [3][H] slab per block goes to HBM.
 template <typename T, int MODE, int NV, int RW, int NW = 4>
-__global__ __launch_bounds__(NW * 64) void ln_bwd_kernel(LnP p) {
+__global__ __launch_bounds__(NW * 64) void ln_bwd_kernel(gstvd_ln_bwd_t p) {
   constexpr int LN_BWD_RPB = NW * RW;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* red = (float*)smem;                   // [NW waves][3][H]
+  float* red = (float*)smem;                   // [NW waves][NVL][H], then (EXT) [NW waves][H] word strips
   const gstvd_ln_t& f = p.f;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int H = (int)f.H;
   const DropKey dpre = make_drop(MODE == GSTVD_LN_RESID ? f.p_pre : 0.f, f.site_pre, f.rng);
   const DropKey dpost = make_drop(f.p_post, f.site_post, f.rng);
-  constexpr int NVP = (MODE == GSTVD_LN_EMBED) ? 4 : 3;      // partial vectors per block that go to HBM
-  constexpr bool EXT = MODE == GSTVD_LN_EMBED && NV <= 4;    // embedding mode, H <= 1024: position slab + word strip fit the LDS
-  constexpr int NVL = EXT ? 5 : NVP;                         // vectors per wave that go through LDS (+ the block's position row)
+  constexpr int NVP = ln_bwd_nvp(MODE), NVL = ln_bwd_nvl(MODE, NV);
+  constexpr bool EXT = ln_bwd_ext(MODE, NV);
   f32x4 ag[NV], ab[NV], ax[NV], a4[NV], ap[NV];
 #pragma unroll
   for (int i = 0; i < NV; ++i) ag[i] = ab[i] = ax[i] = a4[i] = ap[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -155,33 +152,30 @@ __global__ __launch_bounds__(NW * 64) void ln_bwd_kernel(LnP p) {
     }
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
-      const int c = lane * 4 + i * 256;
+      const auto [c, in] = ln_col(lane, i, H);
       xh[j][i] = gy[j][i] = dyv[j][i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-      if (rv[j] && c < H) {
-        f32x4 h = ln_prologue<T, MODE>(f, row, c, dpre, id[j], tpos[j], seg[j], locrow);
-        xh[j][i] = (h - mean) * rstd[j];
-        dyv[j][i] = ld4((const T*)p.dy + row * p.lddy + c) * drop_factor4(dpost, (uint64_t)(row * f.H + c));
-        gy[j][i] = dyv[j][i] * *(const f32x4*)(f.gamma + c);
-        s1[j] += gy[j][i][0] + gy[j][i][1] + gy[j][i][2] + gy[j][i][3];
-        f32x4 t = gy[j][i] * xh[j][i];
-        s2[j] += t[0] + t[1] + t[2] + t[3];
+      if (rv[j] && in) {
+        const f32x4 h = ln_prologue<T, MODE>(f, row, c, dpre, id[j], tpos[j], seg[j], locrow);
+        xh[j][i] = ln_xhat(h, mean, rstd[j]);
+        dyv[j][i] = ld4((const T*)p.dy + row * p.lddy + c) * ln_drop(dpost, row, f.H, c);
+        ln_bwd_sums(dyv[j][i], *(const f32x4*)(f.gamma + c), xh[j][i], gy[j][i], s1[j], s2[j]);
       }
     }
   }
 #pragma unroll
   for (int j = 0; j < RW; ++j) {
     const int64_t row = row0 + j * rstep;
-    const float c1 = wave_sum(s1[j]) / (float)H, c2 = wave_sum(s2[j]) / (float)H;
+    const float c1 = ln_row_mean(s1[j], H), c2 = ln_row_mean(s2[j], H);
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
-      const int c = lane * 4 + i * 256;
-      if (rv[j] && c < H) {
-        f32x4 dh = (gy[j][i] - c1 - xh[j][i] * c2) * rstd[j];
+      const auto [c, in] = ln_col(lane, i, H);
+      if (rv[j] && in) {
+        const f32x4 dh = ln_bwd_dh(gy[j][i], xh[j][i], c1, c2, rstd[j]);
         ag[i] += dyv[j][i] * xh[j][i];
         ab[i] += dyv[j][i];
         if (MODE == GSTVD_LN_RESID) {
           if (p.dres) st4((T*)p.dres + row * p.lddres + c, dh);
-          f32x4 dx = dh * drop_factor4(dpre, (uint64_t)(row * f.H + c));
+          const f32x4 dx = dh * ln_drop(dpre, row, f.H, c);
           if (p.dx && (p.dx != p.dres || dpre.on)) st4((T*)p.dx + row * p.lddx + c, dx);
           ax[i] += dx;
         } else if (MODE == GSTVD_LN_IMAGE) {
@@ -230,8 +224,8 @@ __global__ __launch_bounds__(NW * 64) void ln_bwd_kernel(LnP p) {
   float* mine = red + (int64_t)wave * NVL * H;
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
-    const int c = lane * 4 + i * 256;
-    if (c < H) {
+    const auto [c, in] = ln_col(lane, i, H);
+    if (in) {
       *(f32x4*)(mine + c) = ag[i];
       *(f32x4*)(mine + H + c) = ab[i];
       *(f32x4*)(mine + 2 * H + c) = ax[i];
@@ -260,121 +254,20 @@ __global__ __launch_bounds__(NW * 64) void ln_bwd_kernel(LnP p) {
   }
 }
 
-// out_j[c] (+)= sum_b partial[b][j][c]; block = 64 columns x 4 row groups
-__global__ __launch_bounds__(256) void colsum_partials_kernel(const float* partial, int64_t nblk, int64_t nvec, int64_t H,
-                                                              float* o0, float* o1, float* o2, int accumulate) {
-  __shared__ float red[4][64];
-  const int cl = threadIdx.x & 63, rg = threadIdx.x >> 6;
-  const int64_t col = (int64_t)blockIdx.x * 64 + cl;      // over nvec*H
-  const int64_t W = nvec * H;
-  float a = 0.f;
-  if (col < W) {
-    const int64_t j = col / H, c = col % H;
-    const float* src = partial + j * H + c;
-    for (int64_t b = rg; b < nblk; b += 4) a += src[b * 3 * H];
-  }
-  red[rg][cl] = a;
-  __syncthreads();
-  if (rg == 0 && col < W) {
-    a = red[0][cl] + red[1][cl] + red[2][cl] + red[3][cl];
-    const int64_t j = col / H, c = col % H;
-    float* o = j == 0 ? o0 : (j == 1 ? o1 : o2);
-    if (o) o[c] = accumulate ? o[c] + a : a;
-  }
-}
-
-// stage 1 of a plain column sum: block = 64-row slab x 256 columns -> partial[slab][N] (stride 3*N like LN partials? no: N)
-template <typename T>
-__global__ __launch_bounds__(256) void colsum_slab_kernel(const T* x, int64_t ldx, int64_t M, int64_t N, float* partial) {
-  __shared__ f32x4 red[4][64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int64_t c = (int64_t)blockIdx.x * 256 + lane * 4;
-  const int64_t r0 = (int64_t)blockIdx.y * 64;
-  f32x4 a = {0.f, 0.f, 0.f, 0.f};
-  if (c < N) {
-#pragma unroll 4
-    for (int i = 0; i < 16; ++i) {
-      int64_t r = r0 + wave + 4 * i;
-      if (r < M) a += ld4(x + r * ldx + c);
-    }
-  }
-  red[wave][lane] = a;
-  __syncthreads();
-  if (wave == 0 && c < N) {
-    a = red[0][lane] + red[1][lane] + red[2][lane] + red[3][lane];
-    *(f32x4*)(partial + (int64_t)blockIdx.y * N + c) = a;
-  }
-}
-// table-driven form of the slab stage: every pending bias-gradient column sum of a backward pass in one launch
-template <typename T>
-__global__ __launch_bounds__(256) void colsum_slab_batched_kernel(const gstvd_slab_entry_t* tab, int nent) {
-  __shared__ f32x4 red[4][64];
+// ---- column reductions -------------------------------------------------------------------------------
+// the table entry that owns block b: the last one whose first block blk0 is <= b
+template <typename E> DEVFN int table_entry(const E* tab, int nent, int b) {
   int lo = 0, hi = nent - 1;
-  const int b = blockIdx.x;
   while (lo < hi) { int mid = (lo + hi + 1) >> 1; if (tab[mid].blk0 <= b) lo = mid; else hi = mid - 1; }
-  const gstvd_slab_entry_t e = tab[lo];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int ncb = (int)((e.N + 255) / 256), local = b - e.blk0;
-  const int64_t c = (int64_t)(local % ncb) * 256 + lane * 4, slab = local / ncb, r0 = slab * 64;
-  const T* x = (const T*)e.x;
-  f32x4 a = {0.f, 0.f, 0.f, 0.f};
-  if (c < e.N) {
-#pragma unroll 4
-    for (int i = 0; i < 16; ++i) {
-      int64_t r = r0 + wave + 4 * i;
-      if (r < e.M) a += ld4(x + r * e.ldx + c);
-    }
-  }
-  red[wave][lane] = a;
-  __syncthreads();
-  if (wave == 0 && c < e.N) {
-    a = red[0][lane] + red[1][lane] + red[2][lane] + red[3][lane];
-    *(f32x4*)(e.scratch + slab * e.N + c) = a;
-  }
+  return lo;
 }
 
-// stage 2: out[c] (+)= sum_s partial[s][c]
-__global__ __launch_bounds__(256) void colsum_final_kernel(const float* partial, int64_t nslab, int64_t N, float* out, int accumulate) {
+// out_j[c] (+)= sum_k partial[k * stride + j * H + c] for the 64-column slice `local` of the entry's nvec * H wide row;
+// block = 64 columns x 4 row groups
+DEVFN void colsum_entry(const gstvd_colsum_entry_t e, int local) {
   __shared__ float red[4][64];
   const int cl = threadIdx.x & 63, rg = threadIdx.x >> 6;
-  const int64_t c = (int64_t)blockIdx.x * 64 + cl;
-  float a = 0.f;
-  if (c < N) for (int64_t s = rg; s < nslab; s += 4) a += partial[s * N + c];
-  red[rg][cl] = a;
-  __syncthreads();
-  if (rg == 0 && c < N) {
-    a = red[0][cl] + red[1][cl] + red[2][cl] + red[3][cl];
-    out[c] = accumulate ? out[c] + a : a;
-  }
-}
-
-// dW_loc[h][j] += sum_m dh[m][h] loc[m][j]; grid (ceil(H/256), MS) with atomics
-template <typename T>
-__global__ __launch_bounds__(256) void locgrad_kernel(const T* dh, int64_t lddh, const float* loc, int64_t M, int64_t H, float* dw) {
-  const int64_t h = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (h >= H) return;
-  const int64_t per = (M + gridDim.y - 1) / gridDim.y;
-  const int64_t m0 = blockIdx.y * per, m1 = (m0 + per < M) ? m0 + per : M;
-  float a[5] = {0, 0, 0, 0, 0};
-  for (int64_t m = m0; m < m1; ++m) {
-    const float d = to_f(dh[m * lddh + h]);
-#pragma unroll
-    for (int j = 0; j < 5; ++j) a[j] += d * loc[m * 5 + j];
-  }
-#pragma unroll
-  for (int j = 0; j < 5; ++j) atomicAdd(dw + h * 5 + j, a[j]);
-}
-
-// All pending column reductions of a backward pass in ONE launch: block b serves the 64-column slice
-// (b - blk0) of the entry that contains it (binary search over the entries' first-block offsets).
-__global__ __launch_bounds__(256) void colsum_batched_kernel(const gstvd_colsum_entry_t* tab, int nent) {
-  __shared__ float red[4][64];
-  int lo = 0, hi = nent - 1;
-  const int b = blockIdx.x;
-  while (lo < hi) { int mid = (lo + hi + 1) >> 1; if (tab[mid].blk0 <= b) lo = mid; else hi = mid - 1; }
-  const gstvd_colsum_entry_t e = tab[lo];
-  const int cl = threadIdx.x & 63, rg = threadIdx.x >> 6;
-  const int64_t col = (int64_t)(b - e.blk0) * 64 + cl, W = (int64_t)e.nvec * e.H;
+  const int64_t col = (int64_t)local * 64 + cl, W = (int64_t)e.nvec * e.H;
   float a = 0.f;
   if (col < W) {
     // eight independent loads in flight per thread: the embedding LayerNorm's 1024 partial rows used to be 256 dependent
@@ -399,6 +292,64 @@ __global__ __launch_bounds__(256) void colsum_batched_kernel(const gstvd_colsum_
     const int acc = j == 0 ? e.accumulate[0] : (j == 1 ? e.accumulate[1] : e.accumulate[2]);
     if (o) o[c] = acc ? o[c] + a : a;
   }
+}
+// one entry as the kernel's argument (gstvd_colsum_partials, stage 2 of gstvd_colsum): block b = slice b
+__global__ __launch_bounds__(256) void colsum_entry_kernel(gstvd_colsum_entry_t e) { colsum_entry(e, blockIdx.x); }
+// All pending column reductions of a backward pass in ONE launch: block b serves the 64-column slice
+// (b - blk0) of the entry that contains it (binary search over the entries' first-block offsets).
+__global__ __launch_bounds__(256) void colsum_batched_kernel(const gstvd_colsum_entry_t* tab, int nent) {
+  const gstvd_colsum_entry_t e = tab[table_entry(tab, nent, blockIdx.x)];
+  colsum_entry(e, blockIdx.x - e.blk0);
+}
+
+// stage 1 of a plain column sum: block = 64-row slab x 256 columns (column block cb) -> scratch[slab][N]
+template <typename T>
+DEVFN void colsum_slab(const T* x, int64_t ldx, int64_t M, int64_t N, float* scratch, int cb, int64_t slab) {
+  __shared__ f32x4 red[4][64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t c = (int64_t)cb * 256 + lane * 4, r0 = slab * 64;
+  f32x4 a = {0.f, 0.f, 0.f, 0.f};
+  if (c < N) {
+#pragma unroll 4
+    for (int i = 0; i < 16; ++i) {
+      int64_t r = r0 + wave + 4 * i;
+      if (r < M) a += ld4(x + r * ldx + c);
+    }
+  }
+  red[wave][lane] = a;
+  __syncthreads();
+  if (wave == 0 && c < N) {
+    a = red[0][lane] + red[1][lane] + red[2][lane] + red[3][lane];
+    *(f32x4*)(scratch + slab * N + c) = a;
+  }
+}
+template <typename T>
+__global__ __launch_bounds__(256) void colsum_slab_kernel(const T* x, int64_t ldx, int64_t M, int64_t N, float* scratch) {
+  colsum_slab(x, ldx, M, N, scratch, blockIdx.x, blockIdx.y);
+}
+// table-driven form of the slab stage: every pending bias-gradient column sum of a backward pass in one launch
+template <typename T>
+__global__ __launch_bounds__(256) void colsum_slab_batched_kernel(const gstvd_slab_entry_t* tab, int nent) {
+  const gstvd_slab_entry_t e = tab[table_entry(tab, nent, blockIdx.x)];
+  const int ncb = (int)((e.N + 255) / 256), local = blockIdx.x - e.blk0;
+  colsum_slab((const T*)e.x, e.ldx, e.M, e.N, e.scratch, local % ncb, local / ncb);
+}
+
+// dW_loc[h][j] += sum_m dh[m][h] loc[m][j]; grid (ceil(H/256), MS) with atomics
+template <typename T>
+__global__ __launch_bounds__(256) void locgrad_kernel(const T* dh, int64_t lddh, const float* loc, int64_t M, int64_t H, float* dw) {
+  const int64_t h = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (h >= H) return;
+  const int64_t per = (M + gridDim.y - 1) / gridDim.y;
+  const int64_t m0 = blockIdx.y * per, m1 = (m0 + per < M) ? m0 + per : M;
+  float a[5] = {0, 0, 0, 0, 0};
+  for (int64_t m = m0; m < m1; ++m) {
+    const float d = to_f(dh[m * lddh + h]);
+#pragma unroll
+    for (int j = 0; j < 5; ++j) a[j] += d * loc[m * 5 + j];
+  }
+#pragma unroll
+  for (int j = 0; j < 5; ++j) atomicAdd(dw + h * 5 + j, a[j]);
 }
 
 // ---- host side -------------------------------------------------------------------------------------
@@ -440,6 +391,25 @@ static int ln_bwd_route(const gstvd_ln_bwd_t& b, LnRoute* r) {
   return 0;
 }
 
+// The route's type, mode and NV as template arguments: go(T{}, mode, nv) with T the element type and two std::integral_constant
+// -- the one ladder of each kind, for forward and backward alike.
+template <typename F> static int by_ln_mode(int mode, F f) {
+  if (mode == GSTVD_LN_RESID) return f(std::integral_constant<int, GSTVD_LN_RESID>{});
+  if (mode == GSTVD_LN_EMBED) return f(std::integral_constant<int, GSTVD_LN_EMBED>{});
+  return f(std::integral_constant<int, GSTVD_LN_IMAGE>{});
+}
+template <typename F> static int by_ln_nv(int nv, F f) {
+  if (nv == 1) return f(std::integral_constant<int, 1>{});
+  if (nv == 3) return f(std::integral_constant<int, 3>{});
+  if (nv == 4) return f(std::integral_constant<int, 4>{});
+  return f(std::integral_constant<int, 8>{});
+}
+template <typename F> static int by_ln_route(const LnRoute& r, F go) {
+  return by_ln_mode(r.mode, [&](auto mode) {
+    return by_ln_nv(r.nv, [&](auto nv) { return r.bf ? go(bf16{}, mode, nv) : go(float{}, mode, nv); });
+  });
+}
+
 // plan-only mode (gstvd_ln_kernel_name): the launch site records the kernel handle it WOULD have launched and launches nothing
 template <typename T, int MODE, int NV>
 static int ln_fwd_go(const gstvd_ln_t& f, const LnRoute& r, hipStream_t s, const void** plan) {
@@ -448,46 +418,27 @@ static int ln_fwd_go(const gstvd_ln_t& f, const LnRoute& r, hipStream_t s, const
   GSTVD_LAUNCH_CHECK();
   return 0;
 }
-template <typename T, int MODE>
-static int ln_fwd_nv(const gstvd_ln_t& f, const LnRoute& r, hipStream_t s, const void** plan) {
-  if (r.nv == 1) return ln_fwd_go<T, MODE, 1>(f, r, s, plan);
-  if (r.nv == 3) return ln_fwd_go<T, MODE, 3>(f, r, s, plan);
-  if (r.nv == 4) return ln_fwd_go<T, MODE, 4>(f, r, s, plan);
-  return ln_fwd_go<T, MODE, 8>(f, r, s, plan);
-}
-template <typename T>
-static int ln_fwd_mode(const gstvd_ln_t& f, const LnRoute& r, hipStream_t s, const void** plan) {
-  if (r.mode == GSTVD_LN_RESID) return ln_fwd_nv<T, GSTVD_LN_RESID>(f, r, s, plan);
-  if (r.mode == GSTVD_LN_EMBED) return ln_fwd_nv<T, GSTVD_LN_EMBED>(f, r, s, plan);
-  return ln_fwd_nv<T, GSTVD_LN_IMAGE>(f, r, s, plan);
-}
 static int ln_fwd_entry(const gstvd_ln_t* p, hipStream_t s, const void** plan) {
   int rc = ln_check(p);
   if (rc) return rc;
   if (!p->y) return GSTVD_E_NULL;
   const LnRoute r = ln_fwd_route(*p);
-  return r.bf ? ln_fwd_mode<bf16>(*p, r, s, plan) : ln_fwd_mode<float>(*p, r, s, plan);
+  return by_ln_route(r, [&](auto t, auto mode, auto nv) { return ln_fwd_go<decltype(t), mode.value, nv.value>(*p, r, s, plan); });
 }
 extern "C" int gstvd_ln_fwd(const gstvd_ln_t* p, gstvd_stream_t stream) { return ln_fwd_entry(p, (hipStream_t)stream, nullptr); }
 
 template <typename T, int MODE, int NV, int RW, int NW>
-static int ln_bwd_go(const LnP& p, const LnRoute& r, hipStream_t s, const void** plan) {
-  if (plan) { *plan = (const void*)ln_bwd_kernel<T, MODE, NV, RW, NW>; return 0; }
-  // per wave: 3 slabs; embedding mode 4, or (H <= 1024) 5 slabs + the word strip
-  constexpr int NVL = MODE == GSTVD_LN_EMBED ? (NV <= 4 ? 6 : 4) : 3;
-  constexpr int HMAX = NV == 1 ? 256 : (NV == 3 ? 768 : (NV == 4 ? 1024 : 2048));
-  const size_t lds = (size_t)NW * NVL * p.f.H * sizeof(float);
-  if (lds > 48 * 1024) {
-    static int rc = (int)hipFuncSetAttribute((const void*)ln_bwd_kernel<T, MODE, NV, RW, NW>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             NW * NVL * HMAX * 4);
-    if (rc) return rc;
-  }
-  hipLaunchKernelGGL((ln_bwd_kernel<T, MODE, NV, RW, NW>), dim3((unsigned)r.nblk), dim3(NW * 64), lds, s, p);
+static int ln_bwd_go(const gstvd_ln_bwd_t& p, const LnRoute& r, hipStream_t s, const void** plan) {
+  auto k = ln_bwd_kernel<T, MODE, NV, RW, NW>;
+  if (plan) { *plan = (const void*)k; return 0; }
+  static int attr_rc = ensure_lds(k, ln_bwd_lds(MODE, NV, NW, NV * 256));      // once, for this instantiation's widest row
+  if (attr_rc) return attr_rc;
+  hipLaunchKernelGGL(k, dim3((unsigned)r.nblk), dim3(NW * 64), ln_bwd_lds(MODE, NV, NW, p.f.H), s, p);
   GSTVD_LAUNCH_CHECK();
   return 0;
 }
 template <typename T, int MODE, int NV>
-static int ln_bwd_geo(const LnP& p, const LnRoute& r, hipStream_t s, const void** plan) {
+static int ln_bwd_geo(const gstvd_ln_bwd_t& p, const LnRoute& r, hipStream_t s, const void** plan) {
   // the 16-wave block exists for one-row waves, H <= 768, outside embedding mode: what ln_bwd_nw / gstvd_ln_bwd_blocks_for name;
   // should the two ever drift apart, the launch fails here instead of taking another kernel than the one reported
   if constexpr (MODE != GSTVD_LN_EMBED && NV <= 3) {
@@ -495,19 +446,6 @@ static int ln_bwd_geo(const LnP& p, const LnRoute& r, hipStream_t s, const void*
   }
   if (r.nw != 4) return GSTVD_E_UNSUPPORTED;
   return r.rw == 1 ? ln_bwd_go<T, MODE, NV, 1, 4>(p, r, s, plan) : ln_bwd_go<T, MODE, NV, 2, 4>(p, r, s, plan);
-}
-template <typename T, int MODE>
-static int ln_bwd_nv(const LnP& p, const LnRoute& r, hipStream_t s, const void** plan) {
-  if (r.nv == 1) return ln_bwd_geo<T, MODE, 1>(p, r, s, plan);
-  if (r.nv == 3) return ln_bwd_geo<T, MODE, 3>(p, r, s, plan);
-  if (r.nv == 4) return ln_bwd_geo<T, MODE, 4>(p, r, s, plan);
-  return ln_bwd_geo<T, MODE, 8>(p, r, s, plan);
-}
-template <typename T>
-static int ln_bwd_mode(const LnP& p, const LnRoute& r, hipStream_t s, const void** plan) {
-  if (r.mode == GSTVD_LN_RESID) return ln_bwd_nv<T, GSTVD_LN_RESID>(p, r, s, plan);
-  if (r.mode == GSTVD_LN_EMBED) return ln_bwd_nv<T, GSTVD_LN_EMBED>(p, r, s, plan);
-  return ln_bwd_nv<T, GSTVD_LN_IMAGE>(p, r, s, plan);
 }
 static int ln_bwd_entry(const gstvd_ln_bwd_t* b, hipStream_t s, const void** plan) {
   if (!b) return GSTVD_E_NULL;
@@ -519,11 +457,7 @@ static int ln_bwd_entry(const gstvd_ln_bwd_t* b, hipStream_t s, const void** pla
   LnRoute r;
   rc = ln_bwd_route(*b, &r);
   if (rc) return rc;
-  LnP p;
-  p.f = b->f; p.dy = b->dy; p.lddy = b->lddy; p.dres = b->dres; p.lddres = b->lddres;
-  p.dx = b->dx; p.lddx = b->lddx; p.partial = b->partial;
-  p.dword = b->dword; p.dpos = b->dpos; p.dtt = b->dtt; p.dtt_ext = b->dtt_ext;
-  return r.bf ? ln_bwd_mode<bf16>(p, r, s, plan) : ln_bwd_mode<float>(p, r, s, plan);
+  return by_ln_route(r, [&](auto t, auto mode, auto nv) { return ln_bwd_geo<decltype(t), mode.value, nv.value>(*b, r, s, plan); });
 }
 extern "C" int gstvd_ln_bwd(const gstvd_ln_bwd_t* b, gstvd_stream_t stream) { return ln_bwd_entry(b, (hipStream_t)stream, nullptr); }
 
@@ -541,14 +475,18 @@ extern "C" int gstvd_ln_kernel_name(const void* desc, int32_t bwd, char* buf, in
   return n >= 0 && n < buf_len ? 0 : GSTVD_E_SHAPE;
 }
 
+// one column sum described by an entry: a block per 64 of its nvec * H output columns
+static int colsum_entry_launch(const gstvd_colsum_entry_t& e, hipStream_t s) {
+  hipLaunchKernelGGL(colsum_entry_kernel, dim3((unsigned)((e.nvec * e.H + 63) / 64)), dim3(256), 0, s, e);
+  GSTVD_LAUNCH_CHECK();
+  return 0;
+}
 extern "C" int gstvd_colsum_partials(const float* partial, int64_t nblk, int64_t nvec, int64_t H,
                                      float* out0, float* out1, float* out2, int32_t accumulate, gstvd_stream_t stream) {
   if (!partial) return GSTVD_E_NULL;
   if (nblk <= 0 || nvec <= 0 || nvec > 3 || H <= 0) return GSTVD_E_SHAPE;
-  dim3 grid((unsigned)((nvec * H + 63) / 64));
-  hipLaunchKernelGGL(colsum_partials_kernel, grid, dim3(256), 0, (hipStream_t)stream, partial, nblk, nvec, H, out0, out1, out2, accumulate);
-  GSTVD_LAUNCH_CHECK();
-  return 0;
+  return colsum_entry_launch({partial, {out0, out1, out2}, nblk, 3 * H, H, (int32_t)nvec, {accumulate, accumulate, accumulate}, 0},
+                             (hipStream_t)stream);
 }
 
 extern "C" int gstvd_colsum_batched(const gstvd_colsum_entry_t* table_dev, int64_t nent, int64_t total_blocks, gstvd_stream_t stream) {
@@ -559,49 +497,40 @@ extern "C" int gstvd_colsum_batched(const gstvd_colsum_entry_t* table_dev, int64
   return 0;
 }
 
-// stage 1 only of a plain column sum: scratch[slab][N] (slab = 64 rows); finish with gstvd_colsum_batched / _partials
-extern "C" int gstvd_colsum_slabs(const void* x, int64_t ldx, int64_t M, int64_t N, int32_t dtype, float* scratch,
-                                  int64_t scratch_elems, gstvd_stream_t stream) {
+// the slab stage of a plain column sum: scratch[slab][N] (slab = 64 rows)
+static int colsum_slabs_launch(const void* x, int64_t ldx, int64_t M, int64_t N, int32_t dtype, float* scratch, int64_t scratch_elems,
+                               hipStream_t s) {
   if (!x || !scratch) return GSTVD_E_NULL;
   if (M <= 0 || N <= 0 || (N % 4)) return GSTVD_E_SHAPE;
   const int64_t nslab = (M + 63) / 64;
   if (scratch_elems < nslab * N) return GSTVD_E_SHAPE;
-  hipStream_t s = (hipStream_t)stream;
   dim3 grid((unsigned)((N + 255) / 256), (unsigned)nslab);
-  if (dtype == GSTVD_BF16) hipLaunchKernelGGL(colsum_slab_kernel<bf16>, grid, dim3(256), 0, s, (const bf16*)x, ldx, M, N, scratch);
-  else if (dtype == GSTVD_F32) hipLaunchKernelGGL(colsum_slab_kernel<float>, grid, dim3(256), 0, s, (const float*)x, ldx, M, N, scratch);
-  else return GSTVD_E_DTYPE;
+  GSTVD_FOR_DTYPE(dtype, T, hipLaunchKernelGGL(colsum_slab_kernel<T>, grid, dim3(256), 0, s, (const T*)x, ldx, M, N, scratch));
   GSTVD_LAUNCH_CHECK();
   return 0;
+}
+// stage 1 only; finish with gstvd_colsum_batched / _partials
+extern "C" int gstvd_colsum_slabs(const void* x, int64_t ldx, int64_t M, int64_t N, int32_t dtype, float* scratch,
+                                  int64_t scratch_elems, gstvd_stream_t stream) {
+  return colsum_slabs_launch(x, ldx, M, N, dtype, scratch, scratch_elems, (hipStream_t)stream);
 }
 
 extern "C" int gstvd_colsum_slabs_batched(const gstvd_slab_entry_t* table_dev, int64_t nent, int64_t total_blocks, int32_t dtype,
                                           gstvd_stream_t stream) {
   if (!table_dev) return GSTVD_E_NULL;
   if (nent <= 0 || total_blocks <= 0) return GSTVD_E_SHAPE;
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == GSTVD_BF16) hipLaunchKernelGGL(colsum_slab_batched_kernel<bf16>, dim3((unsigned)total_blocks), dim3(256), 0, s, table_dev, (int)nent);
-  else if (dtype == GSTVD_F32) hipLaunchKernelGGL(colsum_slab_batched_kernel<float>, dim3((unsigned)total_blocks), dim3(256), 0, s, table_dev, (int)nent);
-  else return GSTVD_E_DTYPE;
+  GSTVD_FOR_DTYPE(dtype, T, hipLaunchKernelGGL(colsum_slab_batched_kernel<T>, dim3((unsigned)total_blocks), dim3(256), 0, (hipStream_t)stream, table_dev, (int)nent));
   GSTVD_LAUNCH_CHECK();
   return 0;
 }
 
+// both stages: the slab stage, then out[c] (+)= sum_s scratch[s][c]
 extern "C" int gstvd_colsum(const void* x, int64_t ldx, int64_t M, int64_t N, int32_t dtype, float* out,
                             float* scratch, int64_t scratch_elems, int32_t accumulate, gstvd_stream_t stream) {
-  if (!x || !out || !scratch) return GSTVD_E_NULL;
-  if (M <= 0 || N <= 0 || (N % 4)) return GSTVD_E_SHAPE;
-  const int64_t nslab = (M + 63) / 64;
-  if (scratch_elems < nslab * N) return GSTVD_E_SHAPE;
-  hipStream_t s = (hipStream_t)stream;
-  dim3 grid((unsigned)((N + 255) / 256), (unsigned)nslab);
-  if (dtype == GSTVD_BF16) hipLaunchKernelGGL(colsum_slab_kernel<bf16>, grid, dim3(256), 0, s, (const bf16*)x, ldx, M, N, scratch);
-  else if (dtype == GSTVD_F32) hipLaunchKernelGGL(colsum_slab_kernel<float>, grid, dim3(256), 0, s, (const float*)x, ldx, M, N, scratch);
-  else return GSTVD_E_DTYPE;
-  GSTVD_LAUNCH_CHECK();
-  hipLaunchKernelGGL(colsum_final_kernel, dim3((unsigned)((N + 63) / 64)), dim3(256), 0, s, scratch, nslab, N, out, accumulate);
-  GSTVD_LAUNCH_CHECK();
-  return 0;
+  if (!out) return GSTVD_E_NULL;
+  const int rc = colsum_slabs_launch(x, ldx, M, N, dtype, scratch, scratch_elems, (hipStream_t)stream);
+  if (rc) return rc;
+  return colsum_entry_launch({scratch, {out, nullptr, nullptr}, (M + 63) / 64, N, N, 1, {accumulate, 0, 0}, 0}, (hipStream_t)stream);
 }
 
 extern "C" int gstvd_locgrad(const void* dh, int64_t lddh, const float* loc, int64_t M, int64_t H, int32_t dtype,
@@ -614,9 +543,7 @@ extern "C" int gstvd_locgrad(const void* dh, int64_t lddh, const float* loc, int
     if (e != hipSuccess) return (int)e;
   }
   dim3 grid((unsigned)((H + 255) / 256), 16);
-  if (dtype == GSTVD_BF16) hipLaunchKernelGGL(locgrad_kernel<bf16>, grid, dim3(256), 0, s, (const bf16*)dh, lddh, loc, M, H, dw_loc);
-  else if (dtype == GSTVD_F32) hipLaunchKernelGGL(locgrad_kernel<float>, grid, dim3(256), 0, s, (const float*)dh, lddh, loc, M, H, dw_loc);
-  else return GSTVD_E_DTYPE;
+  GSTVD_FOR_DTYPE(dtype, T, hipLaunchKernelGGL(locgrad_kernel<T>, grid, dim3(256), 0, s, (const T*)dh, lddh, loc, M, H, dw_loc));
   GSTVD_LAUNCH_CHECK();
   return 0;
 }

@@ -171,13 +171,13 @@ CASES = build_cases()
 # Kernel instantiations no case names, each with its reason.
 EXEMPT = {}        # (none: every instantiation is reachable below 8200 x 2048 elements)
 # The column reductions and locgrad: named by the check that launches them (tests/test_ln_exact_gpu.py, section "reductions").
-# For these nine kernels the census is a CLAIM read off ops.py -- colsum launches the slab and the final kernel, add_slabs the
-# batched slab kernel and colsum_batched -- not an assertion: they have no name function, so nothing verifies the launch.
+# For these eight kernels the census is a CLAIM read off ops.py -- colsum_partials and the final stage of colsum launch the one-entry
+# kernel, colsum the slab kernel in front of it, add_slabs the batched slab kernel and colsum_batched -- not an assertion: they have
+# no name function, so nothing verifies the launch.
 REDUCTIONS = {
-    "colsum_partials_kernel": "check_colsum_partials",
+    "colsum_entry_kernel": "check_colsum_partials, check_colsum (final stage)",
     "colsum_batched_kernel": "check_colsum_batch",
     "colsum_slab_kernelIf": "check_colsum f32", "colsum_slab_kernelIDF16b": "check_colsum bf16",
-    "colsum_final_kernel": "check_colsum",
     "colsum_slab_batched_kernelIf": "check_add_slabs f32", "colsum_slab_batched_kernelIDF16b": "check_add_slabs bf16",
     "locgrad_kernelIf": "check_locgrad f32", "locgrad_kernelIDF16b": "check_locgrad bf16",
 }

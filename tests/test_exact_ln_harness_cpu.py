@@ -293,11 +293,11 @@ def test_invariance_checks_accept_the_stand_in():
 
 
 def test_census_check_on_a_synthetic_symbol_list():
-    syms = sorted(set(["_Z13" + c.fwd_kernel + "v10gstvd_ln_t" for c in X.CASES] + ["_Z13" + c.bwd_kernel + "v3LnP" for c in X.CASES if c.bwd]))
+    syms = sorted(set(["_Z13" + c.fwd_kernel + "v10gstvd_ln_t" for c in X.CASES] + ["_Z13" + c.bwd_kernel + "v14gstvd_ln_bwd_t" for c in X.CASES if c.bwd]))
     red = ["_Z9" + r + "Ev" for r in X.REDUCTIONS]
     X.check_census(syms + red, out=lambda s: None)
     with pytest.raises(AssertionError, match="named by"):
-        X.check_census(syms + red + ["_Z13ln_bwd_kernelIfLi0ELi16ELi1ELi4EEv3LnP"], out=lambda s: None)
+        X.check_census(syms + red + ["_Z13ln_bwd_kernelIfLi0ELi16ELi1ELi4EEv14gstvd_ln_bwd_t"], out=lambda s: None)
     with pytest.raises(AssertionError, match="absent from the library"):
         X.check_census(syms[1:] + red, out=lambda s: None)
 

@@ -176,7 +176,8 @@ def test_dx_aliased_to_dres_at_p_zero(c):
 
 
 # ------------------------------------------------------------------------------------------ reductions
-@pytest.mark.parametrize("nblk", [1, 3, 4, 5])
+# (28 .. 61: the loop with eight loads in flight, entered from nblk = 29 on, its tail, and the last count without it)
+@pytest.mark.parametrize("nblk", [1, 3, 4, 5, 28, 29, 32, 33, 61])
 def test_colsum_partials(nblk):
     be = Gpu()
     for nvec in (1, 2, 3):
@@ -195,6 +196,15 @@ def test_colsum_and_colsum_slabs(dtype):
     for i, M in enumerate(X.COLSUM_M):
         for j, N in enumerate(X.COLSUM_N):
             X.check_colsum(be, dtype, M, N, (i + j) % 2 == 1, seed=i * 7 + j)
+
+
+@pytest.mark.parametrize("dtype", ["f32", "bf16"])
+def test_colsum_final_stage_with_32_and_33_slabs(dtype):
+    """The final stage of colsum runs the one-entry kernel: 32 / 33 slabs reach its loop with eight loads in flight and the tail."""
+    be = Gpu()
+    for i, nslab in enumerate((28, 29, 32, 33)):
+        X.check_colsum(be, dtype, 64 * nslab, 8, i % 2 == 1, seed=nslab)
+        X.check_colsum(be, dtype, 64 * nslab - 63, 8, i % 2 == 0, seed=nslab + 1)
 
 
 @pytest.mark.parametrize("dtype", ["f32", "bf16"])
