@@ -9,8 +9,7 @@
 // Phase A (one 1024-thread workgroup per beam row, the row in registers as in sample_topk_kernel): max, log-sum-exp, the row's
 // candidate scores, and its K best under (score, v) in K rounds of block arg-max -> workspace [B, K, K] of (score, v).
 // Phase B (one wave per dialog row): ranks the <= K * K candidates under the full rule; the lane of rank i < K writes new beam i.
-#include "common.h"
-#include <math.h>
+#include "select.h"
 
 namespace {
 
@@ -20,15 +19,12 @@ constexpr int KMAX = 8;
 
 struct Cand { float s; int32_t v; };                          // one workspace entry
 
-// (a, ia) stands in front of (b, ib): larger score, then smaller index (-inf == -inf falls through to the index)
-DEVFN bool before(float a, int ia, float b, int ib) { return a > b || (a == b && ia < ib); }
-
 template <typename T>
 __global__ __launch_bounds__(NT) void beam_topk_kernel(gstvd_beam_step_t a) {
   __shared__ float smf[NWV];
   __shared__ float smv[NWV];
   __shared__ int smi[NWV];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = blockIdx.x, V = a.V, K = a.K;
+  const int tid = threadIdx.x, r = blockIdx.x, V = a.V, K = a.K;
   Cand* ws = (Cand*)a.workspace + (int64_t)r * K;
   if (a.done_in[r] != 0) return;                              // phase B reads nothing of a done beam's workspace rows
   const float s_in = a.score_in[r];
@@ -45,57 +41,30 @@ __global__ __launch_bounds__(NT) void beam_topk_kernel(gstvd_beam_step_t a) {
     const int i = tid + j * NT;
     zr[j] = i < V ? to_f(row[i]) : -INFINITY;
   }
-  float m = -INFINITY;
-#pragma unroll
-  for (int j = 0; j < SEG; ++j) m = fmaxf(m, zr[j]);
-  m = block_reduce(m, smf, true);
-  float e = 0.f;
-#pragma unroll
-  for (int j = 0; j < SEG; ++j) e += (tid + j * NT < V) ? expf(zr[j] - m) : 0.f;
-  const float lse = logf(block_reduce(e, smf, false));
+  float m, lse;
+  sel_row_norm<NWV>(zr, V, smf, m, lse);
   // the candidates' scores, in the spec's own association: s + ((z - max) - lse)
 #pragma unroll
   for (int j = 0; j < SEG; ++j) zr[j] = (tid + j * NT < V) ? s_in + ((zr[j] - m) - lse) : -INFINITY;
 
-  // K rounds: the best (score, v) that stands strictly behind the previous round's winner.  Nothing is marked in the
-  // registers (a dynamic index into zr[] would send the row to scratch); past-the-end slots carry v >= V and never qualify.
-  float pv = INFINITY, mine_s = -INFINITY;
-  int pi = -1, mine_v = 0;
-  for (int round = 0; round < K; ++round) {                  // uniform: every thread holds the same (pv, pi)
-    float bv = -INFINITY;
-    int bi = 0x7fffffff;
+  // select.h's sel_topk_rounds, written out: through the function the bf16 kernel measured 40.6-40.7 us per step against 40.2 with
+  // the loop here (profiles/select_refactor_timing.txt).  Keep the two in step.  (V < K runs out of candidates: never with a real
+  // vocabulary.)
+  Sel prev{INFINITY, -1}, mine{-INFINITY, 0};
+  for (int round = 0; round < K; ++round) {
+    Sel b{-INFINITY, SEL_NONE};
 #pragma unroll
     for (int j = 0; j < SEG; ++j) {
       const int i = tid + j * NT;
-      const bool ok = i < V && before(pv, pi, zr[j], i) && before(zr[j], i, bv, bi);
-      bv = ok ? zr[j] : bv;
-      bi = ok ? i : bi;
+      const bool ok = i < V && sel_before(prev.v, prev.i, zr[j], i) && sel_before(zr[j], i, b.v, b.i);
+      b = Sel{ok ? zr[j] : b.v, ok ? i : b.i};
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ov = __shfl_xor(bv, o, 64);
-      const int oi = __shfl_xor(bi, o, 64);
-      const bool t = before(ov, oi, bv, bi);
-      bv = t ? ov : bv;
-      bi = t ? oi : bi;
-    }
-    __syncthreads();                                         // (the previous round's reads of smv / smi are over)
-    if (lane == 0) { smv[wave] = bv; smi[wave] = bi; }
-    __syncthreads();
-    bv = smv[0]; bi = smi[0];
-#pragma unroll
-    for (int w = 1; w < NWV; ++w) {
-      const float ov = smv[w];
-      const int oi = smi[w];
-      const bool t = before(ov, oi, bv, bi);
-      bv = t ? ov : bv;
-      bi = t ? oi : bi;
-    }
-    if (bi >= V) { bv = -INFINITY; bi = V - 1; }              // (V < K: nothing left; never with a real vocabulary)
-    if (tid == round) { mine_s = bv; mine_v = bi; }
-    pv = bv; pi = bi;
+    b = sel_block_best<NWV>(b, smv, smi);
+    if (b.i >= V) b = Sel{-INFINITY, V - 1};
+    if (tid == round) mine = b;
+    prev = b;
   }
-  if (tid < K) { Cand c; c.s = mine_s; c.v = mine_v; ws[tid] = c; }
+  if (tid < K) { Cand c; c.s = mine.v; c.v = mine.i; ws[tid] = c; }
 }
 
 // One wave per dialog row: lane j * K + i holds candidate i of beam j.

@@ -4,7 +4,7 @@
 // 4-element vector accesses, deterministic reductions, stats by loss_reduce.h's rule.
 #include "loss_reduce.h"
 #include "ce_row.h"
-#include <math.h>
+#include "select.h"
 
 namespace {
 
@@ -14,18 +14,14 @@ constexpr int KMAX = 16;
 constexpr int TNT = 1024, TNW = TNT / 64;
 constexpr int TVEC = 8;                                       // 4-vectors per thread: V <= 8 * 4 * 1024 (checked by the host entry)
 
-// (a, ia) stands in front of (b, ib): larger value, then smaller index (-inf == -inf falls through to the index)
-DEVFN bool before(float a, int ia, float b, int ib) { return a > b || (a == b && ia < ib); }
-
-// The row in registers as in beam.hip's phase A, read once in 4-vectors; K rounds of block arg-max, each behind the previous
-// round's winner.  Nothing is marked in the registers (a dynamic index into zr[] would send the row to scratch); slots at or past
-// V never qualify, whatever they hold.
+// The row in registers as in beam.hip's phase A, read once in 4-vectors (slot j = element (tid + (j >> 2) * TNT) * 4 + (j & 3)); its
+// K best by select.h's rounds.
 template <typename T>
 __global__ __launch_bounds__(TNT) void topk_logp_kernel(const T* logits, int64_t ldl, const float* lse, int V, int K, int64_t* ids,
                                                         float* logp) {
   __shared__ float smv[TNW];
   __shared__ int smi[TNW];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int64_t m = blockIdx.x;
   const T* x = logits + m * ldl;
   float zr[TVEC * 4];
@@ -44,49 +40,11 @@ __global__ __launch_bounds__(TNT) void topk_logp_kernel(const T* logits, int64_t
     for (int e = 0; e < 4; ++e) zr[j * 4 + e] = v[e];
   }
   const float l = lse[m];
-  float pv = INFINITY, mine_v = -INFINITY;
-  int pi = -1, mine_i = 0;
-  for (int round = 0; round < K; ++round) {                   // uniform: every thread holds the same (pv, pi)
-    float bv = -INFINITY;
-    int bi = 0x7fffffff;
-#pragma unroll
-    for (int j = 0; j < TVEC; ++j) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int i = (tid + j * TNT) * 4 + e;
-        const float z = zr[j * 4 + e];
-        const bool ok = i < V && before(pv, pi, z, i) && before(z, i, bv, bi);
-        bv = ok ? z : bv;
-        bi = ok ? i : bi;
-      }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ov = __shfl_xor(bv, o, 64);
-      const int oi = __shfl_xor(bi, o, 64);
-      const bool t = before(ov, oi, bv, bi);
-      bv = t ? ov : bv;
-      bi = t ? oi : bi;
-    }
-    __syncthreads();                                          // (the previous round's reads of smv / smi are over)
-    if (lane == 0) { smv[wave] = bv; smi[wave] = bi; }
-    __syncthreads();
-    bv = smv[0]; bi = smi[0];
-#pragma unroll
-    for (int w = 1; w < TNW; ++w) {
-      const float ov = smv[w];
-      const int oi = smi[w];
-      const bool t = before(ov, oi, bv, bi);
-      bv = t ? ov : bv;
-      bi = t ? oi : bi;
-    }
-    if (bi >= V) { bv = -INFINITY; bi = V - 1; }              // (only a row with NaNs runs out of candidates: K <= V is checked)
-    if (tid == round) { mine_v = bv; mine_i = bi; }
-    pv = bv; pi = bi;
-  }
+  // (only a row with NaNs runs out of candidates: K <= V is checked)
+  const Sel mine = sel_topk_rounds<TNW>(zr, [tid](int j) { return (tid + (j >> 2) * TNT) * 4 + (j & 3); }, V, K, smv, smi);
   if (tid < K) {
-    ids[m * K + tid] = (int64_t)mine_i;
-    logp[m * K + tid] = mine_v - l;
+    ids[m * K + tid] = (int64_t)mine.i;
+    logp[m * K + tid] = mine.v - l;
   }
 }
 

@@ -8,8 +8,7 @@
 // One workgroup per dialog row, the row's V scaled logits live in LDS (V = 30522: 119 KB of the CU's 160 KB).  It replaces
 // ~25 small library kernels per step (topk's multi-block radix passes, softmax, cumsum scans, compares, copies) by one launch,
 // and keeps library kernels with their own temporary storage / memset nodes out of the captured token graph.
-#include "common.h"
-#include <math.h>
+#include "select.h"
 
 namespace {
 
@@ -81,19 +80,10 @@ __global__ __launch_bounds__(NT) void sample_topk_kernel(gstvd_sample_t a, float
     zr[j] = i < V ? to_f(row[i]) : 0.f;
     bn[j] = (ban && i < V) ? ban[i] : (uint8_t)0;
   }
-  // the score's normaliser, over the raw row while it is still in the registers: max x and sum exp(x - max x) in fp32 with
-  // expf / logf (gstvd_beam_step's logp_j[v]); temperature, bans and the filters below play no part in it
+  // the score's normaliser, over the raw row while it is still in the registers: the one gstvd_beam_step's logp_j[v] uses
+  // (select.h); temperature, bans and the filters below play no part in it
   float xmax = 0.f, xlse = 0.f;
-  if constexpr (SCORED) {
-    float rm = -INFINITY;
-#pragma unroll
-    for (int j = 0; j < SEG; ++j) rm = (tid + j * NT < V) ? fmaxf(rm, zr[j]) : rm;
-    xmax = block_reduce(rm, smf, true);
-    float re = 0.f;
-#pragma unroll
-    for (int j = 0; j < SEG; ++j) re += (tid + j * NT < V) ? expf(zr[j] - xmax) : 0.f;
-    xlse = logf(block_reduce(re, smf, false));
-  }
+  if constexpr (SCORED) sel_row_norm<NWV>(zr, V, smf, xmax, xlse);
   float m = -INFINITY;
   int c = 0;
 #pragma unroll

@@ -13,19 +13,19 @@
 //                 partial list in the workspace and a second launch merges a row's partial lists.
 // A pair's D products are added in one fixed order in both (k = 16 s + 4 g + e: s ascending, then e, then g inside the MFMA), so
 // the two routes return the same bits.  No atomics; every output element is written once; the order (larger value first, then the
-// smaller index: vocab_argmax.hip's) is strict over distinct targets, so nothing depends on which workgroup finishes first.
+// smaller index: select.h's) is strict over distinct targets, so nothing depends on which workgroup finishes first.
 #include "gemm_common.h"
+#include "select.h"
 
 namespace {
 
-constexpr int NONE = 0x7fffffff;          // index of an unused slot while lists are built (stored as -1)
 constexpr int TJ = 4;                     // 16-target tiles per wave step
 constexpr int UB = 4;                     // 16-wide k steps per batch of loads
 constexpr int STEP = TJ * 16;             // targets per wave step
 constexpr int MAX_D = 512;                // a workgroup's source rows live in LDS: 32 x (D + 4) floats, 66 KB here (300 must fit: 40 KB)
 constexpr int MANY_MIN_ROWS = 64 * 256;   // from here on the 32-row workgroups alone fill the 256 CUs twice over
 
-struct Ent { float v; int i; };
+typedef Sel Ent;                          // i == SEL_NONE: an unused slot while lists are built (stored as -1)
 
 struct TopkP {
   const float* E; const int32_t* src; int64_t ld;
@@ -35,18 +35,16 @@ struct TopkP {
   Ent* ws; int32_t* idx; float* val;
 };
 
-DEVFN bool better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
-
 // Sorted insert of (v, t) into a list of K entries, all 64 lanes of the wave calling; lanes 0..15 hold one entry each.  Entries
 // better than the candidate form a prefix (the list is sorted), the rest moves down one slot, the last one falls out.
 DEVFN void list_insert(volatile float* lv, volatile int* lx, int K, float v, int t, int lane) {
   const int k = lane & 15;
   const bool in = lane < 16 && k < K;
   const float ov = in ? lv[k] : 0.f;
-  const int ox = in ? lx[k] : NONE;
+  const int ox = in ? lx[k] : SEL_NONE;
   const float pv = (in && k > 0) ? lv[k - 1] : 0.f;
-  const int px = (in && k > 0) ? lx[k - 1] : NONE;
-  const int pos = __popcll(__ballot(in && better(ov, ox, v, t)));
+  const int px = (in && k > 0) ? lx[k - 1] : SEL_NONE;
+  const int pos = __popcll(__ballot(in && sel_before(ov, ox, v, t)));
   if (in && k >= pos) {                   // (every read above is issued before any of these writes: LDS is in order per wave)
     lv[k] = k == pos ? v : pv;
     lx[k] = k == pos ? t : px;
@@ -76,7 +74,7 @@ __global__ __launch_bounds__(NW * 64) void cos_topk_kernel(TopkP p) {
     for (int k = lane * 4; k < S; k += 256)
       *(f32x4*)(As + r * S + k) = (s >= 0 && k < p.D) ? *(const f32x4*)(p.E + (int64_t)s * p.ld + k) : zero;
   }
-  for (int i = tid; i < NW * 16 * K; i += NW * 64) { lv[i] = -__builtin_inff(); lx[i] = NONE; }
+  for (int i = tid; i < NW * 16 * K; i += NW * 64) { lv[i] = -__builtin_inff(); lx[i] = SEL_NONE; }
   __syncthreads();                        // the last one: from here on the waves do not meet
 
   const int blk = wave % SB, sl = wave / SB;
@@ -86,7 +84,7 @@ __global__ __launch_bounds__(NW * 64) void cos_topk_kernel(TopkP p) {
   int sidx[4], ki[4];
   float kv[4];
 #pragma unroll
-  for (int e = 0; e < 4; ++e) { sidx[e] = srow[blk * 16 + 4 * g + e]; kv[e] = -__builtin_inff(); ki[e] = NONE; }
+  for (int e = 0; e < 4; ++e) { sidx[e] = srow[blk * 16 + 4 * g + e]; kv[e] = -__builtin_inff(); ki[e] = SEL_NONE; }
   const int sub = p.chunk / WPB;
   const int64_t tb = (int64_t)blockIdx.y * p.chunk + (int64_t)sl * sub;
   const int tbeg = (int)(tb < p.V ? tb : p.V), tend = (int)(tb + sub < p.V ? tb + sub : p.V);
@@ -120,7 +118,7 @@ __global__ __launch_bounds__(NW * 64) void cos_topk_kernel(TopkP p) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) {       // lane holds dot(source 4 g + e, target t0 + 16 j + li)
         const float v = acc[j][e];
-        pass[j][e] = sidx[e] >= 0 && t < tend && t != sidx[e] && v >= p.thr && better(v, t, kv[e], ki[e]);
+        pass[j][e] = sidx[e] >= 0 && t < tend && t != sidx[e] && v >= p.thr && sel_before(v, t, kv[e], ki[e]);
         any |= pass[j][e];
       }
     }
@@ -177,8 +175,8 @@ __global__ __launch_bounds__(NW * 64) void cos_topk_kernel(TopkP p) {
     const float v = wv[i];
     const int x = wx[i];
     if (p.P == 0) {
-      p.idx[(int64_t)gr * K + k] = x == NONE ? -1 : x;
-      p.val[(int64_t)gr * K + k] = x == NONE ? 0.f : v;
+      p.idx[(int64_t)gr * K + k] = x == SEL_NONE ? -1 : x;
+      p.val[(int64_t)gr * K + k] = x == SEL_NONE ? 0.f : v;
     } else {
       p.ws[((int64_t)gr * p.P + blockIdx.y * WPB + sl) * K + k] = Ent{v, x};
     }
@@ -194,30 +192,26 @@ __global__ __launch_bounds__(64) void cos_topk_merge_kernel(const Ent* __restric
   float lastv = __builtin_inff();
   int lasti = -1;
   for (int k = 0; k < K; ++k) {
-    float bv = -__builtin_inff();
-    int bi = NONE;
+    Sel b{-__builtin_inff(), SEL_NONE};
     for (int l = lane; l < P; l += 64) {              // a list is sorted: its first entry worse than the last one taken is its best left
       const Ent* list = row + (int64_t)l * K;
       for (int j = 0; j < K; ++j) {
         const Ent e = list[j];
-        if (e.i == NONE) break;
-        if (better(lastv, lasti, e.v, e.i)) {
-          if (better(e.v, e.i, bv, bi)) { bv = e.v; bi = e.i; }
+        if (e.i == SEL_NONE) break;
+        if (sel_before(lastv, lasti, e.v, e.i)) {
+          b = sel_take(b, e.v, e.i);
           break;
         }
       }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float v = __shfl_xor(bv, o, 64);
-      const int c = __shfl_xor(bi, o, 64);
-      if (better(v, c, bv, bi)) { bv = v; bi = c; }
-    }
+    b = sel_wave_best(b);
+    const float bv = b.v;
+    const int bi = b.i;
     if (lane == 0) {
-      idx[(int64_t)blockIdx.x * K + k] = bi == NONE ? -1 : bi;
-      val[(int64_t)blockIdx.x * K + k] = bi == NONE ? 0.f : bv;
+      idx[(int64_t)blockIdx.x * K + k] = bi == SEL_NONE ? -1 : bi;
+      val[(int64_t)blockIdx.x * K + k] = bi == SEL_NONE ? 0.f : bv;
     }
-    if (bi == NONE) { lastv = -__builtin_inff(); lasti = NONE; }      // nothing is worse than this: the rest stays unused
+    if (bi == SEL_NONE) { lastv = -__builtin_inff(); lasti = SEL_NONE; }      // nothing is worse than this: the rest stays unused
     else { lastv = bv; lasti = bi; }
   }
 }

@@ -5,20 +5,18 @@
 //                       -- so the [n, V] logits never exist.  MFMA tiles over (64-row block, 64-column vocabulary tile); a tile's
 //                       epilogue reduces each of its rows to one (value, column) pair in a workspace [n, n_tiles]; a second, small
 //                       launch reduces a row's pairs.  No atomics: the result does not depend on the order workgroups finish in.
-// One total order everywhere: larger value first, then the SMALLER column.  Inputs are assumed finite (a NaN never wins).
+// One total order everywhere, select.h's: larger value first, then the SMALLER column.  Inputs are assumed finite.
 #include "gemm_common.h"
+#include "select.h"
 
 namespace {
 
-struct Best { float v; int c; };
-
-DEVFN bool better(float v, int c, const Best& b) { return v > b.v || (v == b.v && c < b.c); }
-DEVFN void take(Best& b, float v, int c) { if (better(v, c, b)) { b.v = v; b.c = c; } }
+typedef Sel Best;                                 // (value, column): one workspace entry
 
 template <int CTRL> DEVFN void dpp_take(Best& b) {
   const float v = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, b.v), CTRL, 0xf, 0xf, true));
-  const int c = __builtin_amdgcn_mov_dpp(b.c, CTRL, 0xf, 0xf, true);
-  take(b, v, c);
+  const int c = __builtin_amdgcn_mov_dpp(b.i, CTRL, 0xf, 0xf, true);
+  b = sel_take(b, v, c);
 }
 // Best over the 16 lanes of a DPP row (lanes with equal lane >> 4), result in every lane of the row: the moves of wave_sum.
 DEVFN void row16_best(Best& b) {
@@ -27,52 +25,31 @@ DEVFN void row16_best(Best& b) {
   dpp_take<0x141>(b);     // row_half_mirror
   dpp_take<0x140>(b);     // row_mirror
 }
-// Best over the 64 lanes, result in every lane.
-DEVFN void wave_best(Best& b) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float v = __shfl_xor(b.v, o, 64);
-    const int c = __shfl_xor(b.c, o, 64);
-    take(b, v, c);
-  }
-}
-// Best over the NW waves of a workgroup, valid in wave 0.
-template <int NW> DEVFN void block_best(Best& b, Best* red) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  wave_best(b);
-  if (lane == 0) red[wave] = b;
-  __syncthreads();
-  if (wave == 0) {
-#pragma unroll
-    for (int w = 1; w < NW; ++w) take(b, red[w].v, red[w].c);
-  }
-}
-
-constexpr int NO_COL = 0x7fffffff;
 
 // ---- rows_argmax: one workgroup per row, columns dealt to the threads in ascending order -------------------------------------
 template <typename T>
 __global__ __launch_bounds__(256) void rows_argmax_kernel(const T* __restrict__ z, int64_t ld, int V, int64_t* __restrict__ idx,
                                                           float* __restrict__ val) {
-  __shared__ Best red[4];
+  __shared__ float smv[4];
+  __shared__ int smi[4];
   const T* row = z + (int64_t)blockIdx.x * ld;
-  Best b{-__builtin_inff(), NO_COL};
+  Best b{-__builtin_inff(), SEL_NONE};
   for (int c = threadIdx.x; c < V; c += 256) {
     const float v = to_f(row[c]);
-    if (v > b.v) { b.v = v; b.c = c; }          // a thread's columns ascend: strict > keeps the smaller one
+    if (v > b.v) { b.v = v; b.i = c; }          // a thread's columns ascend: strict > keeps the smaller one
   }
-  block_best<4>(b, red);
-  if (threadIdx.x == 0) { idx[blockIdx.x] = b.c == NO_COL ? 0 : b.c; val[blockIdx.x] = b.v; }
+  b = sel_block_best<4>(b, smv, smi);
+  if (threadIdx.x == 0) { idx[blockIdx.x] = b.i == SEL_NONE ? 0 : b.i; val[blockIdx.x] = b.v; }
 }
 
 // ---- second launch of the fused form: one wave per row over its n_tiles pairs -------------------------------------------------
 __global__ __launch_bounds__(64) void pairs_argmax_kernel(const Best* __restrict__ ws, int n_tiles, int64_t* __restrict__ idx,
                                                           float* __restrict__ val) {
   const Best* row = ws + (int64_t)blockIdx.x * n_tiles;
-  Best b{-__builtin_inff(), NO_COL};
-  for (int t = threadIdx.x; t < n_tiles; t += 64) take(b, row[t].v, row[t].c);
-  wave_best(b);
-  if (threadIdx.x == 0) { idx[blockIdx.x] = b.c == NO_COL ? 0 : b.c; val[blockIdx.x] = b.v; }
+  Best b{-__builtin_inff(), SEL_NONE};
+  for (int t = threadIdx.x; t < n_tiles; t += 64) b = sel_take(b, row[t].v, row[t].i);
+  b = sel_wave_best(b);
+  if (threadIdx.x == 0) { idx[blockIdx.x] = b.i == SEL_NONE ? 0 : b.i; val[blockIdx.x] = b.v; }
 }
 
 // ---- fused product + per-tile reduction ---------------------------------------------------------------------------------------
@@ -145,7 +122,7 @@ __global__ __launch_bounds__(NW * 64) void vocab_argmax_kernel(VocabP p) {
   if (wave >= MI) return;
   Best best[4];
 #pragma unroll
-  for (int e = 0; e < 4; ++e) best[e] = Best{-__builtin_inff(), NO_COL};
+  for (int e = 0; e < 4; ++e) best[e] = Best{-__builtin_inff(), SEL_NONE};
 #pragma unroll
   for (int j = 0; j < NI; ++j) {                   // columns ascend with j: strict > keeps the smaller one
     const int v = v0 + j * 16 + li;
@@ -157,7 +134,7 @@ __global__ __launch_bounds__(NW * 64) void vocab_argmax_kernel(VocabP p) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const float z = t[e] + b;
-        if (z > best[e].v) { best[e].v = z; best[e].c = v; }
+        if (z > best[e].v) { best[e].v = z; best[e].i = v; }
       }
     }
   }

@@ -22,7 +22,9 @@ Noise rows.    Gaussian logits at scale 2 with offset +60 and at scale 20 (tests
                log_softmax of the stored values under that module's row_loss tolerance, tol(F32) * 5 relative to the reference
                maximum (the same arithmetic: a logit minus a log-sum-exp), at that module's vocabulary sizes.  (Not at V = 5: there
                a scale-20 row puts nearly all mass on one token, every |logp| drawn is below 1e-4 and fp32's own rounding of
-               1 + 1e-4 is 1e-3 of it -- "relative to the reference maximum" measures nothing; V = 5 is covered exactly above.)"""
+               1 + 1e-4 is 1e-3 of it -- "relative to the reference maximum" measures nothing; V = 5 is covered exactly above.)
+Beam's bits.   "The definition `beam_step` uses": on a gaussian row with a unique maximum, beam_step (one beam, score 0, K = 1) and top_k = 1
+               here pick the same token, and score and logp are the same 32 bits (both call csrc/select.h's normaliser)."""
 import ctypes as C
 import math
 
@@ -227,6 +229,28 @@ def test_noise_rows_follow_float64_log_softmax(dtype, V, B, kind):
     err = EL.rel_to_max(lp, ref)
     print("noise-%s-v%d-%s: logp rel-to-max error %.3e (largest |logp| %.3f)" % (dtype, V, kind, err, ref.abs().max().item()))
     assert err <= NOISE_TOL, "noise-%s-v%d-%s: logp %.3e (tol %.1e)" % (dtype, V, kind, err, NOISE_TOL)
+
+
+# ---------------------------------------------------------------------------------------------- the definition beam_step uses
+@pytest.mark.parametrize("dtype", ["f32", "bf16"])
+@pytest.mark.parametrize("V", [600, 1025, 30522])
+def test_logp_has_the_bits_of_the_beam_steps_score(V, dtype):
+    """ops.sample_topk_scored promises "the definition `beam_step` uses": on a gaussian row with a unique maximum, one beam with
+    score 0 and K = 1 scores its best token 0 + ((z - max) - lse); top_k = 1 draws that token, and its logp holds the same 32 bits."""
+    o, dev = ops(), torch.device(DEV, torch.cuda.current_device())
+    x = torch.randn(1, V, generator=torch.Generator().manual_seed(77 + V)) * 2.5
+    x[0, V - 3] = x.max() + 1.5
+    x = x.to(X.DT[dtype]).to(dev)
+    assert int((x == x.max()).sum()) == 1
+    zero, live = torch.zeros(1, 1, device=dev), torch.zeros(1, 1, dtype=torch.int32, device=dev)
+    score, done, parent = torch.full_like(zero, 7.0), torch.zeros_like(live), torch.zeros_like(live)
+    ids = torch.full((1, 1), -1, dtype=torch.int64, device=dev)
+    o.beam_step(x, zero, live, score, done, parent, ids, 0, o.beam_workspace(1, 1, dev), eos=V, pad=0)
+    out, lp = torch.full((1,), -1, dtype=torch.int64, device=dev), torch.full((1,), 7.0, device=dev)
+    o.sample_topk_scored(x, 1.0, 1, torch.full((1,), 0.5, device=dev), out, lp)
+    assert ids.item() == out.item() == V - 3
+    print("V=%d %s: beam score %r, sampler logp %r" % (V, dtype, score.item(), lp.item()))
+    assert torch.equal(bits(score.view(1)), bits(lp)), (score.item(), lp.item())
 
 
 # ---------------------------------------------------------------------------------------------- other cases
