@@ -41,7 +41,7 @@ DEVFN void st4(bf16* p, f32x4 v) {
 }
 
 // ---- AdamW, one 4-vector: pytorch_transformers==1.2.0 optimization.AdamW.step (train_gen.py:16,247) -----------------------
-// Shared by the stand-alone pass (loss.hip) and the weight-gradient launch that updates in its epilogue (gemm_dma256.hip): the
+// Shared by the stand-alone pass (optim.hip) and the weight-gradient launch that updates in its epilogue (gemm_dma256.hip): the
 // two must agree bit for bit, so contraction is OFF inside and every fused multiply-add is spelled out, and the update term
 // m / (sqrt(v) + eps) uses the hardware's 1-ulp v_sqrt_f32 / v_rcp_f32 in both (the IEEE sequences cost ~60 instructions per
 // element: invisible in the HBM-bound pass, ~30 us per tile in a GEMM epilogue with two waves per SIMD); the term is scaled by

@@ -56,7 +56,8 @@ __global__ __launch_bounds__(256) void rows_mul_kernel(T* x, int64_t ldx, const 
 
 // ---- masked-region KL loss ----------------------------------------------------------------------------------------------------
 // row i of the scores belongs to target row trow[i] (or i); labels (or NULL = every row counts): a row whose label is not 1
-// contributes nothing.  The class tail (C % 4 != 0, C = 1601) is handled here: scalar accesses, nothing is padded by the caller.
+// contributes nothing.  The class tail (C % 4 != 0, C = 1601) is handled here: scalar accesses, nothing is padded by the caller --
+// so this normaliser (expf) is not ce_row.h's ce_row_lse, and the two entries keep their own checks (no stride % 4, no alignment step).
 template <typename T>
 __global__ __launch_bounds__(256) void kl_fwd_kernel(const T* scores, int64_t lds, const float* target, int64_t ldt, const int64_t* trow,
                                                      const int64_t* labels, int64_t C, float* row_loss, float* lse_out) {
@@ -98,8 +99,7 @@ __global__ __launch_bounds__(256) void kl_bwd_kernel(const T* scores, int64_t ld
   float ts = 0.f;
   for (int64_t c = threadIdx.x; c < C; c += 256) ts += t[c];
   ts = block_reduce(ts, red, false);            // the row's ACTUAL target sum (not assumed to be 1)
-  float gs = gscale ? gscale[0] : 1.f;
-  if (mean) gs /= stats[1];
+  const float gs = loss_grad_scale(gscale, mean, stats);
   const float l = lse[m];
   for (int64_t c = threadIdx.x; c < ldd; c += 256) {
     float o = 0.f;

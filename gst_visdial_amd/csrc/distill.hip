@@ -1,7 +1,7 @@
 // Soft pseudo-labels of the self-training loop (no reference counterpart; include/gstvd_hip.h states the rules in full): the K best
 // teacher tokens of every position with their log-probabilities (gstvd_topk_logp), and the student's loss against them mixed with
 // the hard-label cross entropy (gstvd_distill_fwd / gstvd_distill_bwd).  Conventions of loss.hip: one workgroup per logits row,
-// 4-element vector accesses, deterministic reductions, stats by loss_reduce.h's rule.
+// 4-element vector accesses, deterministic reductions, the row arithmetic of ce_row.h, stats by loss_reduce.h's rule.
 #include "loss_reduce.h"
 #include "ce_row.h"
 #include "select.h"
@@ -27,15 +27,7 @@ __global__ __launch_bounds__(TNT) void topk_logp_kernel(const T* logits, int64_t
   float zr[TVEC * 4];
 #pragma unroll
   for (int j = 0; j < TVEC; ++j) {
-    const int c = (tid + j * TNT) * 4;
-    f32x4 v = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-    if (c + 3 < V) {
-      v = ld4(x + c);
-    } else {
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        if (c + e < V) v[e] = to_f(x[c + e]);
-    }
+    const f32x4 v = ld4_guard(x, (tid + j * TNT) * 4, V, -INFINITY);
 #pragma unroll
     for (int e = 0; e < 4; ++e) zr[j * 4 + e] = v[e];
   }
@@ -73,31 +65,14 @@ __global__ __launch_bounds__(256) void distill_fwd_kernel(const T* logits, int64
                                                           float* lse_tau) {
   __shared__ float red[4];
   const int64_t m = blockIdx.x;
-  const int64_t lab = labels[m];
-  const bool keep = !(lab == ignore || lab < 0 || lab >= V);
   const int64_t* sid = soft_ids + m * K;
-  if (!(keep && soft_row_ok(sid, K, V))) {                    // block-uniform
+  if (!(ce_counts(labels[m], ignore, V) && soft_row_ok(sid, K, V))) {   // block-uniform
     if (threadIdx.x == 0) { row_loss[m] = ce_loss[m]; row_kd[m] = 0.f; lse_tau[m] = 0.f; }
     return;
   }
   const T* x = logits + m * ldl;
-  const int64_t V4 = V & ~(int64_t)3;
-  float mx = -INFINITY;
-  for (int64_t c = threadIdx.x * 4; c < V4; c += 1024) {
-    f32x4 v = ld4(x + c);
-    mx = fmaxf(fmaxf(mx, fmaxf(v[0], v[1])), fmaxf(v[2], v[3]));
-  }
-  for (int64_t c = V4 + threadIdx.x; c < V; c += 256) mx = fmaxf(mx, to_f(x[c]));
-  mx = block_reduce(mx, red, true) * inv_tau;                 // inv_tau > 0: the maximum of the scaled row
-  float s = 0.f;
-  for (int64_t c = threadIdx.x * 4; c < V4; c += 1024) {
-    f32x4 v = ld4(x + c);
-    s += __expf(v[0] * inv_tau - mx) + __expf(v[1] * inv_tau - mx) + __expf(v[2] * inv_tau - mx) + __expf(v[3] * inv_tau - mx);
-  }
-  for (int64_t c = V4 + threadIdx.x; c < V; c += 256) s += __expf(to_f(x[c]) * inv_tau - mx);
-  s = block_reduce(s, red, false);
+  const float lt = ce_row_lse(x, V, red, RowTimes{inv_tau});   // inv_tau > 0: the scaled maximum is the maximum of the scaled row
   if (threadIdx.x == 0) {
-    const float lt = mx + logf(s);
     const float* sl = soft_logp + m * K;
     float smax, z;
     soft_q_norm(sl, K, inv_tau, smax, z);
@@ -124,9 +99,8 @@ __global__ __launch_bounds__(256) void distill_bwd_kernel(const T* logits, int64
   __shared__ int64_t si[KMAX];
   const int64_t m = blockIdx.x;
   const int64_t lab = labels[m];
-  const bool keep = !(lab == ignore || lab < 0 || lab >= V);
-  float gs = gscale ? gscale[0] : 1.f;
-  gs /= stats[1];
+  const bool keep = ce_counts(lab, ignore, V);
+  const float gs = loss_grad_scale(gscale, 1, stats);
   const T* x = logits + m * ldl;
   T* d = dl + m * ldd;
   const int64_t* sid = soft_ids + m * K;
@@ -147,14 +121,8 @@ __global__ __launch_bounds__(256) void distill_bwd_kernel(const T* logits, int64
   for (int64_t c = threadIdx.x * 4; c < ldd; c += 1024) {
     f32x4 o = {0.f, 0.f, 0.f, 0.f};
     if (c < V) {
-      f32x4 v = {0.f, 0.f, 0.f, 0.f}, qs = {0.f, 0.f, 0.f, 0.f};
-      if (c + 3 < V) {
-        v = ld4(x + c);
-      } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          if (c + e < V) v[e] = to_f(x[c + e]);
-      }
+      const f32x4 v = ld4_guard(x, c, V, 0.f);
+      f32x4 qs = {0.f, 0.f, 0.f, 0.f};
       for (int k = 0; k < K; ++k) {                           // duplicate ids count as separate entries: their q add up, k ascending
         const int64_t off = si[k] - c;
         if (off >= 0 && off < 4) {
@@ -174,15 +142,14 @@ __global__ __launch_bounds__(256) void distill_bwd_kernel(const T* logits, int64
 }  // namespace
 
 // ---- C ABI -----------------------------------------------------------------------------------------------------------------------
+// The student entries' own shape terms: K entries per token, the mixing weight and a finite positive 1 / tau.
+static bool soft_args_bad(int64_t K, float a, float it) { return K < 1 || K > KMAX || !(a >= 0.f && a <= 1.f) || !(it > 0.f) || isinf(it); }
+
 extern "C" int gstvd_topk_logp(const void* logits, int64_t ldl, const float* lse, int64_t M, int64_t V, int64_t K, int32_t dtype,
                                int64_t* ids, float* logp, gstvd_stream_t stream) {
-  if (!logits || !lse || !ids || !logp) return GSTVD_E_NULL;
-  if (M <= 0 || V <= 0 || (ldl % 4) || ldl < V || K < 1 || K > KMAX || K > V) return GSTVD_E_SHAPE;
-  if (dtype != GSTVD_BF16 && dtype != GSTVD_F32) return GSTVD_E_DTYPE;
-  if (ce_misaligned(logits, dtype)) return GSTVD_E_ALIGN;
+  if (const int rc = ce_row_args(!logits || !lse || !ids || !logp, M, V, K < 1 || K > KMAX || K > V, dtype, logits, ldl)) return rc;
   if (V > TVEC * 4 * TNT) return GSTVD_E_UNSUPPORTED;         // a row lives in 32 registers per thread
-  hipStream_t s = (hipStream_t)stream;
-  GSTVD_FOR_DTYPE(dtype, T, hipLaunchKernelGGL(topk_logp_kernel<T>, dim3((unsigned)M), dim3(TNT), 0, s, (const T*)logits, ldl, lse, (int)V, (int)K, ids, logp));
+  GSTVD_FOR_DTYPE(dtype, T, hipLaunchKernelGGL(topk_logp_kernel<T>, dim3((unsigned)M), dim3(TNT), 0, (hipStream_t)stream, (const T*)logits, ldl, lse, (int)V, (int)K, ids, logp));
   GSTVD_LAUNCH_CHECK();
   return 0;
 }
@@ -191,11 +158,8 @@ extern "C" int gstvd_distill_fwd(const void* logits, int64_t ldl, const int64_t*
                                  int64_t M, int64_t V, int64_t K, int64_t ignore_index, float alpha, float inv_tau, int32_t dtype,
                                  const float* ce_row_loss, float* row_loss, float* row_kd, float* lse_tau, float* stats_out,
                                  gstvd_stream_t stream) {
-  if (!logits || !labels || !soft_ids || !soft_logp || !ce_row_loss || !row_loss || !row_kd || !lse_tau || !stats_out) return GSTVD_E_NULL;
-  if (M <= 0 || V <= 0 || (ldl % 4) || ldl < V || K < 1 || K > KMAX || !(alpha >= 0.f && alpha <= 1.f) || !(inv_tau > 0.f) || isinf(inv_tau))
-    return GSTVD_E_SHAPE;
-  if (dtype != GSTVD_BF16 && dtype != GSTVD_F32) return GSTVD_E_DTYPE;
-  if (ce_misaligned(logits, dtype)) return GSTVD_E_ALIGN;
+  if (const int rc = ce_row_args(!logits || !labels || !soft_ids || !soft_logp || !ce_row_loss || !row_loss || !row_kd || !lse_tau || !stats_out, M, V,
+                                 soft_args_bad(K, alpha, inv_tau), dtype, logits, ldl)) return rc;
   hipStream_t s = (hipStream_t)stream;
   GSTVD_FOR_DTYPE(dtype, T, hipLaunchKernelGGL(distill_fwd_kernel<T>, dim3((unsigned)M), dim3(256), 0, s, (const T*)logits, ldl, labels, soft_ids, soft_logp, V, (int)K,
                                                ignore_index, alpha, inv_tau, ce_row_loss, row_loss, row_kd, lse_tau));
@@ -209,14 +173,9 @@ extern "C" int gstvd_distill_bwd(const void* logits, int64_t ldl, const int64_t*
                                  const float* lse, const float* lse_tau, const float* stats, const float* gscale, int64_t M, int64_t V,
                                  int64_t K, int64_t ignore_index, float alpha, float inv_tau, int32_t dtype, void* dlogits, int64_t ldd,
                                  gstvd_stream_t stream) {
-  if (!logits || !labels || !soft_ids || !soft_logp || !lse || !lse_tau || !stats || !dlogits) return GSTVD_E_NULL;
-  if (M <= 0 || V <= 0 || (ldl % 4) || (ldd % 4) || ldl < V || ldd < V || K < 1 || K > KMAX || !(alpha >= 0.f && alpha <= 1.f) ||
-      !(inv_tau > 0.f) || isinf(inv_tau))
-    return GSTVD_E_SHAPE;
-  if (dtype != GSTVD_BF16 && dtype != GSTVD_F32) return GSTVD_E_DTYPE;
-  if (ce_misaligned(logits, dtype) || ce_misaligned(dlogits, dtype)) return GSTVD_E_ALIGN;
-  hipStream_t s = (hipStream_t)stream;
-  GSTVD_FOR_DTYPE(dtype, T, hipLaunchKernelGGL(distill_bwd_kernel<T>, dim3((unsigned)M), dim3(256), 0, s, (const T*)logits, ldl, labels, soft_ids, soft_logp, lse, lse_tau,
+  if (const int rc = ce_row_args(!logits || !labels || !soft_ids || !soft_logp || !lse || !lse_tau || !stats || !dlogits, M, V,
+                                 soft_args_bad(K, alpha, inv_tau), dtype, logits, ldl, dlogits, ldd)) return rc;
+  GSTVD_FOR_DTYPE(dtype, T, hipLaunchKernelGGL(distill_bwd_kernel<T>, dim3((unsigned)M), dim3(256), 0, (hipStream_t)stream, (const T*)logits, ldl, labels, soft_ids, soft_logp, lse, lse_tau,
                                                stats, gscale, V, (int)K, ignore_index, alpha, inv_tau, (T*)dlogits, ldd));
   GSTVD_LAUNCH_CHECK();
   return 0;

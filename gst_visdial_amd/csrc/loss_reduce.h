@@ -3,8 +3,16 @@
 // ONE block; a thread sums the rows tid, tid + blockDim.x, ..., then block_reduce: the block size fixes the order of the additions
 // and with it every bit of stats, so each caller keeps its own (256, 256, 64).  A row counts when
 //   labels == NULL (every row), or eq ? labels[i] == value : labels[i] != value.
+// The backward scales every row by loss_grad_scale (ce_bwd_kernel, distill_bwd_kernel, kl_bwd_kernel).  Not here, on purpose:
+// nsp_train_bwd_kernel (pool_head.hip) divides by its argument B -- it takes no stats pointer; reading one would add a load.
 #pragma once
 #include "common.h"
+
+// Upstream gradient of one row loss: gscale[0] (1 without one), divided by the number of counted rows, stats[1], for a mean loss.
+DEVFN float loss_grad_scale(const float* gscale, int mean, const float* stats) {
+  const float gs = gscale ? gscale[0] : 1.f;
+  return mean ? gs / stats[1] : gs;
+}
 
 static __global__ __launch_bounds__(256) void row_loss_reduce_kernel(const float* row_loss, const int64_t* labels, int64_t value, int eq,
                                                                      int64_t M, float* stats) {

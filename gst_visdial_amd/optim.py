@@ -163,7 +163,7 @@ class FusedAdamW(object):
         self.v = torch.zeros_like(flat.P)
         if old is not None:                      # the flat buffers were re-materialised (model.to(), aliasing): keep the moments
             self.m.copy_(old[0]); self.v.copy_(old[1])
-        # bias correction reads this counter on the device (loss.hip adamw_kernel): it must follow opt_step across resumes
+        # bias correction reads this counter on the device (optim.hip adamw_kernel): it must follow opt_step across resumes
         self.step_dev = torch.full((1,), float(self.opt_step), dtype=torch.float32, device=dev)
         self._built, self._flat_id = True, id(flat.P)
         self._last_lr_key = None

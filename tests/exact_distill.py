@@ -322,5 +322,35 @@ def check_alpha_zero(be, dtype, V):
     surroundings((("dlogits of ce_bwd", dc),), name)
 
 
+# ============================================================================================== one row log-sum-exp
+LSE1_V = (1, 3, 4, 5, 1025, 30522)      # no vector body, tail only, exactly one vector, vector plus tail, the workload's size
+LSE1_CASES = [(dtype, V) for dtype in ("f32", "bf16") for V in LSE1_V]
+
+
+def check_lse_tau_one(be, dtype, V):
+    """tau = 1 on rows that count and carry a soft label: gstvd_distill_fwd's lse_tau is gstvd_ce_fwd's lse as 32-bit patterns.  The
+    two kernels run ONE row log-sum-exp (csrc/ce_row.h), the student's with v * inv_tau in front, and v * 1.0f - mx, fused or not,
+    rounds once to v - mx; gstvd_distill_bwd mixes the two normalisers on one row, so they must stay in step."""
+    dev, dt, M = be.device, DT[dtype], 5
+    name = "distill_lse_tau1-%s-v%d" % (dtype, V)
+    gen = E.generator(9900 + V, dev)
+    x = X.noise_logits(M, V, "gauss", dt, gen, dev)
+    lab = torch.randint(0, V, (M,), generator=gen, device=dev)
+    sid = (torch.arange(M, device=dev) % V).view(M, 1)
+    logits, labels = win_in(x, dt, dev, pad=_dims(V)[0] - V), win_in(lab, I64, dev)
+    sw, lw = win_in(sid, I64, dev), win_in(torch.full((M, 1), -1.0, dtype=torch.float64, device=dev), F32, dev)
+    rl, lse, st = (win_out(1, n, F32, dev) for n in (M, M, 3))
+    be.ce_fwd(logits.view, vec(labels), M, V, vec(rl), vec(lse), vec(st), IGNORE_EXACT)
+    l, kd, lt, so = (win_out(1, n, F32, dev) for n in (M, M, M, 3))
+    be.distill_fwd(logits.view, vec(labels), sw.view, lw.view, M, V, 0.5, 1.0, vec(rl), vec(l), vec(kd), vec(lt), vec(so), IGNORE_EXACT)
+    assert bool(torch.isfinite(vec(lse)).all()) and st.view.reshape(-1)[1].item() == float(M), name + ": every row counts"
+    assert_same_bits(vec(lt), vec(lse), name + ": lse_tau at tau = 1 against gstvd_ce_fwd's lse")
+    e = rel_to_max(vec(lse), torch.logsumexp(x, -1))
+    assert e <= tol(F32) * 5, "%s: lse %.3e (tol %.1e)" % (name, e, tol(F32) * 5)
+    surroundings((("row_loss", l), ("row_kd", kd), ("lse_tau", lt), ("stats", so), ("ce row_loss", rl), ("lse", lse), ("ce stats", st),
+                  ("logits", logits), ("labels", labels), ("soft_ids", sw), ("soft_logp", lw)), name)
+
+
 def case_count():
-    return {"top-k": len(TOPK_CASES), "backward exact": len(BWD_CASES), "noise": len(NOISE_CASES), "alpha 0": len(ALPHA0_CASES)}
+    return {"top-k": len(TOPK_CASES), "backward exact": len(BWD_CASES), "noise": len(NOISE_CASES), "alpha 0": len(ALPHA0_CASES),
+            "lse at tau 1": len(LSE1_CASES)}

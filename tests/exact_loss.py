@@ -1,5 +1,5 @@
 """Exact layer of the loss and optimizer tests: csrc/loss.hip -- cross entropy forward, backward and per-row
-backward, answer_scores, the casts, vl_split and the three AdamW entries -- on inputs whose answer is known bit for bit.
+backward, answer_scores -- csrc/elementwise.hip -- the casts, vl_split -- and csrc/optim.hip -- the three AdamW entries -- on inputs whose answer is known bit for bit.
 
 Cross entropy, pointer rows.  A row has ONE hot column j holding an integer L in [-8, 8]; every other column holds L - 112 - 8k
 (k in 0..15 drawn per column; k in 0..1 where L is odd, so that every value keeps within the 8 bits of bf16) or -inf.  exp(-112)

@@ -1,7 +1,8 @@
 """Exact layer of the soft pseudo-label tests on a real MI355X (tests/exact_distill.py): csrc/distill.hip
 through gst_visdial_amd.ops -- the teacher's top-K on integer rows (ids and logp bit-exact: borders of the loops, ties, rows with
 fewer than K finite values), the student's backward on pointer rows (bit-exact), alpha == 0 against gstvd_ce_bwd bit for bit, forward
-and backward at tau in {0.5, 2} on noise rows against float64 -- every output in a canary window, every input in a poisoned one,
+and backward at tau in {0.5, 2} on noise rows against float64, lse_tau at tau = 1 against gstvd_ce_fwd's lse bit for bit (the one
+row log-sum-exp of csrc/ce_row.h under both of its pre-scales) -- every output in a canary window, every input in a poisoned one,
 every launch repeated.  The harness itself is proved on the CPU by tests/test_exact_distill_harness_cpu.py; the premises of the
 pointer rows (__expf(0) == 1, logf(1) == 0, __expf(x) == 0 for x <= -112) have their tests in tests/test_loss_exact_gpu.py."""
 import pytest
@@ -60,6 +61,11 @@ def test_noise_rows_against_float64(dtype, V, kind, tau):
     D.check_noise(Gpu(), dtype, V, kind, tau)
 
 
+@pytest.mark.parametrize("dtype,V", D.LSE1_CASES)
+def test_lse_tau_at_tau_one_is_the_cross_entropy_lse_bit_for_bit(dtype, V):
+    D.check_lse_tau_one(Gpu(), dtype, V)
+
+
 def test_refusals_come_before_any_launch():
     """K outside 1..16 or above V, alpha outside [0, 1], inv_tau not positive, ldl < V: GSTVD_E_SHAPE; V above 32768 for the top-K:
     GSTVD_E_UNSUPPORTED; a misaligned logits / dlogits pointer: GSTVD_E_ALIGN; a dtype that is neither: GSTVD_E_DTYPE.  Only return
@@ -114,4 +120,4 @@ def test_refusals_come_before_any_launch():
 def test_case_count():
     n = D.case_count()
     print("cases: %s; total %d" % (", ".join("%s %d" % kv for kv in n.items()), sum(n.values())))
-    assert sum(n.values()) == 80
+    assert sum(n.values()) == 92

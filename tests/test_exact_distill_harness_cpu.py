@@ -139,6 +139,11 @@ def test_alpha_zero_case_passes_on_the_stand_in(dtype):
     D.check_alpha_zero(Torch(), dtype, 1030)
 
 
+@pytest.mark.parametrize("dtype,V", [c for c in D.LSE1_CASES if c[1] <= 1025])
+def test_lse_at_tau_one_cases_pass_on_the_stand_in(dtype, V):
+    D.check_lse_tau_one(Torch(), dtype, V)
+
+
 DEFECTS = {
     "ties to the larger id": lambda be: D.check_topk(be, "f32", 1025, 4),
     "-inf entries dropped": lambda be: D.check_topk(be, "bf16", 1023, 16),

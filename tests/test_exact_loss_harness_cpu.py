@@ -1,5 +1,5 @@
 """The exact layer of the loss and optimizer tests proves itself on the CPU (tests/exact_loss.py): every case
-runs against a stand-in of csrc/loss.hip written in torch -- the cross entropy with the kernels' column loops (4-element vectors,
+runs against a stand-in of csrc/loss.hip, csrc/optim.hip and csrc/elementwise.hip written in torch -- the cross entropy with the kernels' column loops (4-element vectors,
 stride 1024, scalar tail), AdamW in emulated fp32 with the kernel's fused steps -- and against deliberately wrong stand-ins, each
 of which must fail the case named for it.  Nothing here touches a GPU."""
 import numpy as np
@@ -32,7 +32,7 @@ def visit_columns(V, stride=1024, tail=None):
 
 
 class Torch(object):
-    """Stand-in of the entries of csrc/loss.hip.  `defect`: one planted error, by its name in DEFECTS."""
+    """Stand-in of the entries of csrc/loss.hip, csrc/optim.hip and csrc/elementwise.hip.  `defect`: one planted error, by its name in DEFECTS."""
 
     def __init__(self, defect=None):
         self.device, self.defect = CPU, defect

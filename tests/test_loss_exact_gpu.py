@@ -1,5 +1,5 @@
-"""Exact layer of the loss and optimizer tests on a real MI355X (tests/exact_loss.py): csrc/loss.hip through
-gst_visdial_amd.ops -- cross entropy forward / backward / per-row backward on pointer rows (bit-exact) and noise rows (float64
+"""Exact layer of the loss and optimizer tests on a real MI355X (tests/exact_loss.py): csrc/loss.hip,
+csrc/optim.hip and csrc/elementwise.hip through gst_visdial_amd.ops -- cross entropy forward / backward / per-row backward on pointer rows (bit-exact) and noise rows (float64
 reference, the tolerances of tests/test_ops_gpu.py), answer_scores, AdamW's three entries on inputs every fp32 operation of which
 is exact, the four casts, cast_ranges, vl_split -- every output in a canary window, every input in a poisoned one, every launch
 repeated.  The harness itself is proved on the CPU by tests/test_exact_loss_harness_cpu.py.

@@ -63,7 +63,7 @@ def test_header_ctypes_table_and_abi_number():
     with open(os.path.join(ROOT, "include", "gstvd_hip.h")) as f:
         h = f.read()
     assert _lib.ABI_VERSION == 9
-    with open(os.path.join(ROOT, "gst_visdial_amd", "csrc", "loss.hip")) as f:
+    with open(os.path.join(ROOT, "gst_visdial_amd", "csrc", "elementwise.hip")) as f:
         assert re.search(r"gstvd_abi_version\(void\) \{ return 9; \}", f.read())
     m = re.search(r"int gstvd_attn_group_bwd\(const gstvd_attn_t\* a, gstvd_stream_t s\);", h)
     assert m and "gstvd_attn_group_bwd" in _lib.SIGNATURES

@@ -153,7 +153,7 @@ def test_documented_abi_version_is_the_librarys():
     txt = open(os.path.join(ROOT, "INTEGRATION.md")).read()
     m = re.search(r"gstvd_abi_version\(\)\s*==\s*(\d+)", txt)
     assert m and int(m.group(1)) == _lib.ABI_VERSION
-    src = open(os.path.join(ROOT, "gst_visdial_amd", "csrc", "loss.hip")).read()
+    src = open(os.path.join(ROOT, "gst_visdial_amd", "csrc", "elementwise.hip")).read()
     m = re.search(r"gstvd_abi_version\(void\)\s*\{\s*return\s+(\d+);", src)
     assert m and int(m.group(1)) == _lib.ABI_VERSION
     design = open(os.path.join(ROOT, "DESIGN.md")).read()
