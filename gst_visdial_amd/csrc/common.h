@@ -145,22 +145,33 @@ DEVFN float block_reduce(float v, float* red, bool is_max) {
 // lowbias32 integer hash (full avalanche); one 32-bit draw serves two elements (16 bits each).
 // Counter hash of the dropout draws: xorshift folds around two 24-bit multiplies (v_mul_u32_u24: full rate; a 32-bit
 // v_mul_lo_u32 issues at quarter rate and the attention kernels, which draw once per two score elements, are VALU bound).
-// The fold in front of each multiply brings bits 16..31 down into the 24 bits the multiply reads.  Avalanche (every output
-// bit flips with probability 0.497-0.503 for every input bit) and the keep statistics of sequential counters match the
-// 32-bit-multiply mixer it replaced (round 3; numbers in DESIGN.md section 3, "Activations").
-DEVFN uint32_t mix32(uint32_t x) {
-  x ^= x >> 16; x = __umul24(x, 0xeb352dU); x ^= x >> 15; x = __umul24(x, 0x6ca68bU); x ^= x >> 16;
+// The fold in front of each multiply brings bits 16..31 down into the 24 bits the multiply reads.  Avalanche: every output
+// bit flips with probability 0.497-0.503 for every input bit.  The keep rates and the independence of sites, offsets, seeds,
+// lags and the two halves of a draw are tests (tests/exact_dropout.py check D, on the device and on its numpy restatement).
+// `mid` is XORed into the product of the first multiply (mix32(x) == mix32(x, 0)): see drop_hash.
+DEVFN uint32_t mix32(uint32_t x, uint32_t mid = 0) {
+  x ^= x >> 16; x = __umul24(x, 0xeb352dU) ^ mid; x ^= x >> 15; x = __umul24(x, 0x6ca68bU); x ^= x >> 16;
   return x;
 }
-// Draw for 32-bit counter c under `key`.  mix32's first multiply reads 24 bits: after the xor-fold the counter's TOP BYTE meets
-// them only linearly (in bits 8..15), so c and c ^ 0x01000100 gave the same draw for every key -- exact duplicates of the mask
-// at a fixed distance as soon as a site has more than 2^24 draws (2^25 elements: attention probabilities at >= 43 rows x 12
-// heads x 256 x 256).  The top byte is therefore hashed into the key first (8 bits x a 24-bit odd constant, a full-rate
-// v_mul_u32_u24; it is zero -- and the stream unchanged -- for the first 2^24 counters of a site): counters that differ in bits
-// 24..31 now collide only like any two unrelated counters (tests/test_host_logic.py restates this hash in numpy and checks
-// both; tests/test_ops_gpu.py checks the device masks of a 2^26-element site).
+// Draw for 32-bit counter c under `key`.  mix32's first multiply reads 24 bits: after the xor-fold it sees the bytes
+// (b2, b1 ^ b3, b0 ^ b2) of its input and nothing else.  WHATEVER is XORed in front of that multiply therefore only permutes
+// one fixed table of 2^24 draws: without a top-byte term c and c ^ 0x01000100 gave the same draw for every key, and with the
+// term umul24(c >> 24, 0x9E3779) XORed into the input (round 3) the repeats only moved -- draw(c | t << 24) == draw(c ^ d_t)
+// for every key, every t and every c < 2^24 (d_1 = 0x9E3679): exact duplicates of the mask at a fixed distance as soon as a
+// site has more than 2^24 draws (2^25 elements: attention probabilities at >= 43 rows x 12 heads x 256 x 256).  The top byte
+// (8 bits x a 24-bit odd constant, a full-rate v_mul_u32_u24) is therefore XORed into the PRODUCT of the first multiply, whose
+// 32 bits the second fold and multiply mix: block t of 2^24 counters is block 0 with another 32-bit word XORed in between the
+// two multiplies, and no XOR distance between two blocks carries more than ~1e-4 of the draws.  The term is zero -- the stream
+// unchanged -- for the first 2^24 counters of a site, and it costs what it cost in front: shift, multiply, XOR (the
+// attention kernels' 32-bit draws compile to the same instruction counts as before; drop_draw's 64-bit form spends one more XOR
+// per TWO draws, since the pair of a drop_factor4 no longer shares key ^ term).  What it cannot
+// do is widen the table's index: draw VALUES still coincide between blocks at the rate any hash with 2^24 outputs per block
+// gives (~0.65), at no particular distance; and a key still has 24 effective bits.
+// tests/exact_dropout.py restates the whole chain in numpy; its checks E (host: no concentrated distance between blocks) and
+// C / F (tests/test_dropout_exact_gpu.py: a 2^26-element site of the device equals the restatement; its keep bits at the
+// distances d_t are independent) hold this.
 DEVFN uint32_t drop_hash(uint32_t c, uint32_t key) {
-  return mix32(c ^ key ^ __umul24(c >> 24, 0x9E3779u));
+  return mix32(c ^ key, __umul24(c >> 24, 0x9E3779u));
 }
 struct DropKey {
   uint32_t key, thr;   // keep iff u16 >= thr
@@ -185,7 +196,7 @@ DEVFN DropKey make_drop(float p, uint32_t site, const uint64_t* rng) {
 }
 DEVFN uint32_t drop_draw(const DropKey& k, uint64_t e2) {   // e2 = element index >> 1
   uint32_t lo = (uint32_t)e2, hi = (uint32_t)(e2 >> 32);
-  return mix32((lo ^ k.key ^ __umul24(lo >> 24, 0x9E3779u)) + hi * 0x9E3779B1u);
+  return mix32((lo ^ k.key) + hi * 0x9E3779B1u, __umul24(lo >> 24, 0x9E3779u));   // hi == 0: drop_hash(lo, k.key)
 }
 DEVFN float drop_factor(const DropKey& k, uint64_t e) {     // scale if kept, 0 if dropped
   if (!k.on) return 1.f;

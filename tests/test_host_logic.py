@@ -358,22 +358,7 @@ def test_rank_seed_gives_every_rank_its_own_dropout_stream():
     assert len({s & 0xffffffff for s in seeds}) == 8 and len({s >> 32 for s in seeds}) == 8     # both words the kernels hash differ
 
 
-def _np_mix32(x):
-    """csrc/common.h mix32 restated in numpy (uint32 wrap-around arithmetic; __umul24 = product of the low 24 bits, low 32 kept)."""
-    import numpy as np
-    x = x.astype(np.uint64)
-    m = np.uint64(0xFFFFFFFF)
-    x ^= x >> np.uint64(16); x = ((x & np.uint64(0xFFFFFF)) * np.uint64(0xeb352d)) & m
-    x ^= x >> np.uint64(15); x = ((x & np.uint64(0xFFFFFF)) * np.uint64(0x6ca68b)) & m
-    x ^= x >> np.uint64(16)
-    return x.astype(np.uint32)
-
-
-def _np_drop_hash(c, key):
-    import numpy as np
-    c = c.astype(np.uint64)
-    t = ((c >> np.uint64(24)) * np.uint64(0x9E3779)) & np.uint64(0xFFFFFFFF)
-    return _np_mix32((c ^ np.uint64(key) ^ t) & np.uint64(0xFFFFFFFF))
+from exact_dropout import mix32 as _np_mix32, drop_hash as _np_drop_hash      # the suite's one numpy restatement of csrc/common.h
 
 
 def test_dropout_counter_hash_has_no_structured_top_byte_collisions():
@@ -389,7 +374,8 @@ def test_dropout_counter_hash_has_no_structured_top_byte_collisions():
         new = _np_drop_hash(c, key)
         low = c < (1 << 24)
         assert np.array_equal(new[low], old[low])                                                   # (a)
-        for flip in (0x01000100, 0x02000200, 0x80008000, 0x01000000, 0xff000000, 0x81008100):
+        for flip in (0x01000100, 0x02000200, 0x80008000, 0x01000000, 0xff000000, 0x81008100,
+                     0x019E3679, 0x023C6DF2, 0xFF992387):      # d_t | t << 24 of the round-3 form, t = 1, 2, 255 (exact_dropout.parent_distance)
             same = (new == _np_drop_hash(c ^ np.uint32(flip), key)).mean()
             assert same < 1e-3, (hex(key), hex(flip), same)                                       # (b): unrelated draws
     # counters that differ ONLY in bits 24..31 (256 blocks of one low part): all 256 draws distinct for almost every low part

@@ -199,6 +199,10 @@ def test_dropout_masks_of_a_site_larger_than_2p24_draws_do_not_repeat():
     partner = (((e >> 1) ^ 0x01000100) << 1) | (e & 1)                  # the element whose pair counter differs in bits 8 and 24
     agree = (keep[e] == keep[partner]).float().mean().item()
     assert abs(agree - (p * p + (1 - p) * (1 - p))) < 5e-3, agree      # 0.625; the defect gave 1.0
+    # the round-3 hash (top byte XORed in FRONT of mix32's first multiply) repeated block 0 in block 1 at distance 0x9E3679
+    partner = ((((e >> 1) ^ 0x9E3679) | (1 << 24)) << 1) | (e & 1)
+    agree = (keep[e] == keep[partner]).float().mean().item()
+    assert int(partner.max()) < n and abs(agree - 0.625) < 5 * 2.4e-4, agree     # 5 sigma at 2^22 samples; that hash gave 1.0
     small = o.dropout_mask(1 << 20, p, 5, rng, DEV) != 0
     assert torch.equal(small, keep[: 1 << 20])
 
