@@ -20,6 +20,7 @@ EPI_COLSUM, EPI_COLSUM_ACC = 32, 64
 EPI_ADAMW = 128
 LN_RESID, LN_EMBED, LN_IMAGE = 0, 1, 2
 RANK_MAX_OPTIONS = 128
+GEN_EVAL, GEN_TEST, GEN_TRAIN_A, GEN_TRAIN_Q = range(4)
 (RANK_N_SPARSE, RANK_N_GT_SKIPPED, RANK_N_NDCG, RANK_N_NDCG_EMPTY, RANK_N_REL_SKIPPED, RANK_N_CALLS, RANK_NDCG_SUM) = range(7)
 RANK_HIST = 8
 RANK_ACC_SLOTS = RANK_HIST + RANK_MAX_OPTIONS + 1
@@ -159,6 +160,19 @@ class DiscRowsDesc(C.Structure):
                 ("tot_rounds", _i32), ("num_options", _i32), ("train", _i32)]
 
 
+class GenRowsDesc(C.Structure):
+    """gstvd_gen_rows_t: encoder and decoder rows of the generative model from token-id pools, one launch."""
+    _fields_ = [("cap", _vp), ("ld_cap", _i64), ("ques", _vp), ("ans", _vp), ("ld_utt", _i64), ("opts", _vp), ("ld_opt", _i64),
+                ("gt_index", _vp), ("enc_dialog", _vp), ("enc_round", _vp), ("u_tok", _vp), ("ld_u", _i64),
+                ("tokens", _vp), ("segments", _vp), ("mlm", _vp), ("att", _vp), ("ld_row", _i64),
+                ("sep_indices", _vp), ("ld_sep", _i64), ("hist_len", _vp),
+                ("dec_dialog", _vp), ("dec_round", _vp), ("dec_slot", _vp),
+                ("dec_ids", _vp), ("dec_labels", _vp), ("dec_att", _vp), ("ld_dec", _i64), ("dec_option", _vp),
+                ("mask_prob", C.c_double), ("cls", _i64), ("sep", _i64), ("mask_id", _i64), ("n_enc", _i64), ("n_dec", _i64),
+                ("D", _i32), ("R", _i32), ("Ro", _i32), ("O", _i32), ("U", _i32), ("Lc", _i32), ("T", _i32), ("S", _i32), ("Ud", _i32),
+                ("num_options", _i32), ("mode", _i32), ("reserved_", _i32)]
+
+
 class RankMetricsDesc(C.Structure):
     """gstvd_rank_metrics_t: ranks, ground-truth ranks, NDCG ratios and accumulator additions of L score lists, one call."""
     _fields_ = [("scores", _vp), ("ld_scores", _i64), ("gt_index", _vp), ("relevance", _vp), ("ld_rel", _i64), ("n_rel", _i64),
@@ -261,6 +275,7 @@ SIGNATURES = {
     "gstvd_cos_topk": (_i32, [_vp, _i64, _i64, _i64, _vp, _i64, _i32, _f32, _i32, _vp, _i64, _vp, _vp, _vp]),
     "gstvd_subseq_replace": (_i32, [C.POINTER(SubseqReplaceDesc), _vp]),
     "gstvd_disc_rows": (_i32, [C.POINTER(DiscRowsDesc), _vp]),
+    "gstvd_gen_rows": (_i32, [C.POINTER(GenRowsDesc), _vp]),
     "gstvd_rank_metrics": (_i32, [C.POINTER(RankMetricsDesc), _vp]),
     "gstvd_gauss_fit_ws_bytes": (_i64, [_i64, _i32]),
     "gstvd_gauss_fit": (_i32, [C.POINTER(GaussFitDesc), _vp]),

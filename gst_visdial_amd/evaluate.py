@@ -5,12 +5,17 @@ same metrics; the model work differs in one way that does not change results: ev
 ONCE and shared by its `options` answer candidates instead of being re-encoded per candidate."""
 import torch
 
+from . import gen_rows as _gen_rows
 from . import metrics as _metrics
 from .metrics import SparseGTMetrics, NDCG, scores_to_ranks
 
 
-def score_batch(model, batch, device, rounds_per_call=20):
-    """-> scores [B, rounds, options] (sum of target-token log-probabilities of every candidate answer)."""
+def score_batch(model, batch, device, rounds_per_call=20, params=None):
+    """-> scores [B, rounds, options] (sum of target-token log-probabilities of every candidate answer).
+    A pooled batch (gen_rows.is_pooled: token-id pools on the device) has its rows written on the device, chunk by chunk; `params`
+    then gives max_seq_len, max_utt_len, num_options, attack and mask_prob (the loader's defaults without it)."""
+    if _gen_rows.is_pooled(batch):
+        return _score_batch_pooled(model, batch, rounds_per_call, params)
     ids = batch["enc_input_ids"]
     B, R_, O = ids.shape[0], ids.shape[1], ids.shape[2]
     T, U = ids.shape[-1], batch["dec_input_ids"].shape[-1]
@@ -58,6 +63,36 @@ def _score_batch_per_row(model, batch, device, rounds_per_call):
     return torch.cat(out).view(B, R_, O)
 
 
+def _score_batch_pooled(model, batch, rounds_per_call, params):
+    """score_batch on token-id pools: per chunk one gen_rows launch writes the encoder row of every round and its decoder rows --
+    nothing is compared, nothing crosses from the host.  A test-split batch (it carries n_rounds) scores one round per dialog;
+    under the random-token noise every option row has its own context (group 1), with the draws of batch['u_tok']
+    [D * R * num_options, T] when given."""
+    feat, loc, imask = (batch[k] for k in _gen_rows.IMAGE_KEYS)
+    test = "n_rounds" in batch
+    D, R = batch["ques"].shape[:2]
+    n = D if test else D * R
+    step = max(1, rounds_per_call)
+    u_tok = batch.get("u_tok")
+    slots = _gen_rows.num_slots(batch, params)               # rows of u_tok per round
+    out = []
+    for s in range(0, n, step):
+        e = min(s + step, n)
+        if test:
+            it = _gen_rows.test_rounds(batch, s, e, params)
+        else:
+            it = _gen_rows.eval_rounds(batch, s, e, params, None if u_tok is None else u_tok[s * slots:e * slots])
+        d = it["dialog"]
+        out.append(model.score_candidates(feat[d], loc[d], imask[d], it["enc_input_ids"], it["enc_segments"], it["enc_att_mask"],
+                                          it["dec_input_ids"], it["dec_att_mask"], it["group"]))
+    scores = torch.cat(out)
+    return scores.view(D, 1, -1) if test else scores.view(D, R, -1)
+
+
+def _default_scorer(params):
+    return lambda model, batch, device: score_batch(model, batch, device, params=params)
+
+
 @torch.no_grad()
 def evaluate(model, dataloader, params, mode="vd_eval_val", scorer=None, group=None, metrics="host"):
     """Returns (ranks_json, metrics) like evaluate_gen.evaluate + its logged metric dict.
@@ -71,10 +106,10 @@ def evaluate(model, dataloader, params, mode="vd_eval_val", scorer=None, group=N
     then ranked by the stable rule; in the test-split modes the ranks cross to the host once, after the loop)."""
     import torch.distributed as dist
     if metrics == "device":
-        return _evaluate_device(model, dataloader, params, mode, scorer or score_batch, group)
+        return _evaluate_device(model, dataloader, params, mode, scorer or _default_scorer(params), group)
     if metrics != "host":
         raise ValueError("evaluate: metrics must be 'host' or 'device' (got %r)" % (metrics,))
-    scorer = scorer or score_batch
+    scorer = scorer or _default_scorer(params)
     sparse, ndcg, ranks_json = SparseGTMetrics(), NDCG(), []
     if hasattr(model, "eval"):
         model.eval()
@@ -86,10 +121,12 @@ def evaluate(model, dataloader, params, mode="vd_eval_val", scorer=None, group=N
             continue
         scores = scorer(model, batch, device)
         if mode == "vd_eval_val":
-            sparse.observe(scores, batch["gt_option_inds"])
+            pooled = _gen_rows.is_pooled(batch)          # its targets follow the slot rule: ground truth first, relevance re-ordered
+            gt_inds, rel = _gen_rows.eval_targets(batch, params) if pooled else (batch["gt_option_inds"], batch.get("gt_relevance"))
+            sparse.observe(scores, gt_inds)
             if params.get("vd_version", "1.0") == "1.0" and "gt_relevance" in batch:
                 rid = batch["round_id"].squeeze(1)
-                ndcg.observe(scores[torch.arange(scores.size(0)), rid - 1, :], batch["gt_relevance"])
+                ndcg.observe(scores[torch.arange(scores.size(0)), (rid.cpu() if pooled else rid) - 1, :], rel)
         else:
             ranks = scores_to_ranks(scores).squeeze(1)
             for j in range(scores.shape[0]):
@@ -135,8 +172,9 @@ def _evaluate_device(model, dataloader, params, mode, scorer, group):
         scores = scorer(model, batch, device)
         if mode == "vd_eval_val":
             with_rel = params.get("vd_version", "1.0") == "1.0" and "gt_relevance" in batch
-            dev.observe(scores, batch["gt_option_inds"], batch["gt_relevance"] if with_rel else None,
-                        batch["round_id"] if with_rel else None)
+            gt_inds, rel = (_gen_rows.eval_targets(batch, params, scores.device) if _gen_rows.is_pooled(batch)
+                            else (batch["gt_option_inds"], batch.get("gt_relevance")))
+            dev.observe(scores, gt_inds, rel if with_rel else None, batch["round_id"] if with_rel else None)
         else:
             for keep, t in zip(kept, (_metrics.scores_to_ranks_device(scores), batch["image_id"], batch["round_id"])):
                 keep.append(t)

@@ -1283,6 +1283,125 @@ def disc_rows(cap, ques, ans, opts, gt_index, row_dialog, row_round, row_slot, T
     return o
 
 
+GEN_MODES = {"eval": L.GEN_EVAL, "test": L.GEN_TEST, "train_a": L.GEN_TRAIN_A, "train_q": L.GEN_TRAIN_Q}
+_GEN_ENC = (("tokens", torch.int64, "T"), ("segments", torch.int64, "T"), ("mlm", torch.int64, "T"), ("att", torch.float32, "T"),
+            ("sep_indices", torch.int64, "S"))
+_GEN_DEC = (("dec_ids", torch.int64, "Ud"), ("dec_att", torch.float32, "Ud"), ("dec_labels", torch.int64, "Ud"))
+
+
+def gen_rows(cap, ques, ans, opts, gt_index, mode, T, Ud, enc_rows=None, dec_rows=None, num_options=None, mask_prob=0.0, u_tok=None,
+             cls=101, sep=102, mask=103, S=DIALOG_MAX_SEP, out=None):
+    """Encoder and decoder rows of the generative model from token-id pools in one launch (gstvd_gen_rows; the rule -- the loader
+    of dataloader/dataloader_visdial_gen.py on token ids -- is stated in include/gstvd_hip.h).
+    Pools, int64 and 0-padded: cap [D, Lc <= 64] (dense rows), ques / ans [D, R, U <= 64], opts [D, Ro, O <= 100, U] with Ro = R or
+    1 (row stride free, everything else dense), gt_index [D, R].  `mode`: "eval" (slot k is option k of the eval order, ground
+    truth first), "test" (slot k is option k; gt_index may be None), "train_a" / "train_q" (the target is the answer / the
+    question, the slot is 0; opts and gt_index may be None).  enc_rows: (dialog, round) int32 [n_enc] or None; dec_rows: (dialog,
+    round, slot) int32 [n_dec] or None.  u_tok fp32 [n_enc, T] (dense rows), required when mask_prob > 0.
+    Returns a dict: with encoder rows tokens, segments, mlm int64 [n_enc, T], att fp32 [n_enc, T], sep_indices int64 [n_enc, S],
+    hist_len int64 [n_enc]; with decoder rows dec_ids int64 [n_dec, Ud], dec_att fp32 [n_dec, Ud], dec_option int32 [n_dec] and, in
+    the train modes, dec_labels int64 [n_dec, Ud].  `out`: a dict of caller-owned tensors to write into instead (the four [n_enc, T]
+    arrays 2-D views of one row stride, the [n_dec, Ud] arrays of one, sep_indices a 2-D view, the rest contiguous)."""
+    who = "gen_rows"
+    if mode not in GEN_MODES:
+        raise L.GstvdError("%s: mode must be one of %s (got %r)" % (who, sorted(GEN_MODES), mode))
+    train = mode in ("train_a", "train_q")
+    need = [("ques", ques, 3), ("ans", ans, 3)] + ([] if train else [("opts", opts, 4)]) + ([("gt_index", gt_index, 2)] if mode == "eval" else [])
+    for name, t, nd in need:
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.dim() != nd:
+            raise L.GstvdError("%s: %s must be an int64 tensor of %d dimensions" % (who, name, nd))
+    if train:
+        opts = gt_index = None
+    elif mode == "test":
+        gt_index = None
+    D, R, U = ques.shape
+    T, Ud, S = int(T), int(Ud), int(S)
+    if tuple(ans.shape) != (D, R, U) or (gt_index is not None and tuple(gt_index.shape) != (D, R)):
+        raise L.GstvdError("%s: ques / ans [D, R, U] and gt_index [D, R] do not belong together: %s %s %s"
+                           % (who, tuple(ques.shape), tuple(ans.shape), None if gt_index is None else tuple(gt_index.shape)))
+    _rows_i64(who, "cap", cap)
+    if not (ques.is_contiguous() and ans.is_contiguous() and (gt_index is None or gt_index.is_contiguous())):
+        raise L.GstvdError("%s: ques, ans and gt_index must be contiguous" % who)
+    Lc = cap.shape[1]
+    if cap.shape[0] != D or D < 1 or not 1 <= U <= DIALOG_MAX_UTT or not 1 <= Lc <= DIALOG_MAX_UTT or T < 2 or Ud < 3:
+        raise L.GstvdError("%s: cap [D >= 1, Lc], 1 <= U, Lc <= %d, T >= 2 and Ud >= 3 (got D %d, U %d, Lc %d, T %d, Ud %d)"
+                           % (who, DIALOG_MAX_UTT, D, U, Lc, T, Ud))
+    if R < 1 or 2 * R > S or S > 64:
+        raise L.GstvdError("%s: %d rounds give %d separators, more than max_sep_len = %d allows (2R <= S <= 64)" % (who, R, 2 * R, S))
+    Ro = O = 0
+    so = (0, 0, U, 1)
+    if opts is not None:
+        Ro, O = opts.shape[1], opts.shape[2]
+        if opts.shape[0] != D or opts.shape[3] != U or Ro not in (R, 1):
+            raise L.GstvdError("%s: opts must be [D, R or 1, O, U] = [%d, %d or 1, O, %d] (got %s)" % (who, D, R, U, tuple(opts.shape)))
+        so = opts.stride()
+        # the kernel addresses row ((d * Ro + round) * O + c) * stride: the dialog stride counts whenever D > 1, also for Ro == 1
+        if D * Ro * O > 0 and ((U > 1 and so[3] != 1) or so[2] < U or (O > 1 and so[1] != O * so[2])
+                               or (D > 1 and so[0] != Ro * O * so[2])):
+            raise L.GstvdError("%s: opts must have dense rows of one stride (got strides %s)" % (who, so))
+        num_options = O if num_options is None else int(num_options)
+        if not 2 <= num_options <= O <= DISC_MAX_OPTIONS:
+            raise L.GstvdError("%s: 2 <= num_options <= O <= %d (got num_options %d, O %d)" % (who, DISC_MAX_OPTIONS, num_options, O))
+    lists = []
+    for name, rows, width in (("enc_rows", enc_rows, 2), ("dec_rows", dec_rows, 3)):
+        if rows is None:
+            lists.append(((None,) * width, 0))
+            continue
+        if len(rows) != width or not isinstance(rows[0], torch.Tensor) or rows[0].dim() != 1:
+            raise L.GstvdError("%s: %s must be %d int32 vectors of one length" % (who, name, width))
+        n = rows[0].numel()
+        for i, t in enumerate(rows):
+            _flag_vec(who, "%s[%d]" % (name, i), t, n, torch.int32)
+        lists.append((tuple(rows), n))
+    (enc_l, n_enc), (dec_l, n_dec) = lists
+    mask_prob = float(mask_prob)
+    if u_tok is None and mask_prob > 0.0:
+        raise L.GstvdError("%s: mask_prob = %g needs u_tok, one uniform per row position [n_enc, T]" % (who, mask_prob))
+    if u_tok is not None and _rows_i64(who, "u_tok", u_tok, T, torch.float32).shape[0] != n_enc:
+        raise L.GstvdError("%s: u_tok must be fp32 [n_enc = %d, T = %d]" % (who, n_enc, T))
+    dims = dict(T=T, S=S, Ud=Ud)
+    enc_out = _GEN_ENC if n_enc else ()
+    dec_out = tuple(v for v in _GEN_DEC if train or v[0] != "dec_labels") if n_dec else ()
+    vec = ((("hist_len", torch.int64, n_enc),) if n_enc else ()) + ((("dec_option", torch.int32, n_dec),) if n_dec else ())
+    if out is None:
+        _p(ques)
+        o = {k: torch.empty(n_enc if c != "Ud" else n_dec, dims[c], dtype=dtp, device=ques.device) for k, dtp, c in enc_out + dec_out}
+        for k, dtp, n in vec:
+            o[k] = torch.empty(n, dtype=dtp, device=ques.device)
+    else:
+        o = out
+        for k, dtp, c in enc_out + dec_out:
+            n = n_dec if c == "Ud" else n_enc
+            if _rows_i64(who, "out[%s]" % k, o[k], dims[c], dtp).shape[0] != n:
+                raise L.GstvdError("%s: out[%s] must have %d rows" % (who, k, n))
+        for k, dtp, n in vec:
+            _flag_vec(who, "out[%s]" % k, o[k], n, dtp)
+        for grp in (tuple(k for k, _, c in enc_out if c == "T"), tuple(k for k, _, _ in dec_out)):
+            if grp and len(set(o[k].stride(0) for k in grp)) != 1:
+                raise L.GstvdError("%s: %s must share one row stride" % (who, ", ".join(grp)))
+    d = L.GenRowsDesc()
+    d.cap, d.ld_cap, d.ques, d.ans, d.ld_utt = _p(cap), max(cap.stride(0), Lc), _p(ques), _p(ans), U
+    d.opts, d.ld_opt, d.gt_index = _p(opts), max(so[2], U), _p(gt_index)
+    d.enc_dialog, d.enc_round = _p(enc_l[0]), _p(enc_l[1])
+    d.u_tok, d.ld_u = _p(u_tok), (max(u_tok.stride(0), T) if u_tok is not None else 0)
+    if n_enc:
+        d.tokens, d.segments, d.mlm, d.att = _p(o["tokens"]), _p(o["segments"]), _p(o["mlm"]), _p(o["att"])
+        d.ld_row, d.sep_indices, d.ld_sep = max(o["tokens"].stride(0), T), _p(o["sep_indices"]), max(o["sep_indices"].stride(0), S)
+        d.hist_len = _p(o["hist_len"])
+    d.dec_dialog, d.dec_round, d.dec_slot = _p(dec_l[0]), _p(dec_l[1]), _p(dec_l[2])
+    if n_dec:
+        d.dec_ids, d.dec_att, d.ld_dec, d.dec_option = _p(o["dec_ids"]), _p(o["dec_att"]), max(o["dec_ids"].stride(0), Ud), _p(o["dec_option"])
+        d.dec_labels = _p(o["dec_labels"]) if train else None
+    d.mask_prob, d.cls, d.sep, d.mask_id, d.n_enc, d.n_dec = mask_prob, int(cls), int(sep), int(mask), n_enc, n_dec
+    d.D, d.R, d.Ro, d.O, d.U, d.Lc, d.T, d.S, d.Ud = D, R, Ro, O, U, Lc, T, S, Ud
+    d.num_options, d.mode = (num_options if opts is not None else 0), GEN_MODES[mode]
+    lib = L.load()
+    e0 = _prof_begin()
+    L.check("gstvd_gen_rows", lib.gstvd_gen_rows(C.byref(d), _stream()))
+    _prof_end(e0, "gen_rows", 0.0, n_enc * (T * 28.0 + S * 8.0) + n_dec * Ud * 12.0, (n_enc + n_dec, T))
+    return o
+
+
 RANK_MAX_OPTIONS = L.RANK_MAX_OPTIONS      # options of a list gstvd_rank_metrics covers (a lane owns options i and i + 64)
 RANK_ACC_SLOTS = L.RANK_ACC_SLOTS          # int64 slots of its accumulator: the counts, the bits of the float64 ndcg sum, hist[0..128]
 RANK_N_SPARSE, RANK_N_GT_SKIPPED, RANK_N_NDCG, RANK_N_NDCG_EMPTY = L.RANK_N_SPARSE, L.RANK_N_GT_SKIPPED, L.RANK_N_NDCG, L.RANK_N_NDCG_EMPTY

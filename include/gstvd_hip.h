@@ -794,6 +794,69 @@ typedef struct {
 } gstvd_disc_rows_t;
 int gstvd_disc_rows(const gstvd_disc_rows_t* a, gstvd_stream_t s);
 
+/* ---- generative rows (entry point added, no signature changed: ABI stays 9) -----------------------------------------------------
+ * gstvd_gen_rows: the rows of the generative (enc_dec) model -- what dataloader/dataloader_visdial_gen.py builds per dialog with a
+ * tokenizer and Python lists (eval rows :295-458, test rows :507-603, teacher rows :123-293) through utils/data_utils.py:34-71
+ * (encode_input) -- from token-id pools, in ONE launch without atomics, workspace, allocation or host synchronisation
+ * (capture-safe).  Every output element is written exactly once: nothing needs zeroing in front.
+ * Pools (int64, 0-padded, no [CLS] / [SEP] inside): cap [D, Lc] (row stride ld_cap); ques, ans [D, R, U] (row stride ld_utt
+ * between the D * R rows; ans = the ground-truth answers); opts [D, Ro, O, U] with Ro == R or Ro == 1 (row stride ld_opt between
+ * the D * Ro * O rows); gt_index int64 [D, R].  opts is read in the modes EVAL and TEST only, gt_index in EVAL only; each may be
+ * NULL elsewhere.  An utterance is the entries in front of the row's first 0 (all of them when there is none); it may be empty and
+ * then contributes a lone [SEP].
+ * One launch takes two independent row lists; either may be empty (n == 0), and then its pointers may be NULL.
+ * Encoder rows: enc_dialog, enc_round int32 [n_enc]; u_tok fp32 [n_enc, T] (row stride ld_u; may be NULL when mask_prob == 0).
+ *   Outputs: tokens, segments, mlm int64 [n_enc, T] and att fp32 [n_enc, T] (one row stride ld_row, in elements of each);
+ *   sep_indices int64 [n_enc, S] (ld_sep); hist_len int64 [n_enc].
+ *   Context of (d, j): caption, q0, a0, ..., q(j-1), a(j-1), qj -- 2j + 2 utterances; in mode TRAIN_Q caption, q0, a0, ...,
+ *     a(j-1) -- 2j + 1 utterances (the questioner's context ends at the previous answer).  hist_len = utterances - 1.  The gen
+ *     loader never calls pruneRounds: the row starts at segment 1 and nothing is dropped.
+ *   encode_input: [CLS] opens the row, every utterance is followed by [SEP], the segment flips after every utterance ([CLS] and each
+ *     [SEP] carry their utterance's segment), the row is cut at T (which may lose the last [SEP], or more) and padded with 0
+ *     (segments 0, mlm -1).  sep_indices: the running separator positions, 0-padded to S, NOT cut at T.
+ *   [MASK] noise: an utterance token at position p < T is masked iff (double)u_tok[r, p] < mask_prob (strict, in double): tokens =
+ *     mask_id and mlm = the original id (no 80 / 10 / 10 rule); everything else has mlm = -1.
+ *   att[t] = (tokens[t] != 0), after the noise.
+ *   A row whose d or j is out of range reads no pool: it is written as padding (tokens, segments, att, sep_indices, hist_len 0;
+ *     mlm -1).
+ * Decoder rows: dec_dialog, dec_round, dec_slot int32 [n_dec].
+ *   Outputs: dec_ids int64 [n_dec, Ud] and dec_att fp32 [n_dec, Ud] (one row stride ld_dec); dec_option int32 [n_dec]; in the train
+ *   modes dec_labels int64 [n_dec, Ud] (ld_dec; not touched and may be NULL otherwise).
+ *   The target x, cut to its first Ud - 2 tokens; the row is [CLS] x [SEP], 0-padded to Ud; dec_att = (row != 0) at this point.
+ *     GSTVD_GEN_EVAL (:303-355, :390-399): x = option c of round j with c = gt if slot == 0, else the (slot - 1)-th index of
+ *       {0..O-1} \ {gt} in increasing order; 0 <= slot < num_options; dec_option = c; dec_ids = the row ([SEP] kept).
+ *     GSTVD_GEN_TEST (:519-557): x = option `slot` of round j (of the pool's only round when Ro == 1), original order; 0 <= slot <
+ *       num_options; gt_index is not read; dec_option = slot; dec_ids = the row.
+ *     GSTVD_GEN_TRAIN_A (:164-169, :226-230): x = ans[d, j]; the slot must be 0; dec_option = -1; dec_labels[:-1] = row[1:],
+ *       dec_labels[-1] = 0; then every element of dec_ids equal to sep becomes 0.
+ *     GSTVD_GEN_TRAIN_Q (:142-147): x = ques[d, j]; otherwise as TRAIN_A.
+ *   A row whose d, j or slot is out of range, or (EVAL) whose gt_index[d, j] is outside [0, O), reads no pool: it is written as
+ *     padding (dec_ids, dec_att, dec_labels 0; dec_option -1).
+ * Limits: 1 <= U, Lc <= 64; R >= 1 and 2R <= S <= 64 (S = 25, the loader's max_sep_len: R <= 12); T >= 2; Ud >= 3; in EVAL and TEST
+ * 2 <= num_options <= O <= 100 and Ro in {R, 1}.  Refused before the launch, nothing written, in this order: a null required pointer,
+ * mask_prob > 0 without u_tok (GSTVD_E_NULL); a mode that is none, a shape outside the limits, n_enc or n_dec < 0 or their sum above
+ * 2^31 - 1 (GSTVD_E_SHAPE); a row stride below its row (GSTVD_E_SHAPE). */
+enum { GSTVD_GEN_EVAL = 0, GSTVD_GEN_TEST = 1, GSTVD_GEN_TRAIN_A = 2, GSTVD_GEN_TRAIN_Q = 3 };
+typedef struct {
+  const int64_t* cap; int64_t ld_cap;
+  const int64_t* ques; const int64_t* ans; int64_t ld_utt;
+  const int64_t* opts; int64_t ld_opt;
+  const int64_t* gt_index;
+  const int32_t* enc_dialog; const int32_t* enc_round;
+  const float* u_tok; int64_t ld_u;
+  int64_t* tokens; int64_t* segments; int64_t* mlm; float* att; int64_t ld_row;
+  int64_t* sep_indices; int64_t ld_sep; int64_t* hist_len;
+  const int32_t* dec_dialog; const int32_t* dec_round; const int32_t* dec_slot;
+  int64_t* dec_ids; int64_t* dec_labels; float* dec_att; int64_t ld_dec;
+  int32_t* dec_option;
+  double mask_prob;
+  int64_t cls; int64_t sep; int64_t mask_id;
+  int64_t n_enc; int64_t n_dec;
+  int32_t D; int32_t R; int32_t Ro; int32_t O; int32_t U; int32_t Lc; int32_t T; int32_t S; int32_t Ud;
+  int32_t num_options; int32_t mode; int32_t reserved_;
+} gstvd_gen_rows_t;
+int gstvd_gen_rows(const gstvd_gen_rows_t* a, gstvd_stream_t s);
+
 /* ---- ranking metrics (entry point added, no signature changed: ABI stays 9) ------------------------------------------------------
  * gstvd_rank_metrics: L score lists of O options -> the rank of every option, the rank of the ground truth, the NDCG ratio of the
  * list and additions to a device-resident accumulator: what utils/visdial_metrics.py computes on the host per batch
